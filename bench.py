@@ -13,8 +13,18 @@ the complex64 channel tensor (104.9 GB per GPU) is written to HBM by every step.
 block-partitioned over ranks with no data-path collective (weak scaling: per-GPU work is fixed).
 
 Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events around the stage-2
-kernel on the stream it is launched on; `cpu_baseline` times the NumPy oracle's reference-style
-per-user loop (oracle/oracle_np.py, style='reference') on a bounded user sample on this host.
+kernel on the stream it is launched on.  A plain run sets up, warms up, times the steps and prints
+the line; `--full` adds the legs beside the headline figure: the same launches with the opt-in
+adaptive-precision flag (`roofline.kernel_ms_adaptive_terms`) and `cpu_baseline`, which times the
+NumPy oracle's reference-style per-user loop (oracle/oracle_np.py, style='reference') and the
+plain-C port on a bounded user sample on this host.
+
+    python bench.py --full                              # every leg (profiles/ lines)
+    python bench.py --steps 5 --dump-outputs out/       # + what the last timed step computed, as .npy
+
+`--dump-outputs DIR` writes, after the timed steps, the arrays a caller of the timed path receives
+(rank 0's shard) as DIR/<name>.npy in float32; see dump_outputs().  The inputs are seeded, so two
+builds given the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -58,6 +68,43 @@ WORKLOADS = {
     # DeepMIMO's default arrays.  A different kind of bench line: see bench_loader().
     "load_asu_shape": dict(n_ue=131_931, bs=[8, 1], ue=[1, 1], L=25, N=512, loader=True),
 }
+
+
+DUMP_BYTES = 64 << 20       # --dump-outputs: at most this many bytes in all
+DUMP_WHOLE_BYTES = 8 << 20  # past DUMP_BYTES in all, arrays above this size share one seeded user sample
+
+
+def dump_outputs(out_dir, arrays):
+    """Write `arrays` ({name: torch tensor or ndarray, users on axis 0}) as out_dir/<name>.npy in float32: complex
+    values get a trailing [re, im] axis, integer side products are exact in float32.  When the whole set is larger than
+    DUMP_BYTES, the arrays larger than DUMP_WHOLE_BYTES are reduced to one fixed, seeded sample of users (the same rows
+    for every such array, the indices written as users_sampled.npy) so that the files stay within DUMP_BYTES."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+
+    def f32_bytes(v):
+        return v.numel() * (8 if v.is_complex() else 4) if torch.is_tensor(v) else np.asarray(v).size * (8 if np.iscomplexobj(v) else 4)
+
+    whole = sum(f32_bytes(v) for v in arrays.values()) <= DUMP_BYTES
+    small = {k: v for k, v in arrays.items() if whole or f32_bytes(v) <= DUMP_WHOLE_BYTES}
+    big = {k: v for k, v in arrays.items() if k not in small}
+    users = None
+    if big:
+        n = int(next(iter(big.values())).shape[0])
+        per_user = sum(f32_bytes(v) // max(1, int(v.shape[0])) for v in big.values())
+        room = DUMP_BYTES - sum(f32_bytes(v) for v in small.values()) - 8 * n
+        k = max(1, min(n, room // max(1, per_user)))
+        users = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    for name, v in arrays.items():
+        if name in big:
+            v = v.index_select(0, torch.from_numpy(users).to(v.device)) if torch.is_tensor(v) else np.asarray(v)[users]
+        if torch.is_tensor(v):
+            v = (torch.view_as_real(v) if v.is_complex() else v).cpu().numpy()
+        v = np.asarray(v)
+        v = np.stack([v.real, v.imag], axis=-1) if np.iscomplexobj(v) else v
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+    if users is not None:
+        np.save(os.path.join(out_dir, "users_sampled.npy"), users.astype(np.float64))
 
 
 def synth_device_rays(n_ue, L, seed, device, all_valid=True, doppler=False):
@@ -152,7 +199,7 @@ def bench_loader(args, w, dev):
             t2 = time.perf_counter()
             assert tuple(H.shape) == (n, 1, w["bs"][0] * w["bs"][1], w["N"]) and bool(torch.isfinite(torch.view_as_real(H[:: max(1, n // 64)])).all())
             los = ds.los
-            return t1 - t0, t2 - t1, ds, los
+            return t1 - t0, t2 - t1, ds, los, H
 
         import contextlib
         import io
@@ -161,9 +208,11 @@ def bench_loader(args, w, dev):
                 one_step()
             loads, gens = [], []
             for _ in range(max(1, args.steps)):
-                a, b, ds, _ = one_step()
+                a, b, ds, los, H = one_step()
                 loads.append(a)
                 gens.append(b)
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, {"channel": H, "los": los, "num_paths": ds.num_paths})
             # the parts of the device path, one field at a time: file pages -> HBM (as stored), then the layout kernel
             path = os.path.join(folder, dm.core.get_mat_filename("power", 0, 0, 1))
             evs = []
@@ -359,12 +408,16 @@ def main():
     ap.add_argument("--workload", default="c3_headline", choices=sorted(WORKLOADS))
     ap.add_argument("--variant", type=int, default=0, help="0 auto, 1 fp32 vector kernel, 2 MFMA kernel, 9 small-output, 12 folded")
     ap.add_argument("--users", type=int, default=0, help="override users per GPU")
-    ap.add_argument("--cpu-users", type=int, default=-1, help="CPU baseline sample size (0 = skip)")
+    ap.add_argument("--cpu-users", type=int, default=-1, help="CPU baseline sample size (0 = skip; --full only)")
     ap.add_argument("--random-valid", action="store_true", help="valid paths per user uniform in 0..L")
-    ap.add_argument("--skip-adaptive", action="store_true", help="no extra launches with the opt-in adaptive-precision flag (profiling runs: one kind of launch only)")
+    ap.add_argument("--skip-adaptive", action="store_true", help="--full without the extra launches with the opt-in adaptive-precision flag")
     ap.add_argument("--cpu-workers", type=int, default=-1, help="processes of the all-cores CPU figure (default min(16, cores))")
     ap.add_argument("--gather", action="store_true", help="N > 1: also time the side-product all_gather and a bounded channel-slice gather to rank 0")
     ap.add_argument("--gather-users", type=int, default=2048, help="users per rank in the gathered channel slice")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beside the headline figure: the adaptive-precision launches and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32, <= 64 MB)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_workers < 0:
@@ -467,11 +520,11 @@ def main():
         if ev1 is not None:
             ev1.record(torch.cuda.current_stream(dev))
 
-    # the same two calls with the opt-in DMX_FLAG_ADAPTIVE_TERMS (a user's weak last path group in one product term),
-    # BEFORE the warm-up and the timed region and outside both: reported beside the timed number.  The flag is a field of
-    # the parameter block of a second preparation - nothing in the process changes.
+    # --full: the same two calls with the opt-in DMX_FLAG_ADAPTIVE_TERMS (a user's weak last path group in one product
+    # term), BEFORE the warm-up and the timed region and outside both: reported beside the timed number.  The flag is a
+    # field of the parameter block of a second preparation - nothing in the process changes.
     k2_ms_ad = None
-    if args.steps and not (w.get("td") or w.get("lpf")) and not args.skip_adaptive:
+    if args.full and args.steps and not (w.get("td") or w.get("lpf")) and not args.skip_adaptive:
         prep_ad = eng.prepare(rays, params, want_side="light", carrier_freq=CARRIER_HZ if dop else 0.0, adaptive_terms=True)
         for _ in range(8):                                         # the chip ramps its clocks over the first launches: a fair
             step(prep=prep_ad)                                     # comparison needs this leg as warm as the timed one below
@@ -506,6 +559,11 @@ def main():
     chk = out[:: max(1, n_ue // 64)]
     chk = torch.view_as_real(chk) if chk.is_complex() else chk
     assert bool(torch.isfinite(chk).all()) and float(chk.abs().max()) > 0, "bench output is not finite / all zero"
+    if args.dump_outputs and rank == 0:
+        res_arrays = {"beam_mean_amplitude": out, "best_beam": best} if n_beams else {"channel": out}
+        for k in ("los", "num_paths", "fov_mask"):                 # the "light" side products stage 1 wrote
+            res_arrays[k] = prep0.side.get(k)
+        dump_outputs(args.dump_outputs, res_arrays)
 
     total_users = n_ue * world
     step_s = elapsed / max(args.steps, 1)
@@ -573,7 +631,7 @@ def main():
     if dist and args.gather:
         res["gather"] = gather_leg(dist, eng, rays, params, out, n_ue, world, rank, dev, args.gather_users,
                                    CARRIER_HZ if dop else 0.0)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         cpu_users = args.cpu_users if args.cpu_users >= 0 else {"c3_headline": 400, "c2_asu_shape": 2000, "c4_shard": 400,
                                                                 "c5_massive": 8, "d8_default_arrays": 8000, "d16_k256": 8000, "d64_k256": 3000, "c3_time_domain": 20000, "c3_rx_filter": 200,
                                                                 "c3_beam_power": 300, "tiny": 100}[args.workload]

@@ -193,7 +193,6 @@ def test_batch_forms_equal_scalar_forms():
 # ---- the committed recipes must keep running (crosscheck_reference.py had rotted unnoticed) -------------
 ORACLE_SCRIPTS = ("gen_golden", "gen_p2m_golden", "gen_sequence_golden", "gen_aux_golden", "gen_helpers_golden", "crosscheck_reference",
                   "certify_baseline", "oracle_np", "oracle_c")
-REFERENCE = "/root/reference"
 
 
 def test_every_oracle_script_imports():
@@ -208,44 +207,19 @@ def test_every_oracle_script_imports():
         assert name in ("oracle_np", "oracle_c") or callable(getattr(mod, "main"))
 
 
-def _run_recipe(script, *args, timeout=600):
-    import subprocess
-    import sys
+def test_crosscheck_against_recorded_reference():
+    """oracle_np vs what the imported reference returned on the first random configurations of the GPU sweep
+    (tests/golden/crosscheck_reference.npz, recorded by oracle/crosscheck_reference.py --save): side products exact,
+    sampled channel elements and per-user peaks within 1e-7, and every channel bit-identical (SHA-256 of its values)."""
+    from oracle import crosscheck_reference as xr
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PYTHONPATH=f"{REFERENCE}:{root}", PYTHONDONTWRITEBYTECODE="1", MPLBACKEND="Agg")
-    return subprocess.run([sys.executable, os.path.join(root, "oracle", script), *args], cwd="/tmp", env=env,
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout)
-
-
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="the reference exists in the build container only")
-def test_crosscheck_against_imported_reference():
-    """oracle_np vs the imported reference on the first random configurations of the GPU sweep: bit-identical."""
-    r = _run_recipe("crosscheck_reference.py", "10")
-    assert r.returncode == 0, r.stdout[-2000:]
-    assert "oracle == reference on 10 random configurations; worst |dH|/peak = 0.00e+00" in r.stdout
-
-
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="the reference exists in the build container only")
-def test_aux_goldens_regenerate_bit_identically(tmp_path):
-    """tests/golden/aux_*.npz are what the reference returns today (the generator is deterministic)."""
-    import shutil
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    gold = os.path.join(root, "tests", "golden")
-    names = ["aux_steering.npz", "aux_pathloss.npz", "aux_sionna.npz", "aux_stale_cache.npz", "aux_helpers.npz"]
-    keep = {n: dict(np.load(os.path.join(gold, n), allow_pickle=False)) for n in names}
-    backup = tmp_path / "backup"
-    backup.mkdir()
-    for n in names:
-        shutil.copy(os.path.join(gold, n), backup / n)
-    try:
-        for script in ("gen_aux_golden.py", "gen_helpers_golden.py"):
-            r = _run_recipe(script)
-            assert r.returncode == 0, r.stdout[-2000:]
-        for n in names:
-            new = np.load(os.path.join(gold, n))
-            assert sorted(new.files) == sorted(keep[n])
-            for k in new.files:
-                assert np.array_equal(new[k], keep[n][k], equal_nan=new[k].dtype.kind in "fc"), (n, k)
-    finally:
-        for n in names:                                            # leave the committed bytes untouched
-            shutil.copy(backup / n, os.path.join(gold, n))
+    z = np.load(os.path.join(root, "tests", "golden", "crosscheck_reference.npz"))
+    n_cfg = int(z["n_cfg"])
+    assert n_cfg == 10
+    worst, same = 0.0, []
+    for seed in range(n_cfg):
+        ref = {k[len(f"s{seed}_"):]: z[k] for k in z.files if k.startswith(f"s{seed}_")}
+        w, ok = xr.check(seed, ref)
+        worst = max(worst, w)
+        same.append(ok)
+    assert worst == 0.0 and all(same), f"oracle != reference: worst |dH|/peak {worst:.2e}, bit-identical {same}"
