@@ -40,6 +40,7 @@ struct MfmaArgs {
     int M;           // antenna pairs
     int K;           // selected subcarriers
     const int32_t* sc;
+    int sc_first, sc_stride;  // GSRC = 4: sc[k] = sc_first + k * sc_stride (host promise, dmx_params)
     double inv_n;
     int nblk;        // row blocks per user
     int rows;        // LDS rows (multiple of 32)
@@ -217,6 +218,29 @@ __device__ __forceinline__ void strip_tiles(int ntiles, const unsigned char* Ahi
     }
 }
 
+// What a GSRC = 4 strip needs to build its fragments (fact_b_strip); unused by the other gain sources
+struct FactStrip {
+    float m1;
+    FactLane fl;
+    const float* c1;
+    const float* e2;
+    bool pack;               // the last K-step is packed (stage_item)
+};
+
+// One strip of the tile-loop kernels (MODE 1, 2).  With GSRC = 4 the strip's fragments are built here first, with the
+// step count and packing of the tile body they go to, both known at compile time (a run-time tail step put a branch into
+// every step and pushed the pipelined kernel into spilling).  LW = a one-MFMA last K-step: packed, or weak (adaptive).
+template <bool NT, int NS, bool PIPE, bool LW, int GSRC>
+__device__ __forceinline__ void strip_case(const FactStrip& fs, int ntiles, const unsigned char* Ahi, const unsigned char* Alo, int col,
+                                           int hh, h8 (&Bhi)[4], h8 (&Blo)[4], const BLane& bl, __amdgpu_buffer_rsrc_t orsrc,
+                                           unsigned row_bytes, float oscale) {
+    if constexpr (GSRC == 4) {
+        if (LW && fs.pack) fact_b_strip<NS, LW>(fs.m1, fs.fl, hh, fs.c1, fs.e2, Bhi, Blo);
+        else fact_b_strip<NS, false>(fs.m1, fs.fl, hh, fs.c1, fs.e2, Bhi, Blo);
+    }
+    strip_tiles<NT, NS, PIPE, LW>(ntiles, Ahi, Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale);
+}
+
 // What one (user, row block) work item keeps in LDS: the A' hi / lo tiles and the per-user path tables.
 struct ItemLds {
     unsigned char* Ahi;      // [rows][144 B]
@@ -225,8 +249,12 @@ struct ItemLds {
     float* crtab;            // [32] scaled c_l
     float* citab;
     float* misc;             // [4]  per-user output / operand scales
+    float* e2tab;            // GSRC = 4 only: E2 of the item (fact_b_step)
+    float* c1tab;            // GSRC = 4 only: this wave's C1 of its current strip
 };
 __host__ __device__ inline size_t item_lds_bytes(int rows) { return (size_t)2 * rows * ROW_BYTES + LPAD * (8 + 4 + 4) + 16; }
+// the factorised tables behind the item's: 4576 B + 384 B per wave (8 waves x 256 rows: 81904 B, two workgroups per CU)
+__host__ __device__ inline size_t fact_lds_bytes(int nw) { return (size_t)FACT_E2_BYTES + (size_t)nw * FACT_C1_BYTES; }
 __device__ __forceinline__ ItemLds item_lds(unsigned char* base, int rows) {
     ItemLds L;
     L.Ahi = base;
@@ -235,6 +263,8 @@ __device__ __forceinline__ ItemLds item_lds(unsigned char* base, int rows) {
     L.crtab = reinterpret_cast<float*>(L.qtab + LPAD);
     L.citab = L.crtab + LPAD;
     L.misc = L.citab + LPAD;
+    L.e2tab = reinterpret_cast<float*>(base + item_lds_bytes(rows));
+    L.c1tab = reinterpret_cast<float*>(base + item_lds_bytes(rows) + FACT_E2_BYTES) + (threadIdx.x >> 6) * (FACT_C1_BYTES / 4);
     return L;
 }
 
@@ -259,12 +289,17 @@ __device__ __forceinline__ ItemPos item_pos(const WsView& ws, const MfmaArgs& a,
 // Stage 1 of a work item: the per-user tables (wave 0) and the A' tiles (thread = antenna pair x slice of the path
 // slots) into `L`.  No barrier inside; nothing here reads what another thread of this call wrote.
 // NW = waves per workgroup (4, 8 or 16).
-template <int NW>
+// GSRC = 4 (factorised B'): also the item's E2 table, and a last K-step that holds at most 2 kept paths is PACKED -
+// its three product terms side by side in one K16 step, A' slots [hi(l) | hi(l) | lo(l) | 0] against B' rows
+// [hi; lo; hi; x] (fact_b_step): one MFMA instead of three, the products as exact as before.
+template <int NW, int GSRC>
 __device__ __forceinline__ void stage_item(const WsView& ws, const MfmaArgs& a, int64_t work, const ItemLds& L) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const ItemPos ip = item_pos(ws, a, work);
     const int n_act = ip.n_act;
     if (n_act == 0) return;                                              // consume_item writes zeros, reads nothing
+    const int l0w = ((n_act - 1) >> 3) << 3;                             // first path of the last K-step
+    const bool pack = GSRC == 4 && n_act - l0w <= 2;
     // uniform per-item bases and 32-bit path indices: indexed as array[row base + l] the compiler keeps eight 64-bit
     // per-lane offsets alive across the whole item loop (16 VGPRs the tile loops need)
     const float* __restrict__ c_re = ws.c_re + ip.rb;
@@ -286,7 +321,6 @@ __device__ __forceinline__ void stage_item(const WsView& ws, const MfmaArgs& a, 
         // 2^-21, i.e. at most 8 paths x 2^-20 = 7.6e-6 of the strongest path's amplitude in the worst case (1e-6 rms), next
         // to the 2e-6 the 3-term products leave and the 5e-5 tolerance (test_adaptive_precision_weak_tail_worst_case).
         // Saves 2 of the 12 MFMAs per tile whenever the last K-step is weak (25 kept paths: it holds the weakest one).
-        const int l0w = ((n_act - 1) >> 3) << 3;
         float a2 = 0.f;
         if (lane < n_act) a2 = fmaf(c_re[lane], c_re[lane], c_im[lane] * c_im[lane]);
         float m2 = a2, mw2 = lane >= l0w ? a2 : 0.f;
@@ -295,7 +329,8 @@ __device__ __forceinline__ void stage_item(const WsView& ws, const MfmaArgs& a, 
         int e;
         (void)frexpf(m, &e);                                             // m = f * 2^e, f in [0.5, 1)
         const float gs = ldexpf(1.0f, 10 - e);
-        if (lane == 0) L.misc[3] = last_weak ? 1.f : 0.f;
+        // a packed last K-step takes the one-MFMA tile bodies of the weak one (with all three product terms)
+        if (lane == 0) L.misc[3] = (last_weak || pack) ? 1.f : 0.f;
         if (lane < LPAD) {
             const bool ok = lane < n_act;
             const double q = ok ? (double)dnp[lane] * a.inv_n : 0.0;
@@ -310,6 +345,16 @@ __device__ __forceinline__ void stage_item(const WsView& ws, const MfmaArgs& a, 
         // rx_filter: |G| can exceed |c| by the sinc sum (a few x); two bits of headroom keep G*gs < 2^13
         if (a.gtab || a.gpack) e += 2;
         if (lane == 0) { L.misc[0] = ldexpf(1.0f, e - 10 - ea); L.misc[1] = ldexpf(1.0f, ea); L.misc[2] = ldexpf(1.0f, 10 - e); }
+    }
+    if constexpr (GSRC == 4) {
+        // E2[l,b] = exp(-j2pi q_l stride b): the phase in float64 (q_l stride b < 2^25 revolutions), then reduced
+        for (int i = tid; i < LPAD * 16; i += NW * 64) {
+            const int l = i & (LPAD - 1), b = i >> 5;
+            float s = 0.f, c = 1.f;
+            if (l < n_act) sincos_rev(frac_rev((double)dnp[l] * a.inv_n * (double)(a.sc_stride * b)), s, c);
+            L.e2tab[FACT_E2_ROW * b + l] = c;
+            L.e2tab[FACT_E2_ARR + FACT_E2_ROW * b + l] = -s;
+        }
     }
 
     constexpr int LSPLIT = NW / 4, LPER = LPAD / LSPLIT;
@@ -340,14 +385,21 @@ __device__ __forceinline__ void stage_item(const WsView& ws, const MfmaArgs& a, 
         }
     } else {
         for (int l = l0; l < l0 + LPER; ++l) {
+            int src = l;                                                 // path whose value goes into slot l
+            bool lo_slot = false;
+            if (pack && l >= l0w) {                                      // packed last K-step: slots j = 0..7 of the step
+                const int j = l - l0w;                                   // hold hi(l0w), hi(l0w+1) twice, lo(..), 0, 0
+                src = j < 6 ? l0w + (j & 1) : LPAD;
+                lo_slot = j >= 4;
+            }
             h2 vh = {(_Float16)0.f, (_Float16)0.f}, vl = vh;
-            if (pok && l < n_act) {
-                const double ph = yr * rx_y[l] + zr * rx_z[l] + yt * tx_y[l] + zt * tx_z[l];
+            if (pok && src < n_act) {
+                const double ph = yr * rx_y[src] + zr * rx_z[src] + yt * tx_y[src] + zt * tx_z[src];
                 float s, c;
                 sincos_rev(frac_rev(ph), s, c);
                 split2_f16(c * A_SCALE, s * A_SCALE, vh, vl, ws.neg_one);
             }
-            rhi[l] = vh;
+            rhi[l] = lo_slot ? vl : vh;
             rlo[l] = vl;
         }
     }
@@ -487,10 +539,42 @@ __device__ __forceinline__ bool consume_item(const WsView& ws, const MfmaArgs& a
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // behind the item's barrier nothing else is in flight
         }
     }
+    const int tail_s = (n_act - 1) >> 3;                                 // GSRC = 4: last K-step, packed if it holds <= 2 paths
+    const bool pack = n_act - 8 * tail_s <= 2;
     for (int strip = wave; strip < nstrips; strip += NW) {
-        const BLane bl = b_lane(strip, col, hh, twoK, a.sc);
+        const BLane bl = b_lane(strip, col, hh, twoK, GSRC == 4 ? nullptr : a.sc);
         h8 Bhi[4], Blo[4];
-        if constexpr (GSRC == 3) {
+        FactLane fl{0, 0};
+        if constexpr (GSRC == 4) {
+            // c_l E1[l, strip] for the wave: lane l, the phase reduced as in gen_b_step (k = the strip's first subcarrier)
+            if (lane < LPAD) {
+                const unsigned k1 = (unsigned)a.sc_first + (unsigned)(16 * strip) * (unsigned)a.sc_stride;
+                const float2 q = L.qtab[lane];
+                const float p1 = q.x * (float)(k1 & 4095u);
+                float sn, cs;
+                sincos_rev(fmaf(q.y, (float)k1, p1 - rintf(p1)), sn, cs);
+                const float cr = L.crtab[lane], ci = L.citab[lane];
+                const float ur = cr * cs + ci * sn, ui = ci * cs - cr * sn;
+                L.c1tab[lane] = ur;
+                L.c1tab[LPAD + lane] = ui;
+                L.c1tab[2 * LPAD + lane] = -ur;
+            }
+            // the table is the wave's own: LDS operations of one wave complete in order
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            fl = fact_lane(bl.c, col >> 1, hh);
+            asm volatile("" : "+v"(fl.u), "+v"(fl.er));                 // see fact_lane
+            if constexpr (MODE == 0) {                                   // run-time guarded tiles: all four steps here
+#pragma unroll
+                for (int st = 0; st < 4; ++st) {
+                    Bhi[st] = h8{0, 0, 0, 0, 0, 0, 0, 0};
+                    Blo[st] = Bhi[st];
+                    if (8 * st < n_act)
+                        fact_b_step(ws.neg_one, st, fl, hh, pack && st == tail_s, L.c1tab, L.e2tab, Bhi[st], Blo[st]);
+                }
+            }                                                            // MODE 1 / 2: in strip_case
+        } else if constexpr (GSRC == 3) {
             const uint2* urow = a.gpack + (size_t)tul * ws.P * a.K;
             if (strip != wave) wait_dma_behind_stores(ntiles);
             read_b_slot(slot, col, hh, bl.c, n_act, Bhi, Blo);
@@ -526,14 +610,17 @@ __device__ __forceinline__ bool consume_item(const WsView& ws, const MfmaArgs& a
         }
         if constexpr (MODE != 0) {
             constexpr bool PIPE = MODE == 2;
-            switch (((n_act + 7) >> 3) + (last_weak ? 4 : 0)) {           // workgroup-uniform
-                case 1: strip_tiles<NT, 1, PIPE, false>(ntiles, L.Ahi, L.Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale); break;
-                case 2: strip_tiles<NT, 2, PIPE, false>(ntiles, L.Ahi, L.Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale); break;
-                case 3: strip_tiles<NT, 3, PIPE, false>(ntiles, L.Ahi, L.Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale); break;
-                case 4: strip_tiles<NT, 4, PIPE, false>(ntiles, L.Ahi, L.Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale); break;
-                case 6: strip_tiles<NT, 2, PIPE, true>(ntiles, L.Ahi, L.Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale); break;
-                case 7: strip_tiles<NT, 3, PIPE, true>(ntiles, L.Ahi, L.Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale); break;
-                default: strip_tiles<NT, 4, PIPE, true>(ntiles, L.Ahi, L.Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale); break;
+            const FactStrip fs{ws.neg_one, fl, L.c1tab, L.e2tab, pack};
+            switch (((n_act + 7) >> 3) + (last_weak ? 4 : 0)) {           // workgroup-uniform; last_weak includes pack
+                case 1: strip_case<NT, 1, PIPE, false, GSRC>(fs, ntiles, L.Ahi, L.Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale); break;
+                case 2: strip_case<NT, 2, PIPE, false, GSRC>(fs, ntiles, L.Ahi, L.Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale); break;
+                case 3: strip_case<NT, 3, PIPE, false, GSRC>(fs, ntiles, L.Ahi, L.Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale); break;
+                case 4: strip_case<NT, 4, PIPE, false, GSRC>(fs, ntiles, L.Ahi, L.Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale); break;
+                // one K-step whose last step is short: only a packed one (the adaptive rule needs two steps or more)
+                case 5: strip_case<NT, 1, PIPE, true, GSRC>(fs, ntiles, L.Ahi, L.Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale); break;
+                case 6: strip_case<NT, 2, PIPE, true, GSRC>(fs, ntiles, L.Ahi, L.Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale); break;
+                case 7: strip_case<NT, 3, PIPE, true, GSRC>(fs, ntiles, L.Ahi, L.Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale); break;
+                default: strip_case<NT, 4, PIPE, true, GSRC>(fs, ntiles, L.Ahi, L.Alo, col, hh, Bhi, Blo, bl, orsrc, row_bytes, oscale); break;
             }
         } else {
             const int n_full = ((n_act + 7) >> 3) - (last_weak ? 1 : 0);
@@ -552,7 +639,7 @@ __global__ __launch_bounds__(NW * 64, 4) void k2_fd_mfma(WsView ws, MfmaArgs a, 
     const ItemLds L = item_lds(smem, a.rows);
     bool prefetched = false;                                             // GSRC = 3, per wave: see consume_item
     for (int64_t w = blockIdx.x; w < total; w += gridDim.x) {
-        stage_item<NW>(ws, a, w, L);
+        stage_item<NW, GSRC>(ws, a, w, L);
         __syncthreads();
         prefetched = consume_item<NT, NW, MODE, GSRC>(ws, a, out, w, (w + gridDim.x < total) ? w + gridDim.x : (int64_t)-1, L, prefetched);
         __syncthreads();                                                 // the next item's tiles overwrite these
@@ -784,6 +871,8 @@ template <bool NT, int NW, int MODE = 0, int GSRC = 0>
 static int launch_mfma_t(const WsView& ws, const MfmaArgs& a, int64_t blocks, size_t smem, float2* out, hipStream_t stream,
                          bool persistent = true, int items_per_wg = ITEMS_PER_WG) {
     const void* kfn = reinterpret_cast<const void*>(k2_fd_mfma<NT, NW, MODE, GSRC>);
+    static_assert(GSRC != 4 || NW <= 8, "the factorised tables of 16 waves do not fit beside 256 rows of A'");
+    if constexpr (GSRC == 4) smem += fact_lds_bytes(NW);
     if (smem > 64 * 1024) {     // per device and cheap: no cached flag, so every GPU of a process gets it
         hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, MFMA_LDS_MAX);
         if (e != hipSuccess) { set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
@@ -877,6 +966,8 @@ static int launch_mfma_any(const dmx_params& prm, const WsView& ws, int64_t user
     a.M = a.m_rx * (n_beams ? n_beams : a.m_tx);
     a.K = prm.n_selected;
     a.sc = prm.selected_subcarriers;
+    a.sc_first = prm.sc_first;
+    a.sc_stride = prm.sc_stride;
     a.inv_n = 1.0 / (double)prm.n_subcarriers;
     const int nstrips = (2 * a.K + 31) / 32;
     // rx_filter with the packed table, every strip full and whole 256-row blocks: gains through LDS-DMA (GSRC = 3) in ONE
@@ -909,10 +1000,23 @@ static int launch_mfma_any(const dmx_params& prm, const WsView& ws, int64_t user
     // The same three bodies in 8-wave workgroups.  Every kernel here is compiled for 4 waves per SIMD (128 VGPRs); a
     // 16-wave workgroup then fills a CU alone, while two 8-wave workgroups share it and overlap each other's phases:
     // 16.0 vs 16.8 ms at the headline shape, 31.7 vs 32.5 at config 5, 8.3 vs 8.8 at config 2 x 200k users.
+    // Uniformly spaced selections of the plain channel take the factorised B' (GSRC = 4, fact_b_step: one complex
+    // product per phasor instead of a sin/cos, and a packed last K-step of <= 2 paths) in the 4- and 8-wave forms.
+    const bool fact = prm.sc_stride > 0 && !n_beams;
     auto go8 = [&](bool persistent, int items_per_wg) {
-        if (a.rows < 128 || tuning_int("DMX_PLAIN_TILE_MODE", 2) == 0) return launch_mfma_t<true, 8, 0>(ws, a, blocks, smem, out, stream, persistent, items_per_wg);
+        const bool rt = a.rows < 128 || tuning_int("DMX_PLAIN_TILE_MODE", 2) == 0;
+        if (fact) {
+            if (rt) return launch_mfma_t<true, 8, 0, 4>(ws, a, blocks, smem, out, stream, persistent, items_per_wg);
+            if (ws.P <= 16) return launch_mfma_t<true, 8, 1, 4>(ws, a, blocks, smem, out, stream, persistent, items_per_wg);
+            return launch_mfma_t<true, 8, 2, 4>(ws, a, blocks, smem, out, stream, persistent, items_per_wg);
+        }
+        if (rt) return launch_mfma_t<true, 8, 0>(ws, a, blocks, smem, out, stream, persistent, items_per_wg);
         if (ws.P <= 16) return launch_mfma_t<true, 8, 1>(ws, a, blocks, smem, out, stream, persistent, items_per_wg);
         return launch_mfma_t<true, 8, 2>(ws, a, blocks, smem, out, stream, persistent, items_per_wg);
+    };
+    auto go4 = [&](bool persistent, int items_per_wg) {
+        if (fact) return launch_mfma_t<true, 4, 0, 4>(ws, a, blocks, smem, out, stream, persistent, items_per_wg);
+        return launch_mfma_t<true, 4>(ws, a, blocks, smem, out, stream, persistent, items_per_wg);
     };
     if (gtab || gpack) {                                   // rx_filter path: gains from the table (float or packed f16)
         const bool small = nstrips <= 8 && a.rows < 128;
@@ -933,7 +1037,7 @@ static int launch_mfma_any(const dmx_params& prm, const WsView& ws, int64_t user
     }
     switch (config) {
         case 1: return launch_mfma_t<false, 16>(ws, a, blocks, smem, out, stream);   // plain stores
-        case 2: return launch_mfma_t<true, 4>(ws, a, blocks, smem, out, stream);
+        case 2: return go4(true, ITEMS_PER_WG);
         case 3: return go8(true, ITEMS_PER_WG8);                                     // 8 waves whatever the strip count
         case 6: return go16(false, 0);                                               // one workgroup per work item
         case 8: return go16(true, ITEMS_PER_WG);                                     // 16 waves whatever the strip count
@@ -943,7 +1047,7 @@ static int launch_mfma_any(const dmx_params& prm, const WsView& ws, int64_t user
             // 128 rows: 64 pairs x 32 subcarriers 1.12 vs 1.68 ms with 8 waves, 16 x 64: 1.08 vs 1.61.  From 128 rows
             // on the 8-wave form wins at every strip count (256 pairs: K=16 2.10 vs 2.40, K=64 3.00 vs 3.39, K=128
             // 4.68 vs 5.09, K=256 8.38 vs 9.07; a single 16-wave workgroup per CU is behind both everywhere).
-            if (nstrips <= 8 && a.rows < 128) return launch_mfma_t<true, 4>(ws, a, blocks, smem, out, stream, true, 0);
+            if (nstrips <= 8 && a.rows < 128) return go4(true, 0);
             return go8(true, ITEMS_PER_WG8);
         default: set_error("unknown matrix-core kernel configuration %d", config); return DMX_ERR_ARG;
     }

@@ -65,7 +65,7 @@ __device__ __forceinline__ BLane b_lane(int strip, int col, int hh, size_t twoK,
     b.kidx = ncol >> 1; b.c = ncol & 1;
     b.kok = (size_t)ncol < twoK;
     b.lane_off = ((unsigned)(4 * hh) * (unsigned)twoK + (unsigned)ncol) * 4u;
-    const int kki = b.kok ? sc[b.kidx] : 0;
+    const int kki = (b.kok && sc) ? sc[b.kidx] : 0;                    // sc = nullptr: kl, kf unused (fact_b_step)
     b.kl = (float)(kki & 4095);
     b.kf = (float)kki;
     return b;
@@ -118,6 +118,73 @@ __device__ __forceinline__ void gen_b_step(float m1, int s, const BLane& bl, int
         Bhi[2 * jj] = ph[0]; Bhi[2 * jj + 1] = ph[1];
         Blo[2 * jj] = pl2[0]; Blo[2 * jj + 1] = pl2[1];
     }
+}
+
+// Factorised B' for a uniformly spaced selection (dmx_params.sc_stride > 0): the lane's subcarrier is
+// k = 16 strip + b with b = col / 2 fixed for the lane, so G[l,k] = (c_l E1[l,strip]) E2[l,b] with
+//   E1[l,strip] = exp(-j2pi q_l (sc_first + 16 stride strip))   one per path and strip, computed by one lane of the wave
+//   E2[l,b]     = exp(-j2pi q_l stride b)                       per item (stage_item), the same for every strip
+// A column c = 0 lane wants (Re G, -Im G), a c = 1 lane (Im G, Re G): the same expression with C1 = c_l E1 replaced by
+// -j C1 = (C1i, -C1r).  So every phasor is ONE complex product (u, v) x E2, with (u, v) = (C1r, C1i) or (C1i, -C1r).
+// Tables in LDS, structure of arrays so that a lane reads the 4 paths of a K-step with one ds_read_b128 per array:
+//   e2tab  E2r [16 b][36] then E2i [16 b][36] (rows padded to 36 floats: the 8 subcarriers of 16 lanes hit distinct
+//          banks; the last row unpadded so that 8 waves x 256 rows still fit two workgroups per CU)
+//   c1tab  per wave, of its current strip: [C1r | C1i | -C1r] x 32 paths; the c = 0 lane reads u, v at 0 / 32,
+//          the c = 1 lane at 32 / 64
+static constexpr int FACT_E2_ROW = 36;
+static constexpr int FACT_E2_ARR = 15 * FACT_E2_ROW + LPAD;     // floats per array
+static constexpr int FACT_E2_BYTES = 2 * FACT_E2_ARR * 4;
+static constexpr int FACT_C1_BYTES = 3 * LPAD * 4;              // per wave
+
+typedef float f4v __attribute__((ext_vector_type(4)));
+
+// float offsets of the lane's u and E2r entries (first path of its half; v and E2i are fixed distances behind them); the
+// caller hides them from loop-invariant code motion, so that the per-step offsets stay immediates of the reads instead
+// of 16 hoisted addresses
+struct FactLane { int u, er; };
+__device__ __forceinline__ FactLane fact_lane(int c, int b, int hh) {
+    FactLane f;
+    f.u = LPAD * c + 4 * hh;
+    f.er = FACT_E2_ROW * b + 4 * hh;
+    return f;
+}
+
+// one K-step (8 paths) of the strip's B' fragments, factorised.  TAIL: this step holds the last <= 2 kept paths and is
+// packed into ONE K16 step (stage_item writes the A' slots as [hi(l) | hi(l) | lo(l) | 0]): rows [hi; lo; hi; x] -
+// the x rows (k = 12..15, lanes hh = 1) meet A' zeros, so both halves of the wave build the same fragment (paths
+// 8s, 8s + 1: the lane's offsets without the half).
+__device__ __forceinline__ void fact_b_step(float m1, int s, const FactLane& f, int hh, bool tail, const float* c1tab,
+                                            const float* e2tab, h8& Bhi, h8& Blo) {
+    const int o = tail ? 8 * s - 4 * hh : 8 * s;
+    const f4v u = *reinterpret_cast<const f4v*>(c1tab + f.u + o), v = *reinterpret_cast<const f4v*>(c1tab + f.u + LPAD + o);
+    const f4v er = *reinterpret_cast<const f4v*>(e2tab + f.er + o);
+    const f4v ei = *reinterpret_cast<const f4v*>(e2tab + f.er + FACT_E2_ARR + o);
+    h2 ph[4], pl2[4];
+#pragma unroll
+    for (int jj = 0; jj < (tail ? 2 : 4); ++jj) {
+        const float e0 = fmaf(u[jj], er[jj], -v[jj] * ei[jj]);
+        const float e1 = -fmaf(u[jj], ei[jj], v[jj] * er[jj]);
+        split2_f16(e0, e1, ph[jj], pl2[jj], m1);
+    }
+    if (tail) {
+        Bhi = h8{ph[0][0], ph[0][1], ph[1][0], ph[1][1], pl2[0][0], pl2[0][1], pl2[1][0], pl2[1][1]};
+        Blo = h8{0, 0, 0, 0, 0, 0, 0, 0};
+        return;
+    }
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+        Bhi[2 * jj] = ph[jj][0]; Bhi[2 * jj + 1] = ph[jj][1];
+        Blo[2 * jj] = pl2[jj][0]; Blo[2 * jj + 1] = pl2[jj][1];
+    }
+}
+
+// the NS K-steps of the strip that hold a kept path (NS and the packing known at compile time, as in the tile bodies
+// the fragments go to: a run-time tail step put a branch into every step)
+template <int NS, bool PACK>
+__device__ __forceinline__ void fact_b_strip(float m1, const FactLane& f, int hh, const float* c1tab, const float* e2tab,
+                                             h8 (&Bhi)[4], h8 (&Blo)[4]) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) fact_b_step(m1, s, f, hh, PACK && s == NS - 1, c1tab, e2tab, Bhi[s], Blo[s]);
 }
 
 // One K-step of the strip's B' fragments from the PACKED gains table the rx_filter path's FFT kernel writes
