@@ -625,8 +625,9 @@ def test_rx_filter_fft512_variants(selection, arrays):
     through the buffer; packed f16 table for the matrix-core contraction or float table for the vector kernel; Doppler on
     and off; users with 0, 1 and all paths; delays that are whole samples (np.sinc(0) = 1 taps, channel.py:166-168).
     dma256 / dma320: 256 and 320 antenna pairs with K a multiple of 16 take the LDS-DMA form of the contraction
-    (k2_fd_mfma<.., GSRC = 3>): whole and ragged row blocks (8 and 2 tiles per strip: both counted waits), the prefetch
-    chain across work items broken by the user without paths."""
+    (k2_fd_mfma<.., GSRC = 3>): whole and ragged row blocks (8 and 2 tiles per strip: both counted waits).  With 21 users
+    every workgroup takes one item, so the prefetch chain across work items is not exercised here:
+    tests/test_gpu_persistent_loops.py (routes l256 / l320) covers it."""
     import deepmimo_amd as dm
     from oracle import oracle_np as onp
     N = 512
