@@ -49,6 +49,14 @@ static int check_params(const dmx_params* p) {
     return DMX_OK;
 }
 
+// the float32-phase kernels refuse a promised selection that reaches DMX_SC_ABS_MAX_F32 (their error grows with |k|)
+static int check_sc_bound_f32(const dmx_params* p, const char* what) {
+    if (!sc_beyond_f32(*p)) return DMX_OK;
+    set_error("%s: selected subcarrier |index| %lld reaches DMX_SC_ABS_MAX_F32 = %d, beyond which its float32 phase "
+              "misses the error bound; use variant 0, 1 or 9", what, (long long)sc_hint_abs_max(*p), DMX_SC_ABS_MAX_F32);
+    return DMX_ERR_ARG;
+}
+
 static inline int used_paths(const dmx_params* p, int32_t loaded) { return p->num_paths < loaded ? p->num_paths : loaded; }
 
 }  // namespace dmx
@@ -121,6 +129,7 @@ int dmx_channels_fd(const dmx_params* prm, const void* workspace, int64_t n_ue, 
     if (!prm->freq_domain) { set_error("dmx_channels_fd called with freq_domain = 0"); return DMX_ERR_ARG; }
     if (prm->rx_filter) { set_error("rx_filter = 1 is handled by dmx_channels_fd_lpf"); return DMX_ERR_ARG; }
     if (variant < 0 || variant > 12) { set_error("unknown variant %d", variant); return DMX_ERR_ARG; }
+    if (variant >= 2 && variant != 9 && (rc = check_sc_bound_f32(prm, "matrix-core / folded variant"))) return rc;
     if (prm->n_selected == 0) return DMX_OK;
     return launch_channels_fd(*prm, ws, user_begin, user_count, (float2*)out_c64, variant, (hipStream_t)stream);
 }
@@ -167,6 +176,7 @@ int dmx_channels_fd_beams(const dmx_params* prm, const void* workspace, int64_t 
     int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_c64, &ws);
     if (rc) return rc;
     if (!prm->freq_domain || prm->rx_filter) { set_error("dmx_channels_fd_beams needs freq_domain = 1 and rx_filter = 0"); return DMX_ERR_ARG; }
+    if ((rc = check_sc_bound_f32(prm, "dmx_channels_fd_beams"))) return rc;
     if (n_beams < 0 || (n_beams > 0 && !codebook_c64)) { set_error("codebook missing"); return DMX_ERR_ARG; }
     if (prm->n_selected == 0 || n_beams == 0) return DMX_OK;
     if (ws.P > 32) { set_error("num_paths = %d exceeds the 32 paths the beam-space kernel supports", ws.P); return DMX_ERR_SHAPE; }
@@ -187,6 +197,7 @@ int dmx_beam_power(const dmx_params* prm, const void* workspace, int64_t n_ue, i
     int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_mean_amp, &ws);
     if (rc) return rc;
     if (!prm->freq_domain || prm->rx_filter) { set_error("dmx_beam_power needs freq_domain = 1 and rx_filter = 0"); return DMX_ERR_ARG; }
+    if ((rc = check_sc_bound_f32(prm, "dmx_beam_power"))) return rc;
     if (n_beams < 1 || !codebook_c64) { set_error("codebook missing"); return DMX_ERR_ARG; }
     if (prm->n_selected < 1) { set_error("dmx_beam_power needs at least one selected subcarrier"); return DMX_ERR_ARG; }
     if (ws.P > 32) { set_error("num_paths = %d exceeds the 32 paths the beam-space kernels support", ws.P); return DMX_ERR_SHAPE; }

@@ -31,6 +31,16 @@ struct WsView {
                       // residual fma, so that it is selected as v_fma_mix_f32 (k2_mfma_frag.h, split2_f16)
 };
 
+// Largest |selected index| the sc_first / sc_stride promise implies (int64: no wrap), or -1 without a promise
+__host__ inline int64_t sc_hint_abs_max(const dmx_params& p) {
+    if (p.sc_stride <= 0 || p.n_selected < 1) return -1;
+    const int64_t a = p.sc_first, b = a + (int64_t)p.sc_stride * (p.n_selected - 1);
+    const int64_t ma = a < 0 ? -a : a, mb = b < 0 ? -b : b;
+    return ma > mb ? ma : mb;
+}
+// the promise shows an index the float32-phase kernels cannot take (include/deepmimo_amd.h DMX_SC_ABS_MAX_F32)
+__host__ inline bool sc_beyond_f32(const dmx_params& p) { return sc_hint_abs_max(p) >= DMX_SC_ABS_MAX_F32; }
+
 __host__ __device__ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Carve the workspace.  Returns total bytes; fills `v` when base != nullptr.

@@ -287,8 +287,10 @@ int launch_channels_fd_fold(const dmx_params& prm, const WsView& ws, int64_t use
 bool fd_fold_preferred(const dmx_params& prm, const WsView& ws);
 
 // what variant 0 runs for this shape: 9 small-output kernel, 12 folded matrix-core kernel (few antenna pairs, uniformly
-// spaced subcarriers), 2 matrix cores, 1 fp32 vector kernel
+// spaced subcarriers), 2 matrix cores, 1 fp32 vector kernel.  Indices at or beyond DMX_SC_ABS_MAX_F32: only the
+// float64-phase kernels, 9 and 1
 int fd_auto_choice(const dmx_params& prm, const WsView& ws) {
+    if (sc_beyond_f32(prm)) return fd_small_preferred(prm, ws) ? 9 : 1;
     if (fd_fold_preferred(prm, ws)) return 12;
     if (fd_small_preferred(prm, ws)) return 9;
     if (fd_mfma_preferred(prm, ws)) return 2;

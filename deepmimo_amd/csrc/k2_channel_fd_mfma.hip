@@ -548,9 +548,10 @@ __device__ __forceinline__ bool consume_item(const WsView& ws, const MfmaArgs& a
         if constexpr (GSRC == 4) {
             // c_l E1[l, strip] for the wave: lane l, the phase reduced as in gen_b_step (k = the strip's first subcarrier)
             if (lane < LPAD) {
-                const unsigned k1 = (unsigned)a.sc_first + (unsigned)(16 * strip) * (unsigned)a.sc_stride;
+                // signed: a strip that starts below subcarrier 0 must convert to -|k1|, not to 2^32 - |k1|
+                const int k1 = a.sc_first + 16 * strip * a.sc_stride;
                 const float2 q = L.qtab[lane];
-                const float p1 = q.x * (float)(k1 & 4095u);
+                const float p1 = q.x * (float)(k1 & 4095);
                 float sn, cs;
                 sincos_rev(fmaf(q.y, (float)k1, p1 - rintf(p1)), sn, cs);
                 const float cr = L.crtab[lane], ci = L.citab[lane];

@@ -53,6 +53,7 @@ class PrepResult:
     rays_struct: Optional[nat.DmxRays] = None
     side_struct: Optional[nat.DmxSide] = None
     workspace_bytes: int = 0
+    sc_abs_max: int = 0            # largest |selected subcarrier index| (check_selection)
 
 
 def is_full_fov(fov) -> bool:
@@ -69,9 +70,48 @@ def uniform_stride(sel: np.ndarray):
     if sel.size == 1:
         return int(sel[0]), 1
     d = int(sel[1] - sel[0])
-    if d <= 0 or d >= 2 ** 20 or not np.array_equal(sel, sel[0] + d * np.arange(sel.size)):
+    if d <= 0 or d >= 2 ** 20 or int(sel[0]) + d * (sel.size - 1) >= 2 ** 31 or \
+            not np.array_equal(sel, sel[0] + d * np.arange(sel.size)):
         return 0, 0
     return int(sel[0]), d
+
+
+# include/deepmimo_amd.h DMX_SC_ABS_MAX_F32: the matrix-core and folded kernels reduce the subcarrier phase in float32,
+# with an error that grows with |k|; from this |k| on only the float64-phase kernels (1 vector, 9 small-output) run
+SC_ABS_MAX_F32 = 32768
+F64_PHASE_VARIANTS = (1, 9)
+
+
+def check_selection(sel):
+    """(int64 copy of ofdm.selected_subcarriers, its largest |index|).  The device array is int32: an index outside
+    int32 raises ValueError here instead of wrapping on upload."""
+    sel = np.asarray(sel).astype(np.int64).ravel()
+    if sel.size == 0:
+        return sel, 0
+    lo, hi = int(sel.min()), int(sel.max())
+    if lo < -2 ** 31 or hi >= 2 ** 31:
+        raise ValueError(f"selected_subcarriers holds {lo if lo < -2 ** 31 else hi}: subcarrier indices must fit int32")
+    return sel, max(-lo, hi)
+
+
+def bounded_fd_variant(variant: int, sc_abs_max: int, small_preferred: bool) -> int:
+    """The stage-2 variant to run under the float32-phase index bound: unchanged below SC_ABS_MAX_F32; from it on
+    variant 0 becomes 9 where the small-output kernel is preferred and 1 elsewhere, 1 and 9 stay, and an explicit
+    matrix-core or folded variant raises ValueError."""
+    if sc_abs_max < SC_ABS_MAX_F32 or variant in F64_PHASE_VARIANTS:
+        return variant
+    if variant == 0:
+        return 9 if small_preferred else 1
+    raise ValueError(f"fd_kernel_variant {variant} evaluates subcarrier phases in float32 and needs every selected |index| "
+                     f"below {SC_ABS_MAX_F32} (DMX_SC_ABS_MAX_F32); the selection reaches {sc_abs_max}: use variant 0, 1 "
+                     f"or 9")
+
+
+def check_beam_bound(sc_abs_max: int):
+    """The beam entry points run the float32-phase kernels only: ValueError from SC_ABS_MAX_F32 on."""
+    if sc_abs_max >= SC_ABS_MAX_F32:
+        raise ValueError(f"beam-space channels / beam power need every selected subcarrier |index| below {SC_ABS_MAX_F32} "
+                         f"(DMX_SC_ABS_MAX_F32); the selection reaches {sc_abs_max}")
 
 
 class ChannelEngine:
@@ -169,7 +209,7 @@ class ChannelEngine:
         n, L = rays.n_ue, rays.n_paths
         ofdm = params[c.PARAMSET_OFDM]
         keep = []
-        sel = np.asarray(ofdm[c.PARAMSET_OFDM_SC_SAMP]).astype(np.int64).ravel()
+        sel, sc_abs_max = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
         sel_dev = torch.from_numpy(sel.astype(np.int32)).to(dev)
         keep.append(sel_dev)
         rot_dev = None
@@ -220,7 +260,17 @@ class ChannelEngine:
         nat.check(rc, "dmx_path_prep")
         keep.extend(rays.fields.values())
         return PrepResult(workspace=ws, n_ue=n, n_paths_loaded=L, params_struct=p, keepalive=keep, side=side,
-                          rays_struct=r, side_struct=s, workspace_bytes=nbytes)
+                          rays_struct=r, side_struct=s, workspace_bytes=nbytes, sc_abs_max=sc_abs_max)
+
+    def fd_variant(self, prep: PrepResult, variant: int = 0) -> int:
+        """The variant stage 2 runs for `variant` (bounded_fd_variant).  Beyond the bound without a spacing promise the
+        library cannot see the indices, so variant 0 is resolved here."""
+        if prep.sc_abs_max < SC_ABS_MAX_F32:
+            return variant
+        p = nat.DmxParams.from_buffer_copy(prep.params_struct)
+        p.sc_first, p.sc_stride = 0, 0                 # the shape's choice without the index range: 9 or not
+        small = self.lib.dmx_fd_kernel_choice(C.byref(p), prep.n_paths_loaded) == 9
+        return bounded_fd_variant(int(variant), prep.sc_abs_max, small)
 
     def relaunch(self, prep: PrepResult, out: torch.Tensor, variant: int = 0) -> torch.Tensor:
         """Re-issue stage 1 + stage 2 of an existing preparation on the current stream, reading whatever the
@@ -233,6 +283,8 @@ class ChannelEngine:
         shape = self.channel_shape(prep)
         if out.dtype != torch.complex64 or tuple(out.shape) != shape or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous complex64 tensor of shape {shape}")
+        if p.freq_domain:
+            variant = self.fd_variant(prep, variant)
         wsp = C.c_void_p(prep.workspace.data_ptr())
         stream = self._stream_ptr()
         with torch.cuda.device(self.device):
@@ -276,6 +328,7 @@ class ChannelEngine:
                 raise ValueError(f"tx_codebook must be [n_beams, {shape[2]}], got {tuple(cb.shape)}")
             if not p.freq_domain or p.rx_filter:
                 raise ValueError("tx_codebook needs freq_domain = 1 and rx_filter = 0")
+            check_beam_bound(prep.sc_abs_max)
             shape = (shape[0], shape[1], int(cb.shape[0]), shape[3])
         if out is None:
             out = torch.empty(shape, dtype=torch.complex64, device=self.device)
@@ -308,7 +361,8 @@ class ChannelEngine:
                 nat.check(rc, "dmx_channels_fd_lpf")
             elif p.freq_domain:
                 rc = self.lib.dmx_channels_fd(C.byref(p), wsp, prep.n_ue, prep.n_paths_loaded, user_begin, user_count,
-                                              C.c_void_p(out.data_ptr()), int(variant), self._stream_ptr())
+                                              C.c_void_p(out.data_ptr()), self.fd_variant(prep, variant),
+                                              self._stream_ptr())
                 nat.check(rc, "dmx_channels_fd")
             else:
                 rc = self.lib.dmx_channels_td(C.byref(p), wsp, prep.n_ue, prep.n_paths_loaded, user_begin, user_count,
@@ -410,6 +464,7 @@ class ChannelEngine:
             raise ValueError(f"tx_codebook must be [n_beams, {m_tx}], got {tuple(cb.shape)}")
         if not p.freq_domain or p.rx_filter:
             raise ValueError("beam_power needs freq_domain = 1 and rx_filter = 0")
+        check_beam_bound(prep.sc_abs_max)
         nb = int(cb.shape[0])
         amp = torch.empty((user_count, nb), dtype=torch.float32, device=self.device)
         best = torch.empty((user_count,), dtype=torch.int32, device=self.device) if want_best else None

@@ -79,7 +79,7 @@ typedef struct dmx_params {
     int32_t freq_domain;          /* 1: OFDM channel, 0: time-domain taps   channel.py:54 */
     int32_t n_subcarriers;        /* ofdm.subcarriers (N) */
     int32_t n_selected;           /* K = len(ofdm.selected_subcarriers) */
-    const int32_t* selected_subcarriers; /* device [K] */
+    const int32_t* selected_subcarriers; /* device [K]; any int32 values (negative, >= N), see DMX_SC_ABS_MAX_F32 */
     double  bandwidth;            /* Hz; Ts = 1/bandwidth             channel.py:223 */
     int32_t rx_filter;            /* ofdm.rx_filter (LPF / sinc interpolation)  channel.py:193-194 */
     int32_t enable_doppler;       /* apply the v3 Doppler term (construct_deepmimo.py:267-280) */
@@ -87,7 +87,9 @@ typedef struct dmx_params {
     /* Host-side promise about the DEVICE array above (ABI 2): when sc_stride > 0 the caller guarantees
      * selected_subcarriers[k] == sc_first + k * sc_stride for every k (np.arange(N), np.arange(0, N, s), [0] ...:
      * what channel.py:57 and the reference's own scripts select).  It lets dmx_channels_fd pick the folded kernel for
-     * few antenna pairs without reading the device array back.  sc_stride = 0 makes no promise (any selection). */
+     * few antenna pairs without reading the device array back.  sc_stride = 0 makes no promise (any selection).
+     * With a promise the library also sees the largest |index|, max(|sc_first|, |sc_first + (K-1) sc_stride|), and
+     * enforces DMX_SC_ABS_MAX_F32 with it; without one, keeping within that bound is the caller's job. */
     int32_t sc_first;
     int32_t sc_stride;
     /* Arithmetic mode of the matrix-core kernels (ABI 3).  The reference multiplies and sums every path in complex128
@@ -102,6 +104,16 @@ typedef struct dmx_params {
 } dmx_params;
 
 #define DMX_FLAG_ADAPTIVE_TERMS 1u
+
+/* Subcarrier index bound of the float32-phase kernels.  The matrix-core and folded kernels (variants 2-5, 8, 10-12, the
+ * beam entry points) reduce the phase dn k / N in float32 as qh (k mod 4096) + ql k, whose error grows linearly with
+ * |k|: they meet the error claim above (~2e-6 of a user's peak) only while every selected |k| is below this bound.  The
+ * fp32 vector kernel (1) and the small-output kernel (9) evaluate the phase in float64 and take any int32 index; the
+ * rx_filter path reduces k mod N exactly and is not bounded either.  When the caller promises a uniform spacing
+ * (sc_stride > 0) and an index reaches the bound, variant 0 picks 1 (or 9 where the small-output kernel is preferred),
+ * and an explicit matrix-core or folded variant, dmx_channels_fd_beams and dmx_beam_power return DMX_ERR_ARG.  Without
+ * the promise the library cannot see the indices: the caller keeps them below the bound or passes variant 1 or 9. */
+#define DMX_SC_ABS_MAX_F32 32768
 
 /* Optional side products of the path-prep stage (any pointer may be NULL = not wanted).
  * All device pointers; [n_ue, n_paths] arrays are dense row-major with row stride n_paths. */
@@ -157,8 +169,8 @@ int dmx_path_prep(const dmx_rays* rays, const dmx_params* prm, void* workspace, 
 int dmx_channels_fd(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                     int64_t user_begin, int64_t user_count, void* out_c64, int32_t variant, void* stream);
 
-/* Host-only: the kernel `variant = 0` selects for this shape (1, 2, 9 or 12 above), from measured crossovers; negative on
- * a bad argument.  No GPU involved. */
+/* Host-only: the kernel `variant = 0` selects for this shape (1, 2, 9 or 12 above), from measured crossovers; 1 or 9
+ * when sc_stride > 0 and an index reaches DMX_SC_ABS_MAX_F32; negative on a bad argument.  No GPU involved. */
 int dmx_fd_kernel_choice(const dmx_params* prm, int32_t n_paths_loaded);
 
 /*

@@ -493,12 +493,20 @@ def test_beam_codebook_projection(cfg):
     F2 = (rng.normal(size=(cfg["nb"], m_tx)) + 1j * rng.normal(size=(cfg["nb"], m_tx))) * 37.5
     ds = dm.Dataset(dict(rays))
     for F in (F1, F2):
-        Y = ds.compute_beam_channels(F, p)
-        Yref = (F @ Href).astype(np.complex64)                      # [n_ue, M_rx, n_beams, K]
-        assert Y.shape == Yref.shape == (70, cfg["ue"][0] * cfg["ue"][1], cfg["nb"], 74)
-        assert_channel_close(Y, Yref, what="beam-space channel")
+        Y = check_beam_channels(ds, p, F, Href)
+        assert Y.shape == (70, cfg["ue"][0] * cfg["ue"][1], cfg["nb"], 74)
     with pytest.raises(ValueError):
         ds.compute_beam_channels(np.ones((4, m_tx + 1)), p)
+
+
+def check_beam_channels(ds, p, F, Href):
+    """Dataset.compute_beam_channels(F) against F @ Href (the oracle's channel, complex128) at the parity tolerance;
+    returns the beam-space channel"""
+    Y = ds.compute_beam_channels(F, p)
+    Yref = (F @ Href).astype(np.complex64)                          # [n_ue, M_rx, n_beams, K]
+    assert Y.shape == Yref.shape
+    assert_channel_close(Y, Yref, what="beam-space channel")
+    return Y
 
 
 @pytest.mark.parametrize("cfg", [dict(bs=[32, 1], ue=[1, 1], nb=16, L=9, rot=[0, 0, -135], sel=np.arange(0, 512, 7)),   # the notebook's sweep
@@ -514,7 +522,6 @@ def test_beam_power_fused_reduction(cfg):
     1e-5 element-wise for every beam within 30 dB of the strongest; dBm within one rounding step; best beam exact except
     near-ties."""
     import deepmimo_amd as dm
-    from deepmimo_amd.dataset import _engine
     from oracle import oracle_np as onp
     n = 70
     rays = onp.synth_rays(n, cfg["L"], seed=56)
@@ -533,42 +540,55 @@ def test_beam_power_fused_reduction(cfg):
     rng = np.random.default_rng(2)
     F2 = (rng.normal(size=(cfg["nb"], m_tx)) + 1j * rng.normal(size=(cfg["nb"], m_tx))) * 11.0
     for F in (F1, F2):
-        want_amp = np.abs(F @ Href).mean(axis=1).mean(axis=-1)                  # [n, nb] float64
-        ds = dm.Dataset(dict(rays))
-        pwr, best = ds.compute_beam_power(F, p, return_best=True)
-        amp = ds["beam_mean_amplitude"]
-        assert amp.shape == (n, cfg["nb"]) and amp.dtype == np.float32 and pwr.dtype == np.float64
-        np.testing.assert_array_equal(ds.los, ref["los"])
-        has = ref["los"] != -1
-        assert has.sum() > 0
-        peak = want_amp[has].max(axis=1, keepdims=True)
-        assert np.all(np.abs(amp[has] - want_amp[has]) <= 1e-5 * peak)
-        strong = want_amp[has] >= peak * 10 ** (-30 / 20)
-        np.testing.assert_allclose(amp[has][strong], want_amp[has][strong], rtol=1e-5, atol=0)
-        assert np.all(amp[~has] == 0)
-        # cells 105 / 110 / 112 on the reference amplitudes, in the notebook's float32 (channel is complex64)
-        want_pwr = np.zeros((n, cfg["nb"])) * np.nan
-        want_pwr[has] = np.around(20 * np.log10(want_amp[has].astype(np.float32)) + 30, 1)
-        assert np.array_equal(np.isnan(pwr), np.isnan(want_pwr))
-        assert np.nanmax(np.abs(pwr - want_pwr)) <= 0.1 + 1e-4                  # a value on a rounding boundary may step
-        assert np.mean(np.abs(pwr[has] - want_pwr[has]) < 1e-4) > 0.98
-        want_best = np.argmax(want_pwr, axis=1).astype(float)
-        want_best[~has] = np.nan
-        assert np.array_equal(np.isnan(best), np.isnan(want_best))
-        for u in np.nonzero(has & (best != want_best))[0]:                       # only (near-)ties may differ
-            assert abs(want_pwr[u, int(best[u])] - want_pwr[u, int(want_best[u])]) <= 0.1 + 1e-4
-        # the kernel's own argmax (first maximum of the un-rounded means)
-        eng = _engine()
-        prep = eng.prepare(eng.upload_rays(rays), p.validate(n))
-        amp_d, best_d = eng.beam_power(prep, F)
-        np.testing.assert_array_equal(amp_d.cpu().numpy(), amp)
-        bd = best_d.cpu().numpy()
-        assert np.all(bd[~has] == -1) and np.array_equal(bd[has], np.argmax(amp[has], axis=1))
-        # a user sub-range is bit-identical to the same rows of the full call (what sharding relies on)
-        part, _ = eng.beam_power(prep, F, user_begin=11, user_count=30)
-        np.testing.assert_array_equal(part.cpu().numpy(), amp[11:41])
+        ds = check_beam_power(rays, p, F, Href, ref["los"])
+        assert ds["beam_mean_amplitude"].shape == (n, cfg["nb"])
     with pytest.raises(ValueError):
         ds.compute_beam_power(np.ones((4, m_tx + 1)), p)
+
+
+def check_beam_power(rays, p, F, Href, los, part=(11, 30)):
+    """Dataset.compute_beam_power(F) and ChannelEngine.beam_power on `rays` against the float64 reduction of the oracle's
+    channel Href (complex128) and its LoS flags `los`, with the tolerances test_beam_power_fused_reduction documents; the
+    user sub-range part = (begin, count) bit for bit.  Returns the dataset."""
+    import deepmimo_amd as dm
+    from deepmimo_amd.dataset import _engine
+    n, nb = Href.shape[0], F.shape[0]
+    want_amp = np.abs(F @ Href).mean(axis=1).mean(axis=-1)                      # [n, nb] float64
+    ds = dm.Dataset(dict(rays))
+    pwr, best = ds.compute_beam_power(F, p, return_best=True)
+    amp = ds["beam_mean_amplitude"]
+    assert amp.shape == (n, nb) and amp.dtype == np.float32 and pwr.dtype == np.float64
+    np.testing.assert_array_equal(ds.los, los)
+    has = los != -1
+    assert has.sum() > 0
+    peak = want_amp[has].max(axis=1, keepdims=True)
+    assert np.all(np.abs(amp[has] - want_amp[has]) <= 1e-5 * peak)
+    strong = want_amp[has] >= peak * 10 ** (-30 / 20)
+    np.testing.assert_allclose(amp[has][strong], want_amp[has][strong], rtol=1e-5, atol=0)
+    assert np.all(amp[~has] == 0)
+    # cells 105 / 110 / 112 on the reference amplitudes, in the notebook's float32 (channel is complex64)
+    want_pwr = np.zeros((n, nb)) * np.nan
+    want_pwr[has] = np.around(20 * np.log10(want_amp[has].astype(np.float32)) + 30, 1)
+    assert np.array_equal(np.isnan(pwr), np.isnan(want_pwr))
+    assert np.nanmax(np.abs(pwr - want_pwr)) <= 0.1 + 1e-4                      # a value on a rounding boundary may step
+    assert np.mean(np.abs(pwr[has] - want_pwr[has]) < 1e-4) > 0.98
+    want_best = np.argmax(want_pwr, axis=1).astype(float)
+    want_best[~has] = np.nan
+    assert np.array_equal(np.isnan(best), np.isnan(want_best))
+    for u in np.nonzero(has & (best != want_best))[0]:                           # only (near-)ties may differ
+        assert abs(want_pwr[u, int(best[u])] - want_pwr[u, int(want_best[u])]) <= 0.1 + 1e-4
+    # the kernel's own argmax (first maximum of the un-rounded means)
+    eng = _engine()
+    prep = eng.prepare(eng.upload_rays(rays), p.validate(n))
+    amp_d, best_d = eng.beam_power(prep, F)
+    np.testing.assert_array_equal(amp_d.cpu().numpy(), amp)
+    bd = best_d.cpu().numpy()
+    assert np.all(bd[~has] == -1) and np.array_equal(bd[has], np.argmax(amp[has], axis=1))
+    # a user sub-range is bit-identical to the same rows of the full call (what sharding relies on)
+    b0, cnt = part
+    sub, _ = eng.beam_power(prep, F, user_begin=b0, user_count=cnt)
+    np.testing.assert_array_equal(sub.cpu().numpy(), amp[b0:b0 + cnt])
+    return ds
 
 
 def test_pathloss_matches_reference_formula():
