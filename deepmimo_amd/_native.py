@@ -18,7 +18,8 @@ EXPORTED_SYMBOLS = ("dmx_version", "dmx_last_error", "dmx_workspace_bytes", "dmx
                     "dmx_path_prep", "dmx_channels_fd", "dmx_channels_td", "dmx_channels_fd_lpf",
                     "dmx_lpf_workspace_bytes", "dmx_mat5_find", "dmx_mat_to_rowmajor_f32", "dmx_mats_to_device",
                     "dmx_beam_workspace_bytes", "dmx_channels_fd_beams", "dmx_pathloss",
-                    "dmx_p2m_count_rx", "dmx_p2m_parse_paths", "dmx_fd_kernel_choice", "dmx_beam_power")
+                    "dmx_p2m_count_rx", "dmx_p2m_parse_paths", "dmx_fd_kernel_choice", "dmx_beam_power",
+                    "dmx_fd_direct_supported", "dmx_channels_fd_direct")
 
 PATTERN_IDS = {"isotropic": 0, "halfwave-dipole": 1}
 
@@ -93,6 +94,11 @@ def load():
     lib.dmx_workspace_bytes.argtypes = [C.POINTER(DmxParams), C.c_int64, C.c_int32]
     lib.dmx_fd_kernel_choice.restype = C.c_int
     lib.dmx_fd_kernel_choice.argtypes = [C.POINTER(DmxParams), C.c_int32]
+    lib.dmx_fd_direct_supported.restype = C.c_int
+    lib.dmx_fd_direct_supported.argtypes = [C.POINTER(DmxParams), C.c_int32]
+    lib.dmx_channels_fd_direct.restype = C.c_int
+    lib.dmx_channels_fd_direct.argtypes = [C.POINTER(DmxRays), C.POINTER(DmxParams), C.POINTER(DmxSide), C.c_int64, C.c_int64,
+                                           C.c_void_p, C.c_void_p]
     lib.dmx_decode_max_delay.restype = C.c_float
     lib.dmx_decode_max_delay.argtypes = [C.c_uint32]
     lib.dmx_path_prep.restype = C.c_int

@@ -10,7 +10,8 @@ complex64 tensor resident in HBM - required when it does not fit host memory); `
 reproduces the reference's cache staleness when only a radiation pattern changes (Dataset._params_for_prep);
 ``host_copy_guard`` makes ``compute_channels`` raise instead of copying a tensor larger than the free host memory;
 ``adaptive_precision`` opts into the one-term rule for weak path groups (default off: three product terms for every
-path, the arithmetic closest to the reference's complex128 sum, channel.py:283-284)."""
+path, the arithmetic closest to the reference's complex128 sum, channel.py:283-284); ``single_pass`` ('auto' / False)
+lets ``compute_channels`` go from the ray matrices to the channels in one kernel for small outputs (engine.single_pass_route)."""
 from __future__ import annotations
 
 from typing import Any
@@ -28,6 +29,9 @@ class _Config:
         "array_response_max_bytes": 2 << 30,   # largest `array_response_product` ([N, M_rx, M_tx, L] complex128) built on request
         "adaptive_precision": False,  # True: DMX_FLAG_ADAPTIVE_TERMS - a user's weak last path group in ONE f16 product term
                                       # (<= 7.6e-6 of the strongest path instead of ~2e-6; 3-5 % faster at 25 paths)
+        "single_pass": "auto",       # rays -> channels in ONE launch (dmx_channels_fd_direct) where variant 0 runs the small-output
+                                     # kernel, the library takes the shape and it measured faster: same bits, no HBM workspace.  False: always two calls;
+                                     # True: wherever possible (engine.single_pass_route)
     }
 
     def __init__(self):

@@ -143,6 +143,48 @@ int dmx_fd_kernel_choice(const dmx_params* prm, int32_t n_paths_loaded) {
     return fd_auto_choice(*prm, ws);
 }
 
+int dmx_fd_direct_supported(const dmx_params* prm, int32_t n_paths_loaded) {
+    int rc = check_params(prm);
+    if (rc) return rc;
+    if (n_paths_loaded < 0) { set_error("n_paths_loaded must be >= 0"); return DMX_ERR_ARG; }
+    return fd_direct_waves_per_block(*prm, n_paths_loaded) > 0 ? 1 : 0;
+}
+
+int dmx_channels_fd_direct(const dmx_rays* rays, const dmx_params* prm, const dmx_side* side,
+                           int64_t user_begin, int64_t user_count, void* out_c64, void* stream) {
+    int rc = check_params(prm);
+    if (rc) return rc;
+    if (!rays) { set_error("rays is NULL"); return DMX_ERR_ARG; }
+    if (rays->n_ue < 0 || rays->n_paths < 0 || rays->ld < rays->n_paths) { set_error("bad ray matrix shape"); return DMX_ERR_ARG; }
+    if (rays->n_ue > 0 && rays->n_paths > 0 &&
+        (!rays->power || !rays->phase || !rays->delay || !rays->aoa_az || !rays->aoa_el || !rays->aod_az ||
+         !rays->aod_el || !rays->inter)) {
+        set_error("a required ray field pointer is NULL"); return DMX_ERR_ARG;
+    }
+    if (user_begin < 0 || user_count < 0 || user_begin + user_count > rays->n_ue) {
+        set_error("user range [%lld, %lld) outside [0, %lld)", (long long)user_begin, (long long)(user_begin + user_count), (long long)rays->n_ue);
+        return DMX_ERR_ARG;
+    }
+    if (user_count > 0x7fffffffLL) { set_error("too many users for one call"); return DMX_ERR_SHAPE; }
+    if (side && (side->aod_el_rot || side->aod_az_rot || side->aoa_el_rot || side->aoa_az_rot || side->power_linear ||
+                 side->power_linear_ant_gain)) {
+        set_error("dmx_channels_fd_direct writes fov_mask, num_paths, los and max_delay_key only: rotated angles and powers come "
+                  "from dmx_path_prep");
+        return DMX_ERR_ARG;
+    }
+    if (!prm->freq_domain) { set_error("dmx_channels_fd_direct called with freq_domain = 0: call dmx_path_prep + dmx_channels_td"); return DMX_ERR_SHAPE; }
+    if (fd_direct_waves_per_block(*prm, rays->n_paths) == 0) {
+        set_error("dmx_channels_fd_direct does not take this shape (frequency domain, rx_filter = 0, flags = 0, 1..64 loaded and "
+                  "1..32 used paths, at least one subcarrier, tables within the LDS): call dmx_path_prep + dmx_channels_fd");
+        return DMX_ERR_SHAPE;
+    }
+    if (user_count > 0 && !out_c64) { set_error("out is NULL"); return DMX_ERR_ARG; }
+    if (((uintptr_t)out_c64 & 7u) != 0) { set_error("out must be 8-byte aligned"); return DMX_ERR_ARG; }
+    dmx_side s;
+    if (side) s = *side; else memset(&s, 0, sizeof(s));
+    return launch_channels_fd_direct(*rays, *prm, s, user_begin, user_count, (float2*)out_c64, (hipStream_t)stream);
+}
+
 size_t dmx_lpf_workspace_bytes(const dmx_params* prm, int64_t user_count, int32_t n_paths_loaded) {
     if (!prm || user_count < 0 || n_paths_loaded < 0 || prm->n_selected < 0) return 0;
     return align_up((size_t)user_count * (size_t)used_paths(prm, n_paths_loaded) * (size_t)prm->n_selected * 8, 256);

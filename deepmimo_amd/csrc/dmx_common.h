@@ -90,6 +90,9 @@ int launch_path_prep(const dmx_rays& rays, const dmx_params& prm, const WsView& 
 int launch_channels_fd(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
                        float2* out, int variant, hipStream_t stream);
 int fd_auto_choice(const dmx_params& prm, const WsView& ws);
+int fd_direct_waves_per_block(const dmx_params& prm, int32_t n_paths_loaded);
+int launch_channels_fd_direct(const dmx_rays& rays, const dmx_params& prm, const dmx_side& side, int64_t user_begin,
+                              int64_t user_count, float2* out, hipStream_t stream);
 int launch_channels_fd_lpf(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
                            float2* gtab, float2* out, hipStream_t stream);
 int launch_channels_fd_beams(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,

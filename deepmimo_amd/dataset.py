@@ -22,6 +22,7 @@ or FoV change - dataset.py:213-220 - and would silently reuse the stale array).
 from __future__ import annotations
 
 import inspect
+import types as _types
 from typing import Any, Dict, Optional
 
 import numpy as np
@@ -194,20 +195,50 @@ class Dataset(DotDict):
         self._data[_PATTERNS_IN_EFFECT] = pats
         return params
 
-    def _run_prep(self, want_side=True):
-        """Stage 1 on the GPU; refreshes every per-path side product in the cache.  want_side="light" computes LoS,
-        path counts and the FoV mask beside the records and leaves the rotated angles / powers to a second stage-1
-        pass that runs only if one of them is ever read (`_store_side`)."""
+    def _prep_inputs(self):
+        """(engine, parameters stage 1 runs with, uploaded rays, prepare keywords) of a GPU pass on this dataset."""
         eng = _engine()
         params = self._params_for_prep()
         rays = eng.upload_rays(self)
         kw = dict(bs_fov=self._data.get("bs_fov"), ue_fov=self._data.get("ue_fov"),
                   ue_rotation_per_user=self._resolved_ue_rotation(), carrier_freq=self._carrier_freq(),
                   adaptive_terms=bool(config.get("adaptive_precision", False)))
-        prep = eng.prepare(rays, params, want_side=want_side, **kw)
+        return eng, params, rays, kw
+
+    def _run_prep(self, want_side=True, inputs=None, structs=None):
+        """Stage 1 on the GPU; refreshes every per-path side product in the cache.  want_side="light" computes LoS,
+        path counts and the FoV mask beside the records and leaves the rotated angles / powers to a second stage-1
+        pass that runs only if one of them is ever read (`_store_side`)."""
+        eng, params, rays, kw = inputs or self._prep_inputs()
+        prep = eng.prepare(rays, params, want_side=want_side, structs=structs, **kw)
         if want_side:
             self._store_side(prep, None if want_side is True else (rays, params.deepcopy(), kw))
         return eng, prep
+
+    def _run_single_pass(self, inputs, to_host: bool):
+        """The single-pass route of `compute_channels` (engine.single_pass_route): rays -> channels in one launch, the
+        light side products from the same kernel, the heavy ones deferred to a stage-1 pass on their first read.
+        Returns ((channels, max delay) or None when the route does not apply and the two calls have to run, the call
+        structs if they were built on the way - stage 1 then takes them instead of building them again)."""
+        from .engine import single_pass_preferred, single_pass_route
+        eng, params, rays, kw = inputs
+        cfg = (config.get("single_pass", "auto"), config.get("fd_kernel_variant", 0), config.get("adaptive_precision", False))
+        # what needs no struct first: a call that cannot be routed pays nothing for the question
+        if not params[c.PARAMSET_FD_CH] or not single_pass_route(*cfg, True, 9, True):
+            return None, None
+        structs = eng._call_structs(rays, params, **kw)
+        p = structs[0]
+        m_rx, m_tx = p.ue_shape[0] * p.ue_shape[1], p.bs_shape[0] * p.bs_shape[1]
+        if not single_pass_route(*cfg,
+                                 eng.direct_supported(rays, params, structs=structs),
+                                 eng.auto_fd_choice(p, rays.n_paths, structs[3]),
+                                 not (to_host and eng.host_copy_chunks(rays.n_ue, m_rx * m_tx * p.n_selected)),
+                                 single_pass_preferred(m_rx + m_tx, rays.n_paths, p.n_selected)):
+            return None, structs
+        out, side = eng.channels_direct(rays, params, structs=structs)
+        prep = _types.SimpleNamespace(side=side)
+        self._store_side(prep, (rays, params.deepcopy(), kw))
+        return ((out.cpu().numpy() if to_host else out), eng.max_delay(prep)), structs
 
     def _store_side(self, prep, deferred=None) -> None:
         """Register every side product of stage 1 under the reference's cache keys.  The arrays stay in HBM
@@ -290,12 +321,18 @@ class Dataset(DotDict):
             ofdm_, n_ant = params[c.PARAMSET_OFDM], [int(np.prod(params[s_][c.PARAMSET_ANT_SHAPE])) for s_ in (c.PARAMSET_ANT_BS, c.PARAMSET_ANT_UE)]
             last = len(np.atleast_1d(ofdm_[c.PARAMSET_OFDM_SC_SAMP])) if params[c.PARAMSET_FD_CH] else int(params[c.PARAMSET_NUM_PATHS])
             self._guard_host_copy(8 * int(self.n_ue) * n_ant[0] * n_ant[1] * last)
-        eng, prep = self._run_prep(want_side="light")
-        variant = int(config.get("fd_kernel_variant", 0))
-        out = eng.channels_to_host(prep, variant=variant) if to_host else eng.channels(prep, variant=variant)
+        inputs = self._prep_inputs()
+        direct, structs = self._run_single_pass(inputs, to_host)
+        if direct is not None:
+            out, max_delay = direct
+        else:
+            eng, prep = self._run_prep(want_side="light", inputs=inputs, structs=structs)
+            variant = int(config.get("fd_kernel_variant", 0))
+            out = eng.channels_to_host(prep, variant=variant) if to_host else eng.channels(prep, variant=variant)
+            max_delay = eng.max_delay(prep) if params[c.PARAMSET_FD_CH] else None
         ofdm = params[c.PARAMSET_OFDM]
         if params[c.PARAMSET_FD_CH]:
-            self._warn_symbol_duration(eng.max_delay(prep), ofdm)
+            self._warn_symbol_duration(max_delay, ofdm)
         self[c.CHANNEL_PARAM_NAME] = out
         return out
 

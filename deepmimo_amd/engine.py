@@ -5,6 +5,7 @@
 allocator / stream provider, not the compute path), fills the C structs of
 include/deepmimo_amd.h and calls the C-ABI:
 
+    dmx_channels_fd_direct -> complex64 [N, M_rx, M_tx, K] straight from the rays (small outputs, one launch)
     dmx_path_prep   -> per-path records + side products (LoS, path counts, FoV mask, angles, powers)
     dmx_channels_fd -> complex64 [N, M_rx, M_tx, K]     (dmx_channels_fd_lpf when rx_filter = 1)
     dmx_channels_td -> complex64 [N, M_rx, M_tx, P]
@@ -92,6 +93,55 @@ def check_selection(sel):
     if lo < -2 ** 31 or hi >= 2 ** 31:
         raise ValueError(f"selected_subcarriers holds {lo if lo < -2 ** 31 else hi}: subcarrier indices must fit int32")
     return sel, max(-lo, hi)
+
+
+# Single pass against the two calls: tools/direct_bench.py --sweep --paths L on an MI355X (200k users, average ms of 50
+# launches, routes alternating in one process; the same route differs by <= 0.005 ms between two passes, 0.02 at the
+# largest shape), at L = 10, 16, 25 and 40 loaded paths (num_paths = 25), shapes where variant 0 runs the small-output
+# kernel; profiles/r5_direct_sweep*.jsonl.  Speed-up two calls / single pass per class of table rows M_rx + M_tx:
+#   rows (BS / UE)                 K    L=10          L=16          L=25          L=40
+#   2..17  (1x1, 8x1, 4x4 / 1x1)   1,2  0.95-1.01     1.02-1.14     1.08-1.18     1.45-1.58
+#   33, 34 (8x4 / 1x1, 2x1)        1-4  1.02-1.16     1.09-1.22     1.04-1.20     1.33-1.48
+#   65, 66 (8x8 / 1x1, 2x1)        1,2  1.00-1.04     0.96-1.05     0.88-1.11     1.09-1.28
+#                                  4    1.07-1.15     0.99-1.15     1.12-1.14     1.30-1.31
+#   68     (8x8 / 2x2)             1,2  1.05          0.80-0.83     1.00-1.02     1.14-1.18
+#                                  4,8  1.21-1.22     0.95-1.10     1.16-1.24     1.32-1.34
+# The default call (8x1 / 1x1, K = 1): 0.222 | 0.223 ms at L = 10, 0.270 | 0.242 at 16, 0.314 | 0.271 at 25, 0.533 | 0.342
+# at 40.  The gain is the record round trip (it grows with the path count); the cost is that up to 32 loaded paths stage 1
+# packs two users into a wave and the fused kernel cannot, and that large tables leave the fused kernel's stage-1 part
+# fewer waves per SIMD than it has in a launch of its own.  The automatic choice keeps a class only where every
+# measured point of it is faster by more than the spread; everything else, and everything not measured (fewer than 10
+# loaded paths, more than 68 table rows, more than 8 subcarriers, K > 2 on the smallest panels), stays on the two calls.
+def single_pass_preferred(table_rows: int, loaded_paths: int, n_selected: int) -> bool:
+    """The measured crossover above: table_rows = M_rx + M_tx, loaded_paths = columns of the ray matrices."""
+    rows, L, K = int(table_rows), int(loaded_paths), int(n_selected)
+    if rows > 68 or K > 8 or L < 10:
+        return False
+    if L >= 33:                       # stage 1 runs one user per wave there too (measured at 40)
+        return True
+    if rows <= 17:
+        return L >= 16 and K <= 2
+    if rows <= 34:
+        return K <= 4
+    return L >= 25 and K >= 4
+
+
+def single_pass_route(single_pass, fd_kernel_variant, adaptive_precision, direct_supported, auto_choice, one_piece,
+                      preferred=True) -> bool:
+    """Whether ``Dataset.compute_channels`` takes the single-pass kernel (dmx_channels_fd_direct) instead of stage 1 +
+    stage 2.  All of: ``config('single_pass')`` is not False; the kernel variant is the automatic one (0) and adaptive
+    precision is off; the library takes the shape (dmx_fd_direct_supported == 1); variant 0 would run the small-output
+    kernel there (dmx_fd_kernel_choice == 9), so the arithmetic - and every output bit - is the one the two calls give;
+    the tensor leaves in one piece (resident, or a host copy `channels_to_host` would not chunk); and, for 'auto', the
+    shape is on the winning side of the measured crossover (`single_pass_preferred`).  ``single_pass = True`` takes the
+    route wherever it is possible, whatever the crossover says."""
+    if single_pass is False or single_pass is None or single_pass in (0, "off", "false", "False"):
+        return False
+    if int(fd_kernel_variant) != 0 or bool(adaptive_precision):
+        return False
+    if not (bool(direct_supported) and int(auto_choice) == 9 and bool(one_piece)):
+        return False
+    return True if single_pass is True else bool(preferred)
 
 
 def bounded_fd_variant(variant: int, sc_abs_max: int, small_preferred: bool) -> int:
@@ -198,13 +248,11 @@ class ChannelEngine:
     def _stream_ptr(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    # ------------------------------------------------------------------ stage 1
-    def prepare(self, rays: DeviceRays, params, bs_fov=None, ue_fov=None, ue_rotation_per_user=None,
-                carrier_freq: float = 0.0, want_side=True, adaptive_terms: bool = False) -> PrepResult:
-        """Run dmx_path_prep.  ue_rotation_per_user: optional [N, 3] degrees (numpy/torch).  want_side: True = every
-        side product, "light" = LoS / path counts / FoV mask only, False = none.  adaptive_terms: opt into
-        DMX_FLAG_ADAPTIVE_TERMS (include/deepmimo_amd.h: weak last path groups in one product term); the flag travels in
-        the parameter block of the preparation, so every stage-2 call on it runs in the same mode."""
+    def _call_structs(self, rays: DeviceRays, params, bs_fov=None, ue_fov=None, ue_rotation_per_user=None,
+                      carrier_freq: float = 0.0, adaptive_terms: bool = False):
+        """The dmx_params / dmx_rays of a call on `rays` (shared by `prepare` and `channels_direct`): checks the
+        selection, uploads it and the per-user rotation.  Returns (params struct, rays struct, tensors to keep alive,
+        largest |selected index|)."""
         dev = self.device
         n, L = rays.n_ue, rays.n_paths
         ofdm = params[c.PARAMSET_OFDM]
@@ -231,6 +279,21 @@ class ChannelEngine:
             setattr(r, k, rays.fields[k].data_ptr() if n * L > 0 else None)
         r.doppler_vel = rays.doppler_vel.data_ptr() if have_dop and n * L > 0 else None
         r.doppler_acc = rays.doppler_acc.data_ptr() if have_dop and n * L > 0 else None
+        return p, r, keep, sc_abs_max
+
+    # ------------------------------------------------------------------ stage 1
+    def prepare(self, rays: DeviceRays, params, bs_fov=None, ue_fov=None, ue_rotation_per_user=None,
+                carrier_freq: float = 0.0, want_side=True, adaptive_terms: bool = False, structs=None) -> PrepResult:
+        """Run dmx_path_prep.  ue_rotation_per_user: optional [N, 3] degrees (numpy/torch).  want_side: True = every
+        side product, "light" = LoS / path counts / FoV mask only, False = none.  adaptive_terms: opt into
+        DMX_FLAG_ADAPTIVE_TERMS (include/deepmimo_amd.h: weak last path groups in one product term); the flag travels in
+        the parameter block of the preparation, so every stage-2 call on it runs in the same mode.  structs: what
+        `_call_structs` returned for the same arguments, when the caller has built them already."""
+        dev = self.device
+        n, L = rays.n_ue, rays.n_paths
+        p, r, keep, sc_abs_max = structs or self._call_structs(rays, params, bs_fov, ue_fov, ue_rotation_per_user,
+                                                               carrier_freq, adaptive_terms)
+        keep = list(keep)
 
         nbytes = int(self.lib.dmx_workspace_bytes(C.byref(p), n, L))
         ws = torch.empty(max(nbytes, 256) + 256, dtype=torch.uint8, device=dev)
@@ -369,6 +432,69 @@ class ChannelEngine:
                                               C.c_void_p(out.data_ptr()), self._stream_ptr())
                 nat.check(rc, "dmx_channels_td")
         return out
+
+    # ------------------------------------------------------------------ single pass
+    def direct_supported(self, rays: DeviceRays, params, structs=None, **prepare_kwargs) -> bool:
+        """dmx_fd_direct_supported for these rays and parameters (host-only query; `channels_direct` raises where it
+        says no).  structs: what `_call_structs` returned for the same arguments, to build them once."""
+        p = (structs or self._call_structs(rays, params, **prepare_kwargs))[0]
+        rc = self.lib.dmx_fd_direct_supported(C.byref(p), rays.n_paths)
+        if rc < 0:
+            nat.check(rc, "dmx_fd_direct_supported")
+        return rc == 1
+
+    def auto_fd_choice(self, p: nat.DmxParams, n_paths_loaded: int, sc_abs_max: int) -> int:
+        """The kernel ``variant = 0`` runs for this parameter block (dmx_fd_kernel_choice, with `fd_variant`'s rule for
+        selections beyond the float32-phase bound that carry no spacing promise)."""
+        if sc_abs_max < SC_ABS_MAX_F32:
+            return int(self.lib.dmx_fd_kernel_choice(C.byref(p), n_paths_loaded))
+        q = nat.DmxParams.from_buffer_copy(p)
+        q.sc_first, q.sc_stride = 0, 0
+        return 9 if self.lib.dmx_fd_kernel_choice(C.byref(q), n_paths_loaded) == 9 else 1
+
+    def host_copy_chunks(self, n_users: int, per_user_elems: int) -> bool:
+        """True when `channels_to_host` would move a tensor of this size in more than one chunk."""
+        if n_users == 0 or per_user_elems == 0:
+            return False
+        return max(1, int(self.HOST_CHUNK_BYTES) // (per_user_elems * 8)) < n_users
+
+    def channels_direct(self, rays: DeviceRays, params, out: Optional[torch.Tensor] = None, user_begin: int = 0,
+                        user_count: Optional[int] = None, want_side="light", structs=None, **prepare_kwargs):
+        """Ray matrices -> frequency-domain channels in one launch (dmx_channels_fd_direct), no workspace: the small-
+        output shapes of variant 9, bit-identical to ``prepare(want_side="light")`` + ``channels(variant=9)``.
+        want_side: "light" = LoS / path counts / FoV mask (when a FoV is set) / delay maximum, False = the delay maximum
+        only; the rotated angles and powers are stage 1's (``prepare(want_side=True)``).  Returns (out, side) with
+        out = complex64 [user_count, M_rx, M_tx, K] and side tensors sized for ALL users of `rays` (the kernel writes
+        the rows of the users it ran).  structs: as for `direct_supported`.  Raises where the shape is not taken."""
+        if want_side not in ("light", False):
+            raise ValueError('channels_direct: want_side must be "light" or False (the heavy side products are stage 1\'s)')
+        dev = self.device
+        n, L = rays.n_ue, rays.n_paths
+        p, r, keep, _ = structs or self._call_structs(rays, params, **prepare_kwargs)
+        if user_count is None:
+            user_count = n - user_begin
+        shape = (user_count, p.ue_shape[0] * p.ue_shape[1], p.bs_shape[0] * p.bs_shape[1], p.n_selected)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.complex64, device=dev)
+        elif out.dtype != torch.complex64 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous complex64 tensor of shape {shape}")
+        side = {}
+        if want_side:
+            side["fov_mask"] = torch.empty((n, L), dtype=torch.uint8, device=dev) if p.fov_enabled else None
+            side["num_paths"] = torch.empty((n,), dtype=torch.int32, device=dev)
+            side["los"] = torch.empty((n,), dtype=torch.int32, device=dev)
+        side["max_delay_key"] = torch.zeros((1,), dtype=torch.int32, device=dev)
+        s = nat.DmxSide()
+        for k, t in side.items():
+            if t is not None and t.numel() > 0:
+                setattr(s, k, t.data_ptr())
+        with torch.cuda.device(dev):
+            rc = self.lib.dmx_channels_fd_direct(C.byref(r), C.byref(p), C.byref(s), int(user_begin), int(user_count),
+                                                 C.c_void_p(out.data_ptr()), self._stream_ptr())
+        nat.check(rc, "dmx_channels_fd_direct")
+        # `keep` (selection, rotations) may go out of scope: the launch is on torch's current stream and the caching
+        # allocator reuses freed blocks in stream order
+        return out, side
 
     # ------------------------------------------------------------------ stage 2 -> NumPy
     HOST_CHUNK_BYTES = 256 << 20          # per pipeline stage; two device buffers + two pinned staging buffers of this size

@@ -174,6 +174,29 @@ int dmx_channels_fd(const dmx_params* prm, const void* workspace, int64_t n_ue, 
 int dmx_fd_kernel_choice(const dmx_params* prm, int32_t n_paths_loaded);
 
 /*
+ * Single pass for small outputs: ray matrices -> frequency-domain channels in ONE launch, without a workspace (one
+ * wave per user keeps its compacted per-path records in LDS; k12_fd_direct.hip).  Meant for the shapes where variant 9
+ * runs (DeepMIMO's default call: 8 antenna pairs, one subcarrier), where the records' round trip through HBM is most
+ * of the two-call route's traffic.
+ *
+ * dmx_fd_direct_supported - host-only: 1 if dmx_channels_fd_direct takes this shape, 0 if not (call dmx_path_prep +
+ * dmx_channels_fd), negative on a bad argument.  No GPU involved.  Taken: freq_domain = 1, rx_filter = 0, flags = 0,
+ * 1 <= n_paths_loaded <= 64, 1 <= min(num_paths, n_paths_loaded) <= 32, n_selected >= 1, and one wave's records and
+ * tables (1408 + (M_rx + M_tx + K) * P * 8 bytes) within 156 KB.
+ */
+int dmx_fd_direct_supported(const dmx_params* prm, int32_t n_paths_loaded);
+
+/*
+ * Users [user_begin, user_begin + user_count) of `rays`; out = complex64 [user_count, M_rx, M_tx, K] of the first of
+ * them.  side: only fov_mask, num_paths, los, max_delay_key may be non-NULL (indexed by absolute user, as dmx_path_prep
+ * writes them; max_delay_key zeroed by the caller); any other non-NULL member is DMX_ERR_ARG.  Unsupported shape:
+ * DMX_ERR_SHAPE with a message that names the two-call route.
+ * Result: bit-identical to dmx_path_prep + dmx_channels_fd(variant = 9) on the same inputs and side pointers.
+ */
+int dmx_channels_fd_direct(const dmx_rays* rays, const dmx_params* prm, const dmx_side* side,
+                           int64_t user_begin, int64_t user_count, void* out_c64, void* stream);
+
+/*
  * Stage 2, frequency domain with the receive low-pass filter (ofdm.rx_filter = 1; replaces
  * channel.py:166-168, 193-194): g[l,k] = sum_d c_l sinc(d - dn_l) exp(-j 2pi d sc_k / N) is first
  * written to `lpf_workspace` (dmx_lpf_workspace_bytes(prm, user_count, n_paths_loaded) bytes,
