@@ -79,7 +79,39 @@ __device__ __forceinline__ float frac_rev(double t) {
     return (float)(t - rint(t));
 }
 
+// One wave's own LDS traffic is ordered by the hardware; this only stops the compiler from moving reads over writes
+// (the one-wave-per-user kernels k2_fd_small and k12_fd_direct have no workgroup barrier)
+__device__ __forceinline__ void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
 void set_error(const char* fmt, ...);
+
+// Waves per workgroup of the one-wave-per-user kernels from the LDS bytes one wave needs: four while 4 x fit the 64 KB a
+// workgroup gets by default, then two, then one; a single wave may take up to 156 KB (of the CU's 160 KB) with the
+// dynamic-LDS attribute raised.  0 = does not fit.
+static constexpr size_t WAVE_LDS_MAX = 156 * 1024;
+__host__ inline int lds_waves_per_block(size_t bytes_per_wave) {
+    if (bytes_per_wave == 0) return 0;
+    if (bytes_per_wave * 4 <= 64 * 1024) return 4;
+    if (bytes_per_wave * 2 <= 64 * 1024) return 2;
+    if (bytes_per_wave <= WAVE_LDS_MAX) return 1;
+    return 0;
+}
+
+// raise the kernel's dynamic-LDS attribute where the request needs it, launch, check
+template <class... Params, class... Args>
+int launch_dyn_lds(void (*kernel)(Params...), const char* name, dim3 g, dim3 b, size_t smem, hipStream_t stream, const Args&... args) {
+    if (smem > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WAVE_LDS_MAX);
+        if (e != hipSuccess) { set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
+    }
+    hipLaunchKernelGGL(kernel, g, b, smem, stream, args...);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("%s launch failed: %s", name, hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
+    return DMX_OK;
+}
 
 // compute units of the current device (persistent grids are sized from it)
 int device_cu_count();

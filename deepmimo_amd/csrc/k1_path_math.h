@@ -1,9 +1,10 @@
 // Per-path arithmetic of stage 1, shared by k1_path_prep.hip and the single-pass kernel k12_fd_direct.hip: the
-// constants, NumPy's float32 sin / cos, the float64 rotation, the field-of-view test, the dipole gain and the small
-// ballot helpers.  Every function is __forceinline__ and follows the reference's dtype flow; the including file
-// decides the FMA contraction: both k1_path_prep.hip and k12_fd_direct.hip are compiled with -ffp-contract=off (Makefile;
-// the single-pass kernel switches contraction back ON with a pragma after its stage-1 part), so both kernels evaluate
-// the very same operations.  stage1_form is the one rule by which both launchers pick the arithmetic form.
+// constants, NumPy's float32 sin / cos, the float64 rotation, the field-of-view test, the dipole gain, the small
+// ballot helpers, and on top of them stage1_path - the whole per-path body from the ray loads to the record values -
+// with the lane-0 epilogue stage1_user_out.  Every function is __forceinline__ and follows the reference's dtype flow;
+// the including file decides the FMA contraction: both k1_path_prep.hip and k12_fd_direct.hip are compiled with
+// -ffp-contract=off (Makefile), so both kernels evaluate the very same operations.  Stage1Params / stage1_params and
+// stage1_form are what both launchers pass and pick.
 #pragma once
 #include "dmx_common.h"
 #include <math.h>
@@ -161,6 +162,245 @@ __device__ __forceinline__ unsigned long long group_mask(unsigned long long b, i
 __device__ __forceinline__ uint32_t float_order_key(float f) {
     uint32_t b = __float_as_uint(f);
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// Stage 1's parameters as both kernels take them (PrepArgs of k1_path_prep.hip and DirectArgs of k12_fd_direct.hip embed it)
+struct Stage1Params {
+    double bsx, csx, bsy, csy, brz;       // sin/cos of BS rotation about x, y; rotation about z (rad)
+    double usx, ucx, usy, ucy, urz;       // same for a constant UE rotation
+    const double* ue_rot_pu;              // [n,3] degrees or nullptr
+    int fov_enabled, bs_restricted, ue_restricted;
+    double bs_fh, bs_fv, ue_fh, ue_fv;    // radians
+    int bs_pat, ue_pat;
+    double bs_spacing, ue_spacing;
+    int P;                                // paths used for the channel
+    int n_sc;
+    float ts32;                           // float32(1/bandwidth)
+    int doppler;
+    double fc;
+};
+__host__ inline Stage1Params stage1_params(const dmx_params& prm, int P) {
+    Stage1Params s;
+    s.bsx = sin(prm.bs_rotation[0]); s.csx = cos(prm.bs_rotation[0]);
+    s.bsy = sin(prm.bs_rotation[1]); s.csy = cos(prm.bs_rotation[1]);
+    s.brz = prm.bs_rotation[2];
+    s.usx = sin(prm.ue_rotation[0]); s.ucx = cos(prm.ue_rotation[0]);
+    s.usy = sin(prm.ue_rotation[1]); s.ucy = cos(prm.ue_rotation[1]);
+    s.urz = prm.ue_rotation[2];
+    s.ue_rot_pu = prm.ue_rotation_per_user;
+    s.fov_enabled = prm.fov_enabled; s.bs_restricted = prm.bs_fov_restricted; s.ue_restricted = prm.ue_fov_restricted;
+    s.bs_fh = prm.bs_fov[0]; s.bs_fv = prm.bs_fov[1]; s.ue_fh = prm.ue_fov[0]; s.ue_fv = prm.ue_fov[1];
+    s.bs_pat = prm.bs_pattern; s.ue_pat = prm.ue_pattern;
+    s.bs_spacing = prm.bs_spacing; s.ue_spacing = prm.ue_spacing;
+    s.P = P; s.n_sc = prm.n_subcarriers;
+    s.ts32 = (float)(1.0 / prm.bandwidth);
+    s.doppler = prm.enable_doppler; s.fc = prm.carrier_freq;
+    return s;
+}
+
+// the UE rotation of user u: the launch's constant one, or the user's own in degrees (dataset.py:329-338)
+__device__ __forceinline__ void stage1_ue_rotation(const Stage1Params& a, int64_t u, double& usx, double& ucx, double& usy,
+                                                   double& ucy, double& urz) {
+    usx = a.usx; ucx = a.ucx; usy = a.usy; ucy = a.ucy; urz = a.urz;
+    if (a.ue_rot_pu) {
+        const double rx = a.ue_rot_pu[3 * u + 0] * D2R_D, ry = a.ue_rot_pu[3 * u + 1] * D2R_D;
+        urz = a.ue_rot_pu[3 * u + 2] * D2R_D;
+        sincos(rx, &usx, &ucx);
+        sincos(ry, &usy, &ucy);
+    }
+}
+
+// What stage1_path yields for one lane's path: the record values, and whether the path takes a record slot
+struct Stage1Path {
+    float c_re, c_im, dn;                 // dn = 0 in the time domain
+    double ty, tz, ry, rz;
+    float dvel, dacc;                     // the rays' Doppler terms as loaded (0 without Doppler)
+    bool keep;
+};
+// A user's light side products as they build up over the passes of its lanes; every pass of stage1_path adds its share.
+// count_paths / has_fov_path / first_inter are the same in every lane of the user's group, maxd / any_delay are per lane
+// and reduced by stage1_user_out's caller.
+struct Stage1User {
+    int count_paths = 0;                  // dataset.py:616-619
+    bool has_fov_path = false;            // FoV on: some path so far is inside
+    float first_inter = __int_as_float(0x7fc00000);   // interaction code of the first path (FoV on: the first inside)
+    float maxd = -INFINITY;               // largest delay of a used path
+    bool any_delay = false;
+};
+
+// Path j of user u - k1_path_prep's loop body and k12_fd_direct's phase A.  LPU = lanes per user, `in` = the lane has a
+// path of a real user, grp = the user's group in the wave, first_pass = j is among the user's first LPU paths; the
+// pass's share of the per-user side products goes into `us` (updated in place for the register count).  The
+// side outputs that are per path (angles, powers, FoV mask) are written here; a kernel that does not have one passes a
+// constant nullptr in `side` and that code is compiled out, as it is for freq_domain / rx_filter given as constants.
+template <int LPU, bool LEAN, bool ZROT>
+__device__ __forceinline__ Stage1Path stage1_path(const Stage1Params& a, const dmx_rays& r, const dmx_side& side,
+                                                  const int freq_domain, const int rx_filter, const int need_angles,
+                                                  const double usx, const double ucx, const double usy, const double ucy,
+                                                  const double urz, const int64_t u, const int j, const bool in, const int grp,
+                                                  const bool first_pass, Stage1User& us) {
+    const int L = r.n_paths;
+    const size_t row = (size_t)u * (size_t)r.ld;
+    const size_t srow = (size_t)u * (size_t)L;              // dense side-product rows
+    const bool iso = (a.bs_pat == DMX_PATTERN_ISOTROPIC) && (a.ue_pat == DMX_PATTERN_ISOTROPIC);
+    const float nan32 = __int_as_float(0x7fc00000);
+    const double nan64 = (double)nan32;
+    Stage1Path o;
+
+    // Eight loads issued TOGETHER, from an index every lane may read (idle lanes: the user's last path), masked
+    // afterwards.  Written as `in ? array[row + j] : nan`, each load sat alone in a branch of its own with an
+    // `s_waitcnt vmcnt(0)` behind it: eight memory round trips in a row were the 8 us a wave lived (SQ_WAVE_CYCLES /
+    // SQ_WAVES, profiles/r3_d8_summary.txt) and 0.20-0.28 ms of stage 1 per 200k users.
+    const size_t jc = row + (size_t)(j < L ? j : L - 1);
+    const float power_r = r.power[jc], phase_r = r.phase[jc], delay_r = r.delay[jc], aoa_az_r = r.aoa_az[jc];
+    const float aoa_el_r = r.aoa_el[jc], aod_az_r = r.aod_az[jc], aod_el_r = r.aod_el[jc], inter_r = r.inter[jc];
+    const bool dop_rays = a.doppler && r.doppler_vel && r.doppler_acc;       // kernel-uniform
+    o.dvel = 0.f; o.dacc = 0.f;
+    if (dop_rays) { o.dvel = r.doppler_vel[jc]; o.dacc = r.doppler_acc[jc]; }    // in the same batch
+    const float power = in ? power_r : nan32;
+    const float phase = in ? phase_r : nan32;
+    const float delay = in ? delay_r : nan32;
+    const float aoa_az = in ? aoa_az_r : nan32;
+    const float aoa_el = in ? aoa_el_r : nan32;
+    const float aod_az = in ? aod_az_r : nan32;
+    const float aod_el = in ? aod_el_r : nan32;
+    const float inter = in ? inter_r : nan32;
+
+    double zc_t, re_t, im_t, zc_r, re_r, im_r, sphi_t = 0.0, sphi_r = 0.0;
+    if constexpr (ZROT) {
+        rotate_dir_zero(aod_el, aod_az, zc_t, re_t, im_t, sphi_t);
+        rotate_dir_zero(aoa_el, aoa_az, zc_r, re_r, im_r, sphi_r);
+    } else {
+        rotate_dir<LEAN>(aod_el, aod_az, a.bsx, a.csx, a.bsy, a.csy, a.brz, zc_t, re_t, im_t);
+        rotate_dir<LEAN>(aoa_el, aoa_az, usx, ucx, usy, ucy, urz, zc_r, re_r, im_r);
+    }
+    // arccos is NaN outside [-1, 1]; np.angle is NaN only for NaN input
+    double th_t = (isnan(zc_t) || fabs(zc_t) > 1.0) ? nan64 : 0.0, ph_t = (isnan(re_t) || isnan(im_t)) ? nan64 : 0.0;
+    double th_r = (isnan(zc_r) || fabs(zc_r) > 1.0) ? nan64 : 0.0, ph_r = (isnan(re_r) || isnan(im_r)) ? nan64 : 0.0;
+    if constexpr (!LEAN) {
+        if (need_angles) {                               // wave-uniform
+            th_t = acos(zc_t); ph_t = atan2(im_t, re_t);
+            th_r = acos(zc_r); ph_r = atan2(im_r, re_r);
+        }
+        if (in) {
+            if (side.aod_el_rot) side.aod_el_rot[srow + j] = th_t;
+            if (side.aod_az_rot) side.aod_az_rot[srow + j] = ph_t;
+            if (side.aoa_el_rot) side.aoa_el_rot[srow + j] = th_r;
+            if (side.aoa_az_rot) side.aoa_az_rot[srow + j] = ph_r;
+        }
+    }
+
+    // field of view (dataset.py:493-511): outside -> angles become NaN
+    bool mask = true;
+    if (!LEAN && a.fov_enabled) {
+        if (a.bs_restricted) mask = mask && in_fov(th_t, ph_t, a.bs_fh, a.bs_fv);
+        if (a.ue_restricted) mask = mask && in_fov(th_r, ph_r, a.ue_fh, a.ue_fv);
+        mask = mask && in;
+        if (in && side.fov_mask) side.fov_mask[srow + j] = mask ? 1 : 0;
+        if (!mask) { th_t = nan64; ph_t = nan64; th_r = nan64; ph_r = nan64; }
+        const unsigned long long mb = group_mask<LPU>(__ballot(mask), grp);
+        // first in-FoV path (dataset.py:594-598); the shuffle is executed by every lane, the
+        // result is kept only by groups that had no in-FoV path yet
+        const int src = mb != 0ull ? __ffsll((long long)mb) - 1 : 0;
+        const float cand = __shfl(inter, src, LPU);
+        if (!us.has_fov_path && mb != 0ull) { us.has_fov_path = true; us.first_inter = cand; }
+    } else if (first_pass) {
+        us.first_inter = __shfl(inter, 0, LPU);          // dataset.py:602
+    }
+    us.count_paths += __popcll(group_mask<LPU>(__ballot(in && !isnan(ph_r)), grp));   // dataset.py:616-619
+
+    // powers (generator_utils.py:35, ant_patterns.py:167-168)
+    const float p10 = power / 10.0f;
+    const float pl = exp10f(p10);                        // float32 pow, as NumPy evaluates 10**float32
+    double pw;
+    if (LEAN || iso) {
+        pw = (double)pl;
+    } else {
+        const double gt = a.bs_pat == DMX_PATTERN_HALFWAVE_DIPOLE ? dipole_gain(th_t) : 1.0;
+        const double gr = a.ue_pat == DMX_PATTERN_HALFWAVE_DIPOLE ? dipole_gain(th_r) : 1.0;
+        pw = (double)pl * (gt * gr);
+    }
+    if constexpr (!LEAN) {
+        if (in) {
+            if (side.power_linear) side.power_linear[srow + j] = pl;
+            if (side.power_linear_ant_gain) side.power_linear_ant_gain[srow + j] = pw;
+        }
+    }
+
+    // per-path record for the first P paths (dataset.py:258-261)
+    const bool used = in && j < a.P;
+    if (used && !isnan(delay)) { us.maxd = fmaxf(us.maxd, delay); us.any_delay = true; }
+    const bool valid = used && !isnan(pw);               // channel.py:260
+    const float ph32 = phase * D2R_F;                    // np.deg2rad(float32)
+    float e_re, e_im;
+    np_sincosf(ph32, e_im, e_re);                        // complex64 exp: NumPy's float32 cos / sin (and NaN-cheap, see there)
+    const bool ang_ok = !isnan(th_t) && !isnan(th_r);    // geometry.py:65 zeroes NaN-zenith columns
+    float c_re, c_im, dn = 0.0f;
+    if (freq_domain) {
+        dn = delay / a.ts32;                             // float32 / float32 (channel.py:183)
+        double pwc = pw;
+        if (dn >= (float)a.n_sc) { pwc = 0.0; dn = (float)a.n_sc; }   // channel.py:187-189
+        if (LEAN || iso) {
+            const float amp = sqrtf((float)pwc / (float)a.n_sc);      // float32 (channel.py:192)
+            c_re = amp * e_re; c_im = amp * e_im;
+        } else {
+            const double amp = sqrt(pwc / (double)a.n_sc);
+            c_re = (float)(amp * (double)e_re); c_im = (float)(amp * (double)e_im);
+        }
+        if (dop_rays && !rx_filter) {                                        // construct_deepmimo.py:267-280
+            const double v = in ? (double)o.dvel : 0.0;
+            const double ac = in ? (double)o.dacc : 0.0;
+            const double tau = (double)delay;
+            const double arg = -TWO_PI * a.fc * (v * tau / LIGHTSPEED + ac * (tau * tau) / (2.0 * LIGHTSPEED));
+            double sd, cd;
+            sincos(arg, &sd, &cd);
+            const float nr = (float)((double)c_re * cd - (double)c_im * sd);
+            const float ni = (float)((double)c_re * sd + (double)c_im * cd);
+            c_re = nr; c_im = ni;
+        }
+        // nansum (channel.py:283): a path with any NaN factor contributes nothing
+        o.keep = valid && ang_ok && !isnan(ph_t) && !isnan(ph_r) && !isnan(c_re) && !isnan(c_im) && !isnan(dn) &&
+                 (c_re != 0.0f || c_im != 0.0f);        // clipped / zero-gain paths add exactly 0
+    } else {
+        if (LEAN || iso) {
+            const float amp = sqrtf((float)pw);                        // channel.py:286
+            c_re = amp * e_re; c_im = amp * e_im;
+        } else {
+            const double amp = sqrt(pw);
+            c_re = (float)(amp * (double)e_re); c_im = (float)(amp * (double)e_im);
+        }
+        if (!ang_ok) { c_re *= 0.0f; c_im *= 0.0f; }                   // zero array response, NaN stays NaN
+        o.keep = valid;                                                // slot even if coefficient is 0
+    }
+    o.c_re = c_re; o.c_im = c_im; o.dn = dn;
+    o.ty = 0.0; o.tz = 0.0; o.ry = 0.0; o.rz = 0.0;
+    if (ang_ok && ZROT) {
+        o.ty = a.bs_spacing * (sqrt(1.0 - zc_t * zc_t) * sphi_t); o.tz = a.bs_spacing * zc_t;
+        o.ry = a.ue_spacing * (sqrt(1.0 - zc_r * zc_r) * sphi_r); o.rz = a.ue_spacing * zc_r;
+    } else if (ang_ok) {                                 // geometry.py:99-101 in revolutions (kd / 2pi = spacing)
+        const double rho_t = sqrt(re_t * re_t + im_t * im_t), rho_r = sqrt(re_r * re_r + im_r * im_r);
+        o.ty = a.bs_spacing * (sqrt(1.0 - zc_t * zc_t) * (rho_t > 0.0 ? im_t / rho_t : 0.0)); o.tz = a.bs_spacing * zc_t;
+        o.ry = a.ue_spacing * (sqrt(1.0 - zc_r * zc_r) * (rho_r > 0.0 ? im_r / rho_r : 0.0)); o.rz = a.ue_spacing * zc_r;
+    }
+    return o;
+}
+
+// A user's light side products, by lane 0 of the user's group once its passes are done; maxd = us.maxd reduced over the
+// group's lanes, anyd = any of them had a delay
+__device__ __forceinline__ void stage1_user_out(const dmx_side& side, const int fov_enabled, const int64_t u,
+                                                const Stage1User& us, const float maxd, const bool anyd) {
+    if (side.num_paths) side.num_paths[u] = us.count_paths;
+    if (side.los) {
+        const bool has = fov_enabled ? us.has_fov_path : (us.count_paths > 0);
+        side.los[u] = has ? ((us.first_inter == 0.0f) ? 1 : 0) : -1;    // dataset.py:604-609
+    }
+    // one running maximum for the whole launch: a returning atomic per user would serialise 1e5 updates on
+    // one L2 word (~88 per us), so look first (relaxed, L2-served) and only update when this user raises it
+    if (side.max_delay_key && anyd) {
+        const uint32_t key = float_order_key(maxd);
+        if (key > __hip_atomic_load(side.max_delay_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            atomicMax(side.max_delay_key, key);
+    }
 }
 
 // The arithmetic form of stage 1 for a launch - ONE rule for launch_path_prep and launch_channels_fd_direct, whose

@@ -10,6 +10,7 @@
 //   the array-response phase    geometry.py:85-102
 // and emits per-path records (dmx_common.h) with the contributing paths compacted to the front
 // of each user's row (wave ballot + prefix popcount), so stage 2 never touches a dead path.
+// The per-path arithmetic itself is stage1_path in k1_path_math.h, which the single-pass kernel (k12_fd_direct.hip) runs too.
 //
 // Numerics follow the reference's dtype flow on purpose (DESIGN.md "numerics"): deg2rad in
 // float32, sin/cos of the zenith angle rounded to float32, everything touching the rotation in
@@ -24,6 +25,88 @@
 namespace dmx {
 
 struct PrepArgs {
+    dmx_rays rays;
+    dmx_side side;
+    WsView ws;
+    Stage1Params s1;                       // k1_path_math.h: what the single-pass kernel takes too
+    int freq_domain;
+    int rx_filter;
+    int need_angles;                       // angles wanted as numbers (side outputs, FoV, dipole), not just directions
+    int sort_paths;                        // frequency domain: kept paths ordered by falling amplitude (the sum does not care;
+                                           // stage 2 drops product terms of a weak last K-step, k2_channel_fd_mfma.hip)
+};
+
+// The LEAN forms: nothing needs the angles as numbers (no FoV, isotropic patterns, no angle / power side outputs - what
+// compute_channels and bench.py run), so the arccos / atan2 / FoV / dipole code of stage1_path is compiled out, which
+// takes the kernel from 228 to far fewer registers, i.e. from 2 to 3-4 waves per SIMD on a kernel that waits on its loads
+// and stores.  LPU = lanes per user (32: two users share a wave; 64: one user per wave, any path count).  ZROT: both
+// rotations are exactly zero and the same for every user.  The per-path arithmetic is stage1_path (k1_path_math.h); here
+// are the passes over a user's paths, the record slots, the workspace writes and the reductions.  The form that does
+// need the angles is k1_path_prep_full below.
+#ifndef K1_WAVES
+#define K1_WAVES 4                                          // waves per workgroup (every wave works alone)
+#endif
+template <int LPU, bool ZROT = false>
+__global__ __launch_bounds__(64 * K1_WAVES, 16 / K1_WAVES) void k1_path_prep(PrepArgs a) {
+    constexpr int UPW = 64 / LPU;                           // users per wave
+    const int lane = threadIdx.x & (LPU - 1);               // lane inside the user's group
+    const int grp = (threadIdx.x & 63) / LPU;               // which group of the wave
+    const int64_t u_raw = ((int64_t)blockIdx.x * K1_WAVES + (threadIdx.x >> 6)) * UPW + grp;
+    const bool u_ok = u_raw < a.rays.n_ue;
+    if (__ballot(u_ok) == 0ull) return;                     // whole wave past the end
+    const int64_t u = u_ok ? u_raw : a.rays.n_ue - 1;       // idle group shadows the last user, writes nothing
+    const int L = a.rays.n_paths;
+    const size_t wrow = (size_t)u * (size_t)a.s1.P;
+
+    double usx, ucx, usy, ucy, urz;
+    stage1_ue_rotation(a.s1, u, usx, ucx, usy, ucy, urz);
+
+    int keep_base = 0;
+    Stage1User us;
+
+    for (int j0 = 0; j0 < L; j0 += LPU) {
+        const int j = j0 + lane;
+        const Stage1Path p = stage1_path<LPU, true, ZROT>(a.s1, a.rays, a.side, a.freq_domain, a.rx_filter, a.need_angles,
+                                                          usx, ucx, usy, ucy, urz, u, j, u_ok && j < L, grp, j0 == 0, us);
+        const unsigned long long kb = group_mask<LPU>(__ballot(p.keep), grp);
+        int rank = 0;
+        const bool sorted = a.sort_paths && L <= LPU;          // kernel-uniform; the whole user is in this one pass
+        if (sorted) {
+            // rank among the kept paths by |c|^2, ties by path index: 0 = strongest.  Lanes that keep nothing carry -1.
+            const float key = p.keep ? p.c_re * p.c_re + p.c_im * p.c_im : -1.0f;
+            for (int jj = 0; jj < L; ++jj) {
+                const float kj = __shfl(key, jj, LPU);
+                rank += (kj > key || (kj == key && jj < lane)) ? 1 : 0;
+            }
+        }
+        if (p.keep) {
+            const int slot = sorted ? rank : keep_base + __popcll(kb & ((1ull << lane) - 1ull));
+            a.ws.c_re[wrow + slot] = p.c_re; a.ws.c_im[wrow + slot] = p.c_im; a.ws.dn[wrow + slot] = p.dn;
+            a.ws.tx_y[wrow + slot] = p.ty; a.ws.tx_z[wrow + slot] = p.tz;
+            a.ws.rx_y[wrow + slot] = p.ry; a.ws.rx_z[wrow + slot] = p.rz;
+            a.ws.dop_v[wrow + slot] = p.dvel;                                    // 0 without Doppler; `keep` lanes are `in` lanes
+            a.ws.dop_a[wrow + slot] = p.dacc;
+        }
+        keep_base += __popcll(kb);
+    }
+
+    // wave reductions
+    float maxd = us.maxd;
+    for (int off = LPU / 2; off > 0; off >>= 1) maxd = fmaxf(maxd, __shfl_xor(maxd, off, LPU));
+    const bool anyd = group_mask<LPU>(__ballot(us.any_delay), grp) != 0ull;
+    if (lane == 0 && u_ok) {
+        a.ws.n_keep[u] = keep_base;
+        stage1_user_out(a.side, a.s1.fov_enabled, u, us, maxd, anyd);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The FULL form (something needs the angles as numbers) is deliberately NOT on the shared body: on stage1_path its two
+// instantiations ran 1.4 - 1.9 % longer than before at the same occupancy, beyond the spread, and
+// the cause was not found in the disassembly.  It keeps its own argument struct and the inline loop body it had; whatever
+// changes in stage1_path (k1_path_math.h) has to be made here too, and tests/test_gpu_fd_direct.py (the FoV and dipole
+// cases run k12_fd_direct's MODE 0 = stage1_path against this kernel, torch.equal) notices if it is not.
+struct PrepArgsFull {
     dmx_rays rays;
     dmx_side side;
     WsView ws;
@@ -48,16 +131,9 @@ struct PrepArgs {
     double fc;
 };
 
-// LPU = lanes per user (32: two users share a wave; 64: one user per wave, any path count).
-// LEAN = nothing needs the angles as numbers (no FoV, isotropic patterns, no angle / power side outputs - what
-// compute_channels and bench.py run): the arccos / atan2 / FoV / dipole code is compiled out, which takes the kernel
-// from 228 to far fewer registers, i.e. from 2 to 3-4 waves per SIMD on a kernel that waits on its loads and stores.
-// ZROT (with LEAN): both rotations are exactly zero and the same for every user.
-#ifndef K1_WAVES
-#define K1_WAVES 4                                          // waves per workgroup (every wave works alone)
-#endif
-template <int LPU, bool LEAN, bool ZROT = false>
-__global__ __launch_bounds__(64 * K1_WAVES, (LEAN ? 16 : 8) / K1_WAVES) void k1_path_prep(PrepArgs a) {
+template <int LPU>
+__global__ __launch_bounds__(64 * K1_WAVES, 8 / K1_WAVES) void k1_path_prep_full(PrepArgsFull a) {
+    constexpr bool LEAN = false, ZROT = false;
     constexpr int UPW = 64 / LPU;                           // users per wave
     const int lane = threadIdx.x & (LPU - 1);               // lane inside the user's group
     const int grp = (threadIdx.x & 63) / LPU;               // which group of the wave
@@ -270,37 +346,38 @@ __global__ __launch_bounds__(64 * K1_WAVES, (LEAN ? 16 : 8) / K1_WAVES) void k1_
 
 int launch_path_prep(const dmx_rays& rays, const dmx_params& prm, const WsView& ws, const dmx_side& side,
                      hipStream_t stream) {
-    PrepArgs a;
-    a.rays = rays; a.side = side; a.ws = ws;
-    a.bsx = sin(prm.bs_rotation[0]); a.csx = cos(prm.bs_rotation[0]);
-    a.bsy = sin(prm.bs_rotation[1]); a.csy = cos(prm.bs_rotation[1]);
-    a.brz = prm.bs_rotation[2];
-    a.usx = sin(prm.ue_rotation[0]); a.ucx = cos(prm.ue_rotation[0]);
-    a.usy = sin(prm.ue_rotation[1]); a.ucy = cos(prm.ue_rotation[1]);
-    a.urz = prm.ue_rotation[2];
-    a.ue_rot_pu = prm.ue_rotation_per_user;
-    a.fov_enabled = prm.fov_enabled; a.bs_restricted = prm.bs_fov_restricted; a.ue_restricted = prm.ue_fov_restricted;
-    a.bs_fh = prm.bs_fov[0]; a.bs_fv = prm.bs_fov[1]; a.ue_fh = prm.ue_fov[0]; a.ue_fv = prm.ue_fov[1];
-    a.bs_pat = prm.bs_pattern; a.ue_pat = prm.ue_pattern;
-    a.bs_spacing = prm.bs_spacing; a.ue_spacing = prm.ue_spacing;
-    a.P = ws.P; a.freq_domain = prm.freq_domain; a.n_sc = prm.n_subcarriers;
-    a.ts32 = (float)(1.0 / prm.bandwidth);
-    a.doppler = prm.enable_doppler; a.fc = prm.carrier_freq; a.rx_filter = prm.rx_filter && prm.freq_domain;
+    if (rays.n_ue == 0) return DMX_OK;
+    const Stage1Params s1 = stage1_params(prm, ws.P);
+    const int rx_filter = prm.rx_filter && prm.freq_domain;
     // amplitude order only where something uses it: the opt-in adaptive precision of stage 2 (frequency domain; the
     // time-domain slots keep the path order, channel.py:285-287).  25 lane shuffles per user otherwise saved.
-    a.sort_paths = (prm.freq_domain && (prm.flags & DMX_FLAG_ADAPTIVE_TERMS)) ? 1 : 0;
-    a.need_angles = stage1_need_angles(prm, side);
-    if (rays.n_ue == 0) return DMX_OK;
+    const int sort_paths = (prm.freq_domain && (prm.flags & DMX_FLAG_ADAPTIVE_TERMS)) ? 1 : 0;
+    const int need_angles = stage1_need_angles(prm, side);
     const Stage1Form form = stage1_form(prm, side, rays.n_paths);            // k1_path_math.h: shared with the single pass
-    if (rays.n_paths <= 32) {
-        const unsigned grid = (unsigned)((rays.n_ue + 2 * K1_WAVES - 1) / (2 * K1_WAVES));
-        if (form == STAGE1_LEAN_ZROT) hipLaunchKernelGGL((k1_path_prep<32, true, true>), dim3(grid), dim3(64 * K1_WAVES), 0, stream, a);
-        else if (form == STAGE1_LEAN) hipLaunchKernelGGL((k1_path_prep<32, true>), dim3(grid), dim3(64 * K1_WAVES), 0, stream, a);
-        else hipLaunchKernelGGL((k1_path_prep<32, false>), dim3(grid), dim3(64 * K1_WAVES), 0, stream, a);
+    const bool two = rays.n_paths <= 32;                                     // two users per wave
+    const int upb = (two ? 2 : 1) * K1_WAVES;
+    const dim3 grid((unsigned)((rays.n_ue + upb - 1) / upb)), block(64 * K1_WAVES);
+    if (form == STAGE1_FULL) {
+        PrepArgsFull a;
+        a.rays = rays; a.side = side; a.ws = ws;
+        a.bsx = s1.bsx; a.csx = s1.csx; a.bsy = s1.bsy; a.csy = s1.csy; a.brz = s1.brz;
+        a.usx = s1.usx; a.ucx = s1.ucx; a.usy = s1.usy; a.ucy = s1.ucy; a.urz = s1.urz;
+        a.ue_rot_pu = s1.ue_rot_pu;
+        a.fov_enabled = s1.fov_enabled; a.bs_restricted = s1.bs_restricted; a.ue_restricted = s1.ue_restricted;
+        a.bs_fh = s1.bs_fh; a.bs_fv = s1.bs_fv; a.ue_fh = s1.ue_fh; a.ue_fv = s1.ue_fv;
+        a.bs_pat = s1.bs_pat; a.ue_pat = s1.ue_pat;
+        a.bs_spacing = s1.bs_spacing; a.ue_spacing = s1.ue_spacing;
+        a.P = s1.P; a.freq_domain = prm.freq_domain; a.n_sc = s1.n_sc; a.ts32 = s1.ts32;
+        a.doppler = s1.doppler; a.rx_filter = rx_filter; a.need_angles = need_angles; a.sort_paths = sort_paths; a.fc = s1.fc;
+        if (two) hipLaunchKernelGGL((k1_path_prep_full<32>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((k1_path_prep_full<64>), grid, block, 0, stream, a);
     } else {
-        const unsigned grid = (unsigned)((rays.n_ue + K1_WAVES - 1) / K1_WAVES);
-        if (form != STAGE1_FULL) hipLaunchKernelGGL((k1_path_prep<64, true>), dim3(grid), dim3(64 * K1_WAVES), 0, stream, a);
-        else hipLaunchKernelGGL((k1_path_prep<64, false>), dim3(grid), dim3(64 * K1_WAVES), 0, stream, a);
+        PrepArgs a;
+        a.rays = rays; a.side = side; a.ws = ws; a.s1 = s1;
+        a.freq_domain = prm.freq_domain; a.rx_filter = rx_filter; a.need_angles = need_angles; a.sort_paths = sort_paths;
+        if (!two) hipLaunchKernelGGL((k1_path_prep<64>), grid, block, 0, stream, a);
+        else if (form == STAGE1_LEAN_ZROT) hipLaunchKernelGGL((k1_path_prep<32, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((k1_path_prep<32>), grid, block, 0, stream, a);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("k1_path_prep launch failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }

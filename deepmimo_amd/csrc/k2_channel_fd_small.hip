@@ -13,108 +13,29 @@
 // kernels (dataset.py:398-417 + channel.py:264-284; same record layout, first 32 kept paths, the rest through
 // launch_extra_path_passes).  Bound: VALU / LDS issue (tables), far below HBM: the regime is latency, not bandwidth.
 #include "dmx_common.h"
+#include "k2_small_body.h"
 
 namespace dmx {
 
-struct SmallArgs {
-    int64_t user_begin, user_count;
-    int m_rx, m_tx, ue_mh, bs_mh;
-    int K;
-    const int32_t* sc;
-    double inv_n;
-    int ld;          // table row stride in path slots = min(P, 32)
-};
-
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
+// the tables and the output loop are small_user_block (k2_small_body.h), shared with the single-pass kernel
 template <int KC>
 __global__ __launch_bounds__(256) void k2_fd_small(WsView ws, SmallArgs a, float2* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
-    const int ld = a.ld, K = a.K, M = a.m_rx * a.m_tx;
-    const int per_wave = (a.m_rx + a.m_tx + K) * ld;
+    const int per_wave = (a.m_rx + a.m_tx + a.K) * a.ld;
     float2* brx = reinterpret_cast<float2*>(smem_raw) + (size_t)wave * per_wave;   // [m_rx][ld]
-    float2* atx = brx + (size_t)a.m_rx * ld;                                        // [m_tx][ld]
-    float2* g = atx + (size_t)a.m_tx * ld;                                          // [ld][K]
-    const int nchunk = (K + KC - 1) / KC;
-    const int total = M * nchunk;
-
+    float2* atx = brx + (size_t)a.m_rx * a.ld;                                      // [m_tx][ld]
+    float2* g = atx + (size_t)a.m_tx * a.ld;                                        // [ld][K]
     for (int64_t ul = (int64_t)blockIdx.x * wpb + wave; ul < a.user_count; ul += (int64_t)gridDim.x * wpb) {
         const int64_t u = a.user_begin + ul;
-        float2* o = out + (size_t)ul * M * K;
-        int n_act = ws.n_keep[u];
-        n_act = n_act < ld ? n_act : ld;
-        if (n_act == 0) {                                                   // channel.py:270-271
-            for (int i = lane; i < M * K; i += 64) o[i] = make_float2(0.f, 0.f);
-            continue;
-        }
-        const size_t rb = (size_t)u * ws.P;
-        wave_lds_fence();                                                   // previous user's table reads are done
-        for (int i = lane; i < a.m_rx * n_act; i += 64) {
-            const int r = i / n_act, l = i - r * n_act;
-            float s, c;
-            sincos_rev(frac_rev((double)(r % a.ue_mh) * ws.rx_y[rb + l] + (double)(r / a.ue_mh) * ws.rx_z[rb + l]), s, c);
-            const float cr = ws.c_re[rb + l], ci = ws.c_im[rb + l];
-            brx[r * ld + l] = make_float2(cr * c - ci * s, cr * s + ci * c);
-        }
-        for (int i = lane; i < a.m_tx * n_act; i += 64) {
-            const int t = i / n_act, l = i - t * n_act;
-            float s, c;
-            sincos_rev(frac_rev((double)(t % a.bs_mh) * ws.tx_y[rb + l] + (double)(t / a.bs_mh) * ws.tx_z[rb + l]), s, c);
-            atx[t * ld + l] = make_float2(c, s);
-        }
-        for (int i = lane; i < n_act * K; i += 64) {
-            const int l = i / K, k = i - l * K;
-            float s, c;
-            sincos_rev(frac_rev((double)ws.dn[rb + l] * a.inv_n * (double)a.sc[k]), s, c);
-            g[l * K + k] = make_float2(c, -s);                              // exp(-j 2pi x) = cos - j sin
-        }
-        wave_lds_fence();
-
-        for (int e = lane; e < total; e += 64) {
-            const int p = e / nchunk, k0 = (e - p * nchunk) * KC;
-            const int rx = p / a.m_tx, tx = p - rx * a.m_tx;
-            const float2* br = brx + rx * ld;
-            const float2* at = atx + tx * ld;
-            int kj[KC];
-#pragma unroll
-            for (int j = 0; j < KC; ++j) kj[j] = (k0 + j) < K ? (k0 + j) : (K - 1);
-            float2 acc[KC];
-#pragma unroll
-            for (int j = 0; j < KC; ++j) acc[j] = make_float2(0.f, 0.f);
-            for (int l = 0; l < n_act; ++l) {
-                const float2 b = br[l], t = at[l];
-                const float wr = b.x * t.x - b.y * t.y, wi = b.x * t.y + b.y * t.x;
-                const float2* gl = g + l * K;
-#pragma unroll
-                for (int j = 0; j < KC; ++j) {
-                    const float2 v = gl[kj[j]];
-                    acc[j].x += wr * v.x - wi * v.y;
-                    acc[j].y += wr * v.y + wi * v.x;
-                }
-            }
-            float2* dst = o + (size_t)p * K + k0;
-#pragma unroll
-            for (int j = 0; j < KC; ++j)
-                if (k0 + j < K) dst[j] = acc[j];
-        }
+        small_user_block<KC, 1>(a, WsRecords{ws, (size_t)u * ws.P}, ws.n_keep[u], lane, brx, atx, g,
+                             out + (size_t)ul * a.m_rx * a.m_tx * a.K);
     }
 }
 
-// One wave's tables: four waves share a workgroup while 4 x tables fit the 64 KB a workgroup gets by default, then
-// two, then one; a single wave may take up to 156 KB (of the CU's 160 KB) with the dynamic-LDS attribute raised.
-static constexpr size_t SMALL_LDS_MAX = 156 * 1024;
+static int small_ld(const WsView& ws) { return ws.P < 32 ? ws.P : 32; }      // first 32 kept paths, the rest through launch_extra_path_passes
 static int small_waves_per_block(const dmx_params& prm, const WsView& ws) {
-    const int ld = ws.P < 32 ? ws.P : 32;
-    const size_t bytes = (size_t)(prm.ue_shape[0] * prm.ue_shape[1] + prm.bs_shape[0] * prm.bs_shape[1] + prm.n_selected) * ld * 8;
-    if (bytes == 0) return 0;
-    if (bytes * 4 <= 64 * 1024) return 4;
-    if (bytes * 2 <= 64 * 1024) return 2;
-    if (bytes <= SMALL_LDS_MAX) return 1;
-    return 0;
+    return lds_waves_per_block(small_table_bytes(prm, small_ld(ws)));
 }
 
 bool fd_small_supported(const dmx_params& prm, const WsView& ws) { return small_waves_per_block(prm, ws) > 0; }
@@ -135,34 +56,12 @@ bool fd_small_preferred(const dmx_params& prm, const WsView& ws) {
     return K <= 8 && wpb >= 2 && M * K <= 2048;
 }
 
-template <int KC>
-static int launch_small_t(const WsView& ws, const SmallArgs& a, dim3 g, dim3 b, size_t smem, float2* out, hipStream_t stream) {
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k2_fd_small<KC>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMALL_LDS_MAX);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
-    }
-    hipLaunchKernelGGL((k2_fd_small<KC>), g, b, smem, stream, ws, a, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("k2_fd_small launch failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
-    return DMX_OK;
-}
-
 int launch_channels_fd_small(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
                              float2* out, hipStream_t stream) {
     const int wpb = small_waves_per_block(prm, ws);
     if (!wpb) { set_error("small-output kernel: tables of one user do not fit the LDS"); return DMX_ERR_SHAPE; }
-    SmallArgs a;
-    a.user_begin = user_begin; a.user_count = user_count;
-    a.m_rx = prm.ue_shape[0] * prm.ue_shape[1];
-    a.m_tx = prm.bs_shape[0] * prm.bs_shape[1];
-    a.ue_mh = prm.ue_shape[0];
-    a.bs_mh = prm.bs_shape[0];
-    a.K = prm.n_selected;
-    a.sc = prm.selected_subcarriers;
-    a.inv_n = 1.0 / (double)prm.n_subcarriers;
-    a.ld = ws.P < 32 ? ws.P : 32;
-    const size_t smem = (size_t)wpb * (a.m_rx + a.m_tx + a.K) * a.ld * 8;
+    const SmallArgs a = small_args(prm, user_begin, user_count, small_ld(ws));
+    const size_t smem = (size_t)wpb * small_table_bytes(prm, a.ld);
     // persistent: as many workgroups as the LDS lets be resident (160 KB per CU), at most 8 waves per SIMD
     int per_cu = (int)((size_t)160 * 1024 / smem);
     if (per_cu * wpb > 32) per_cu = 32 / wpb;
@@ -170,9 +69,9 @@ int launch_channels_fd_small(const dmx_params& prm, const WsView& ws, int64_t us
     int64_t grid = (user_count + wpb - 1) / wpb;
     if (grid > (int64_t)256 * per_cu) grid = (int64_t)256 * per_cu;
     const dim3 g((unsigned)grid), b(64 * wpb);
-    if (a.K >= 4) return launch_small_t<4>(ws, a, g, b, smem, out, stream);
-    if (a.K >= 2) return launch_small_t<2>(ws, a, g, b, smem, out, stream);
-    return launch_small_t<1>(ws, a, g, b, smem, out, stream);
+    if (a.K >= 4) return launch_dyn_lds(k2_fd_small<4>, "k2_fd_small", g, b, smem, stream, ws, a, out);
+    if (a.K >= 2) return launch_dyn_lds(k2_fd_small<2>, "k2_fd_small", g, b, smem, stream, ws, a, out);
+    return launch_dyn_lds(k2_fd_small<1>, "k2_fd_small", g, b, smem, stream, ws, a, out);
 }
 
 }  // namespace dmx
