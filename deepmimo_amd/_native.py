@@ -19,9 +19,11 @@ EXPORTED_SYMBOLS = ("dmx_version", "dmx_last_error", "dmx_workspace_bytes", "dmx
                     "dmx_lpf_workspace_bytes", "dmx_mat5_find", "dmx_mat_to_rowmajor_f32", "dmx_mats_to_device",
                     "dmx_beam_workspace_bytes", "dmx_channels_fd_beams", "dmx_pathloss",
                     "dmx_p2m_count_rx", "dmx_p2m_parse_paths", "dmx_fd_kernel_choice", "dmx_beam_power",
-                    "dmx_fd_direct_supported", "dmx_channels_fd_direct")
+                    "dmx_fd_direct_supported", "dmx_channels_fd_direct", "dmx_covariance_supported",
+                    "dmx_channel_covariance")
 
 PATTERN_IDS = {"isotropic": 0, "halfwave-dipole": 1}
+COV_SIDES = {"tx": 0, "rx": 1}            # DMX_COV_TX / DMX_COV_RX
 
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
@@ -99,6 +101,11 @@ def load():
     lib.dmx_channels_fd_direct.restype = C.c_int
     lib.dmx_channels_fd_direct.argtypes = [C.POINTER(DmxRays), C.POINTER(DmxParams), C.POINTER(DmxSide), C.c_int64, C.c_int64,
                                            C.c_void_p, C.c_void_p]
+    lib.dmx_covariance_supported.restype = C.c_int
+    lib.dmx_covariance_supported.argtypes = [C.POINTER(DmxParams), C.c_int32, C.c_int32]
+    lib.dmx_channel_covariance.restype = C.c_int
+    lib.dmx_channel_covariance.argtypes = [C.POINTER(DmxParams), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
+                                           C.c_int32, C.c_void_p, C.c_void_p]
     lib.dmx_decode_max_delay.restype = C.c_float
     lib.dmx_decode_max_delay.argtypes = [C.c_uint32]
     lib.dmx_path_prep.restype = C.c_int

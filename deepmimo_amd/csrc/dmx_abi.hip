@@ -252,6 +252,47 @@ int dmx_beam_power(const dmx_params* prm, const void* workspace, int64_t n_ue, i
                              out_mean_amp, out_best_beam, (hipStream_t)stream);
 }
 
+// 1: taken; 0: not taken, with the limit in the error string; negative: bad argument
+static int covariance_shape(const dmx_params* prm, int32_t n_paths_loaded, int32_t side) {
+    if (side != DMX_COV_TX && side != DMX_COV_RX) { set_error("side must be DMX_COV_TX (0) or DMX_COV_RX (1), got %d", side); return DMX_ERR_ARG; }
+    if (n_paths_loaded < 0) { set_error("n_paths_loaded must be >= 0"); return DMX_ERR_ARG; }
+    if (!prm->freq_domain || prm->rx_filter) { set_error("the covariance needs freq_domain = 1 and rx_filter = 0"); return 0; }
+    const int P = used_paths(prm, n_paths_loaded);
+    if (P < 1 || P > 32) {
+        set_error("covariance: min(num_paths, loaded paths) = %d is outside the 1..32 paths the kernel supports", P);
+        return 0;
+    }
+    if (prm->n_selected < 1) { set_error("covariance: at least one selected subcarrier is needed"); return 0; }
+    if (cov_waves_per_block(*prm, P, side, nullptr) == 0) {
+        const long long m_tx = (long long)prm->bs_shape[0] * prm->bs_shape[1], m_rx = (long long)prm->ue_shape[0] * prm->ue_shape[1];
+        set_error("covariance: one user's tables, (%lld + %lld + %lld + %d + 8) * %d * 8 = %lld bytes, exceed the %zu bytes of LDS "
+                  "a wave can get", m_tx, m_rx, side == DMX_COV_TX ? m_tx : m_rx, P, P,
+                  (m_tx + m_rx + (side == DMX_COV_TX ? m_tx : m_rx) + P + 8) * P * 8, WAVE_LDS_MAX);
+        return 0;
+    }
+    return 1;
+}
+
+int dmx_covariance_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t side) {
+    int rc = check_params(prm);
+    if (rc) return rc;
+    return covariance_shape(prm, n_paths_loaded, side);
+}
+
+int dmx_channel_covariance(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
+                           int64_t user_begin, int64_t user_count, int32_t side, void* out_c64, void* stream) {
+    WsView ws;
+    int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_c64, &ws);
+    if (rc) return rc;
+    if (!prm->freq_domain) { set_error("dmx_channel_covariance called with freq_domain = 0"); return DMX_ERR_ARG; }
+    if (prm->rx_filter) { set_error("dmx_channel_covariance does not cover rx_filter = 1"); return DMX_ERR_ARG; }
+    rc = covariance_shape(prm, n_paths_loaded, side);
+    if (rc < 0) return rc;
+    if (rc == 0) return DMX_ERR_SHAPE;
+    if (user_count == 0) return DMX_OK;
+    return launch_covariance(*prm, ws, user_begin, user_count, side, (float2*)out_c64, (hipStream_t)stream);
+}
+
 int dmx_channels_td(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                     int64_t user_begin, int64_t user_count, void* out_c64, void* stream) {
     WsView ws;

@@ -135,5 +135,8 @@ int launch_beam_power(const dmx_params& prm, const WsView& ws, int64_t user_begi
 bool fd_mfma_supported(const dmx_params& prm, const WsView& ws);
 int launch_channels_td(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
                        float2* out, hipStream_t stream);
+int cov_waves_per_block(const dmx_params& prm, int P, int side, int* kc_out);
+int launch_covariance(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, int side,
+                      float2* out, hipStream_t stream);
 
 }  // namespace dmx

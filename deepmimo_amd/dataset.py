@@ -394,6 +394,27 @@ class Dataset(DotDict):
         best[np.isnan(pwr[:, 0])] = np.nan
         return pwr, best
 
+    def compute_covariance(self, params: Optional[ChannelGenParameters] = None, side: str = "tx"):
+        """Per-user spatial covariance of the frequency-domain channel, with no channel tensor written anywhere
+        (extension):
+
+            side "tx":  R[u] = np.einsum('rik,rjk->ij', H[u], H[u].conj()) / (M_rx * K)      # over the BS array
+            side "rx":  R[u] = np.einsum('itk,jtk->ij', H[u], H[u].conj()) / (M_tx * K)      # over the UE array
+
+        Returns complex64 [n_ue, M, M]: a NumPy array by default, the HBM-resident torch tensor when
+        ``config('channel_output') == 'torch'``.  Every block is exactly Hermitian.  Frequency domain without
+        ``rx_filter``, at most 32 used paths, tables within the LDS (include/deepmimo_amd.h has the rule): anything else
+        raises ValueError before any GPU work.  Not cached."""
+        from .engine import check_covariance_call
+        if params is None:
+            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
+        self.set_channel_params(params)
+        check_covariance_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), side)
+        np.random.seed(1001)
+        eng, prep = self._run_prep(want_side="light")
+        R = eng.covariance(prep, side=side)
+        return R if config.get("channel_output", "numpy") == "torch" else R.cpu().numpy()
+
     def compute_pathloss(self, coherent: bool = True) -> np.ndarray:
         """Path loss in dB assuming 0 dBm transmitted power (dataset.py:541-566); cached as ``pathloss``."""
         eng = _engine()

@@ -9,6 +9,7 @@ include/deepmimo_amd.h and calls the C-ABI:
     dmx_path_prep   -> per-path records + side products (LoS, path counts, FoV mask, angles, powers)
     dmx_channels_fd -> complex64 [N, M_rx, M_tx, K]     (dmx_channels_fd_lpf when rx_filter = 1)
     dmx_channels_td -> complex64 [N, M_rx, M_tx, P]
+    dmx_channel_covariance -> complex64 [N, M, M]       (per-user spatial covariance, no channel tensor)
 
 It replaces the body of Dataset.compute_channels (deepmimo/generator/dataset.py:224-268).
 No CPU path exists here: without the shared library or without a GPU every entry point raises.
@@ -162,6 +163,39 @@ def check_beam_bound(sc_abs_max: int):
     if sc_abs_max >= SC_ABS_MAX_F32:
         raise ValueError(f"beam-space channels / beam power need every selected subcarrier |index| below {SC_ABS_MAX_F32} "
                          f"(DMX_SC_ABS_MAX_F32); the selection reaches {sc_abs_max}")
+
+
+def covariance_side(side) -> int:
+    """DMX_COV_TX / DMX_COV_RX for "tx" / "rx"; anything else raises ValueError."""
+    if not isinstance(side, str) or side not in nat.COV_SIDES:
+        raise ValueError(f"covariance: side must be 'tx' (over the BS array) or 'rx' (over the UE array), got {side!r}")
+    return nat.COV_SIDES[side]
+
+
+def check_covariance_call(params, n_paths_loaded: int, side) -> int:
+    """Everything `Dataset.compute_covariance` can refuse without a GPU, as ValueError: the side, time domain, rx_filter,
+    and a shape dmx_covariance_supported does not take (the message is the library's and names the limit).  `params`:
+    validated ChannelGenParameters.  Returns the side id."""
+    sid = covariance_side(side)
+    bs, ue, ofdm = params[c.PARAMSET_ANT_BS], params[c.PARAMSET_ANT_UE], params[c.PARAMSET_OFDM]
+    if not params[c.PARAMSET_FD_CH]:
+        raise ValueError("covariance: needs the frequency-domain channel (freq_domain = 1)")
+    if ofdm[c.PARAMSET_OFDM_LPF]:
+        raise ValueError("covariance: ofdm.rx_filter = 1 is not covered")
+    sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
+    p = nat.DmxParams()
+    p.bs_shape[0], p.bs_shape[1] = int(bs[c.PARAMSET_ANT_SHAPE][0]), int(bs[c.PARAMSET_ANT_SHAPE][1])
+    p.ue_shape[0], p.ue_shape[1] = int(ue[c.PARAMSET_ANT_SHAPE][0]), int(ue[c.PARAMSET_ANT_SHAPE][1])
+    p.num_paths, p.freq_domain = int(params[c.PARAMSET_NUM_PATHS]), 1
+    p.n_subcarriers, p.n_selected = int(ofdm[c.PARAMSET_OFDM_SC_NUM]), int(sel.size)
+    p.bandwidth = float(ofdm[c.PARAMSET_OFDM_BANDWIDTH])
+    host_sel = (C.c_int32 * max(1, int(sel.size)))()          # the query reads the count, never the array
+    p.selected_subcarriers = C.addressof(host_sel)
+    lib = nat.load()
+    rc = lib.dmx_covariance_supported(C.byref(p), int(n_paths_loaded), sid)
+    if rc != 1:
+        raise ValueError("covariance: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
+    return sid
 
 
 class ChannelEngine:
@@ -606,6 +640,36 @@ class ChannelEngine:
                                          C.c_void_p(best.data_ptr()) if want_best else None, self._stream_ptr())
             nat.check(rc, "dmx_beam_power")
         return amp, best
+
+    def covariance_supported(self, prep: PrepResult, side="tx") -> bool:
+        """dmx_covariance_supported for this preparation (host-only query; `covariance` raises where it says no)."""
+        rc = self.lib.dmx_covariance_supported(C.byref(prep.params_struct), prep.n_paths_loaded, covariance_side(side))
+        if rc < 0:
+            nat.check(rc, "dmx_covariance_supported")
+        return rc == 1
+
+    def covariance(self, prep: PrepResult, side="tx", user_begin: int = 0, user_count: Optional[int] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dmx_channel_covariance: per-user spatial covariance of the frequency-domain channel over the BS array
+        (side "tx": R[u, i, j] = mean over rx and subcarriers of H[u, r, i, k] conj(H[u, r, j, k])) or over the UE array
+        (side "rx": mean over tx and subcarriers), complex64 [user_count, M, M] in HBM, from the per-path records of
+        `prep` - the channel tensor is not written.  Every block is exactly Hermitian."""
+        sid = covariance_side(side)
+        p = prep.params_struct
+        if user_count is None:
+            user_count = prep.n_ue - user_begin
+        m = p.bs_shape[0] * p.bs_shape[1] if sid == 0 else p.ue_shape[0] * p.ue_shape[1]
+        shape = (user_count, m, m)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.complex64, device=self.device)
+        elif out.dtype != torch.complex64 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous complex64 tensor of shape {shape}")
+        with torch.cuda.device(self.device):
+            rc = self.lib.dmx_channel_covariance(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
+                                                 prep.n_paths_loaded, int(user_begin), int(user_count), sid,
+                                                 C.c_void_p(out.data_ptr()), self._stream_ptr())
+        nat.check(rc, "dmx_channel_covariance")
+        return out
 
     def pathloss(self, rays: DeviceRays, coherent: bool = True) -> torch.Tensor:
         """dmx_pathloss: float32 [n_ue] dB (dataset.py:541-566)."""

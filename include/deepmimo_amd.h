@@ -233,6 +233,41 @@ int dmx_beam_power(const dmx_params* prm, const void* workspace, int64_t n_ue, i
                    void* stream);
 
 /*
+ * Fused consumer: the per-user spatial covariance of the frequency-domain channel over one array,
+ * averaged over the other array and the selected subcarriers, from the workspace of dmx_path_prep - H is never written.
+ * With c_l the path coefficient, a_tx[t,l] / a_rx[r,l] the array responses and g[l,k] = exp(-j 2pi dn_l sc_k / N):
+ *   H[r,t,k]  = sum_l c_l a_rx[r,l] a_tx[t,l] g[l,k]
+ *   R_tx[i,j] = 1 / (M_rx K) sum_r sum_k H[r,i,k] conj(H[r,j,k])                      side = DMX_COV_TX
+ *             = sum_l sum_l' a_tx[i,l] Q[l,l'] conj(a_tx[j,l'])
+ *   Q[l,l']   = c_l conj(c_l') S[l,l'] D[l,l']
+ *   S[l,l']   = 1 / M_rx sum_r a_rx[r,l] conj(a_rx[r,l'])
+ *   D[l,l']   = 1 / K sum_k g[l,k] conj(g[l',k])
+ *   R_rx[i,j] = 1 / (M_tx K) sum_t sum_k H[i,t,k] conj(H[j,t,k])                      side = DMX_COV_RX (arrays exchanged)
+ * out: complex64 interleaved, C-contiguous [user_count, M, M] of users [user_begin, user_begin + user_count), M = M_tx
+ * or M_rx.  Every block equals its conjugate transpose exactly, with diagonal imaginary parts 0 and real parts >= 0; a
+ * user without kept paths gets zeros.  fp32 arithmetic in a fixed order: launches repeat bit for bit and a user sub-range
+ * equals the same rows of a whole launch.  Subcarrier phases are reduced in float64: any int32 index is valid
+ * (DMX_SC_ABS_MAX_F32 does not apply).  prm->flags changes the order of a user's records and so the summation order only;
+ * the workspace of either arithmetic mode is accepted.
+ *
+ * dmx_covariance_supported - host-only: 1 if dmx_channel_covariance takes this shape, 0 if not (dmx_last_error() then
+ * names the limit), negative on a bad argument (a `side` other than the two above is DMX_ERR_ARG).  No GPU involved.
+ * Taken: freq_domain = 1, rx_filter = 0, P = min(num_paths, n_paths_loaded) in 1..32, n_selected >= 1, and one wave's
+ * tables within the LDS: (M_out + M_avg + M_out + P + 8) * P * 8 bytes <= 156 KB (159744), M_out the array R is over and
+ * M_avg the other one (the kernel takes subcarriers in chunks of 64, 32, 16 or 8, the largest that costs no wave of the
+ * workgroup, so 8 decides).  At 25 paths: 2 M_out + M_avg <= 765, e.g. a 64 x 4 BS panel with a 2 x 2 UE on either side;
+ * a 32 x 32 BS panel is refused on both sides.
+ *
+ * dmx_channel_covariance - time domain, rx_filter = 1 or a bad side: DMX_ERR_ARG; an unsupported shape: DMX_ERR_SHAPE with
+ * the limit in the message.
+ */
+#define DMX_COV_TX 0   /* R over the BS array: [user_count, M_tx, M_tx], mean over rx and k */
+#define DMX_COV_RX 1   /* R over the UE array: [user_count, M_rx, M_rx], mean over tx and k */
+int dmx_covariance_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t side);
+int dmx_channel_covariance(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
+                           int64_t user_begin, int64_t user_count, int32_t side, void* out_c64, void* stream);
+
+/*
  * Stage 2, time domain (replaces channel.py:285-287): out[u, rx, tx, s] = a_rx a_tx sqrt(p) e^{j phase}
  * of the s-th valid path (valid paths compacted to the front, remaining slots zero),
  * complex64 [user_count, M_rx, M_tx, P], P = min(num_paths, n_paths_loaded).
