@@ -59,6 +59,60 @@ static int check_sc_bound_f32(const dmx_params* p, const char* what) {
 
 static inline int used_paths(const dmx_params* p, int32_t loaded) { return p->num_paths < loaded ? p->num_paths : loaded; }
 
+// Checks shared by the entry points.  Which of several faults is reported is part of the behaviour: each entry point keeps
+// its order of calls (tests/test_host_cpu.py pins return code and message of single and paired faults).
+static int check_rays(const dmx_rays* rays) {
+    if (!rays) { set_error("rays is NULL"); return DMX_ERR_ARG; }
+    if (rays->n_ue < 0 || rays->n_paths < 0 || rays->ld < rays->n_paths) { set_error("bad ray matrix shape"); return DMX_ERR_ARG; }
+    if (rays->n_ue > 0 && rays->n_paths > 0 &&
+        (!rays->power || !rays->phase || !rays->delay || !rays->aoa_az || !rays->aoa_el || !rays->aod_az ||
+         !rays->aod_el || !rays->inter)) {
+        set_error("a required ray field pointer is NULL"); return DMX_ERR_ARG;
+    }
+    return DMX_OK;
+}
+
+static int check_user_range(int64_t n_ue, int64_t user_begin, int64_t user_count) {
+    if (n_ue < 0 || user_begin < 0 || user_count < 0 || user_begin + user_count > n_ue) {
+        set_error("user range [%lld, %lld) outside [0, %lld)", (long long)user_begin, (long long)(user_begin + user_count), (long long)n_ue);
+        return DMX_ERR_ARG;
+    }
+    if (user_count > 0x7fffffffLL) { set_error("too many users for one call"); return DMX_ERR_SHAPE; }
+    return DMX_OK;
+}
+
+static int check_workspace_aligned(const void* workspace) {
+    if (((uintptr_t)workspace & 255u) == 0) return DMX_OK;
+    set_error("workspace must be 256-byte aligned"); return DMX_ERR_WORKSPACE;
+}
+static int check_out_aligned(const void* out) {
+    if (((uintptr_t)out & 7u) == 0) return DMX_OK;
+    set_error("out must be 8-byte aligned"); return DMX_ERR_ARG;
+}
+
+// the beam-space entry points: plain frequency domain within the float32-phase bound, a codebook of at least `min_beams`
+static int check_beam_call(const dmx_params* p, const char* entry, const void* codebook, int32_t n_beams, int32_t min_beams) {
+    if (!p->freq_domain || p->rx_filter) { set_error("%s needs freq_domain = 1 and rx_filter = 0", entry); return DMX_ERR_ARG; }
+    if (int rc = check_sc_bound_f32(p, entry)) return rc;
+    if (n_beams < min_beams || (n_beams > 0 && !codebook)) { set_error("codebook missing"); return DMX_ERR_ARG; }
+    return DMX_OK;
+}
+
+static int check_beam_workspace(int64_t user_count, int32_t n_beams, int P, const void* beam_ws, size_t beam_ws_bytes) {
+    const size_t need = beam_workspace_bytes(user_count, n_beams, P);
+    if (!beam_ws || beam_ws_bytes < need || ((uintptr_t)beam_ws & 255u)) {
+        set_error("beam workspace too small or misaligned: need %zu bytes, 256-byte aligned", need);
+        return DMX_ERR_WORKSPACE;
+    }
+    return DMX_OK;
+}
+
+static dmx_side side_or_none(const dmx_side* side) {
+    dmx_side s;
+    if (side) s = *side; else memset(&s, 0, sizeof(s));
+    return s;
+}
+
 }  // namespace dmx
 
 using namespace dmx;
@@ -85,38 +139,23 @@ float dmx_decode_max_delay(uint32_t key) {
 int dmx_path_prep(const dmx_rays* rays, const dmx_params* prm, void* workspace, size_t workspace_bytes,
                   const dmx_side* side, void* stream) {
     int rc = check_params(prm);
-    if (rc) return rc;
-    if (!rays) { set_error("rays is NULL"); return DMX_ERR_ARG; }
-    if (rays->n_ue < 0 || rays->n_paths < 0 || rays->ld < rays->n_paths) { set_error("bad ray matrix shape"); return DMX_ERR_ARG; }
-    if (rays->n_ue > 0 && rays->n_paths > 0 &&
-        (!rays->power || !rays->phase || !rays->delay || !rays->aoa_az || !rays->aoa_el || !rays->aod_az ||
-         !rays->aod_el || !rays->inter)) {
-        set_error("a required ray field pointer is NULL"); return DMX_ERR_ARG;
-    }
+    if (rc || (rc = check_rays(rays))) return rc;
     if (rays->n_ue > 0x7fffffffLL * 4) { set_error("too many users for one call"); return DMX_ERR_SHAPE; }
     const int P = used_paths(prm, rays->n_paths);
     const size_t need = ws_carve(nullptr, rays->n_ue, P, nullptr);
     if (need > 0 && (!workspace || workspace_bytes < need)) { set_error("workspace too small: need %zu bytes", need); return DMX_ERR_WORKSPACE; }
-    if (((uintptr_t)workspace & 255u) != 0) { set_error("workspace must be 256-byte aligned"); return DMX_ERR_WORKSPACE; }
+    if ((rc = check_workspace_aligned(workspace))) return rc;
     WsView ws;
     ws_carve(workspace, rays->n_ue, P, &ws);
-    dmx_side s;
-    if (side) s = *side; else memset(&s, 0, sizeof(s));
-    return launch_path_prep(*rays, *prm, ws, s, (hipStream_t)stream);
+    return launch_path_prep(*rays, *prm, ws, side_or_none(side), (hipStream_t)stream);
 }
 
 static int stage2_common(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                          int64_t user_begin, int64_t user_count, void* out, WsView* ws) {
     int rc = check_params(prm);
-    if (rc) return rc;
-    if (n_ue < 0 || user_begin < 0 || user_count < 0 || user_begin + user_count > n_ue) {
-        set_error("user range [%lld, %lld) outside [0, %lld)", (long long)user_begin, (long long)(user_begin + user_count), (long long)n_ue);
-        return DMX_ERR_ARG;
-    }
-    if (user_count > 0x7fffffffLL) { set_error("too many users for one call"); return DMX_ERR_SHAPE; }
+    if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
     if (user_count > 0 && (!workspace || !out)) { set_error("workspace/out is NULL"); return DMX_ERR_ARG; }
-    if (((uintptr_t)workspace & 255u) != 0) { set_error("workspace must be 256-byte aligned"); return DMX_ERR_WORKSPACE; }
-    if (((uintptr_t)out & 7u) != 0) { set_error("out must be 8-byte aligned"); return DMX_ERR_ARG; }
+    if ((rc = check_workspace_aligned(workspace)) || (rc = check_out_aligned(out))) return rc;
     ws_carve(const_cast<void*>(workspace), n_ue, used_paths(prm, n_paths_loaded), ws);
     return DMX_OK;
 }
@@ -153,19 +192,7 @@ int dmx_fd_direct_supported(const dmx_params* prm, int32_t n_paths_loaded) {
 int dmx_channels_fd_direct(const dmx_rays* rays, const dmx_params* prm, const dmx_side* side,
                            int64_t user_begin, int64_t user_count, void* out_c64, void* stream) {
     int rc = check_params(prm);
-    if (rc) return rc;
-    if (!rays) { set_error("rays is NULL"); return DMX_ERR_ARG; }
-    if (rays->n_ue < 0 || rays->n_paths < 0 || rays->ld < rays->n_paths) { set_error("bad ray matrix shape"); return DMX_ERR_ARG; }
-    if (rays->n_ue > 0 && rays->n_paths > 0 &&
-        (!rays->power || !rays->phase || !rays->delay || !rays->aoa_az || !rays->aoa_el || !rays->aod_az ||
-         !rays->aod_el || !rays->inter)) {
-        set_error("a required ray field pointer is NULL"); return DMX_ERR_ARG;
-    }
-    if (user_begin < 0 || user_count < 0 || user_begin + user_count > rays->n_ue) {
-        set_error("user range [%lld, %lld) outside [0, %lld)", (long long)user_begin, (long long)(user_begin + user_count), (long long)rays->n_ue);
-        return DMX_ERR_ARG;
-    }
-    if (user_count > 0x7fffffffLL) { set_error("too many users for one call"); return DMX_ERR_SHAPE; }
+    if (rc || (rc = check_rays(rays)) || (rc = check_user_range(rays->n_ue, user_begin, user_count))) return rc;
     if (side && (side->aod_el_rot || side->aod_az_rot || side->aoa_el_rot || side->aoa_az_rot || side->power_linear ||
                  side->power_linear_ant_gain)) {
         set_error("dmx_channels_fd_direct writes fov_mask, num_paths, los and max_delay_key only: rotated angles and powers come "
@@ -179,10 +206,8 @@ int dmx_channels_fd_direct(const dmx_rays* rays, const dmx_params* prm, const dm
         return DMX_ERR_SHAPE;
     }
     if (user_count > 0 && !out_c64) { set_error("out is NULL"); return DMX_ERR_ARG; }
-    if (((uintptr_t)out_c64 & 7u) != 0) { set_error("out must be 8-byte aligned"); return DMX_ERR_ARG; }
-    dmx_side s;
-    if (side) s = *side; else memset(&s, 0, sizeof(s));
-    return launch_channels_fd_direct(*rays, *prm, s, user_begin, user_count, (float2*)out_c64, (hipStream_t)stream);
+    if ((rc = check_out_aligned(out_c64))) return rc;
+    return launch_channels_fd_direct(*rays, *prm, side_or_none(side), user_begin, user_count, (float2*)out_c64, (hipStream_t)stream);
 }
 
 size_t dmx_lpf_workspace_bytes(const dmx_params* prm, int64_t user_count, int32_t n_paths_loaded) {
@@ -217,16 +242,10 @@ int dmx_channels_fd_beams(const dmx_params* prm, const void* workspace, int64_t 
     WsView ws;
     int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_c64, &ws);
     if (rc) return rc;
-    if (!prm->freq_domain || prm->rx_filter) { set_error("dmx_channels_fd_beams needs freq_domain = 1 and rx_filter = 0"); return DMX_ERR_ARG; }
-    if ((rc = check_sc_bound_f32(prm, "dmx_channels_fd_beams"))) return rc;
-    if (n_beams < 0 || (n_beams > 0 && !codebook_c64)) { set_error("codebook missing"); return DMX_ERR_ARG; }
+    if ((rc = check_beam_call(prm, "dmx_channels_fd_beams", codebook_c64, n_beams, 0))) return rc;
     if (prm->n_selected == 0 || n_beams == 0) return DMX_OK;
     if (ws.P > 32) { set_error("num_paths = %d exceeds the 32 paths the beam-space kernel supports", ws.P); return DMX_ERR_SHAPE; }
-    const size_t need = beam_workspace_bytes(user_count, n_beams, ws.P);
-    if (!beam_workspace || beam_workspace_bytes_ < need || ((uintptr_t)beam_workspace & 255u)) {
-        set_error("beam workspace too small or misaligned: need %zu bytes, 256-byte aligned", need);
-        return DMX_ERR_WORKSPACE;
-    }
+    if ((rc = check_beam_workspace(user_count, n_beams, ws.P, beam_workspace, beam_workspace_bytes_))) return rc;
     return launch_channels_fd_beams(*prm, ws, user_begin, user_count, (const float2*)codebook_c64, n_beams, beam_workspace,
                                     (float2*)out_c64, (hipStream_t)stream);
 }
@@ -238,16 +257,10 @@ int dmx_beam_power(const dmx_params* prm, const void* workspace, int64_t n_ue, i
     WsView ws;
     int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_mean_amp, &ws);
     if (rc) return rc;
-    if (!prm->freq_domain || prm->rx_filter) { set_error("dmx_beam_power needs freq_domain = 1 and rx_filter = 0"); return DMX_ERR_ARG; }
-    if ((rc = check_sc_bound_f32(prm, "dmx_beam_power"))) return rc;
-    if (n_beams < 1 || !codebook_c64) { set_error("codebook missing"); return DMX_ERR_ARG; }
+    if ((rc = check_beam_call(prm, "dmx_beam_power", codebook_c64, n_beams, 1))) return rc;
     if (prm->n_selected < 1) { set_error("dmx_beam_power needs at least one selected subcarrier"); return DMX_ERR_ARG; }
     if (ws.P > 32) { set_error("num_paths = %d exceeds the 32 paths the beam-space kernels support", ws.P); return DMX_ERR_SHAPE; }
-    const size_t need = beam_workspace_bytes(user_count, n_beams, ws.P);
-    if (!beam_workspace || beam_workspace_bytes_ < need || ((uintptr_t)beam_workspace & 255u)) {
-        set_error("beam workspace too small or misaligned: need %zu bytes, 256-byte aligned", need);
-        return DMX_ERR_WORKSPACE;
-    }
+    if ((rc = check_beam_workspace(user_count, n_beams, ws.P, beam_workspace, beam_workspace_bytes_))) return rc;
     return launch_beam_power(*prm, ws, user_begin, user_count, (const float2*)codebook_c64, n_beams, beam_workspace,
                              out_mean_amp, out_best_beam, (hipStream_t)stream);
 }

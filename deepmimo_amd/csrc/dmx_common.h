@@ -100,11 +100,31 @@ __host__ inline int lds_waves_per_block(size_t bytes_per_wave) {
     return 0;
 }
 
-// raise the kernel's dynamic-LDS attribute where the request needs it, launch, check
+// compute units of the current device (persistent grids are sized from it)
+int device_cu_count();
+
+// ---- launch layer: every kernel launch of the library goes through these two ----
+// Workgroups of `kernel` the device holds at once, CUs x workgroups per CU as registers and LDS allow (1 where the
+// runtime cannot say).  A persistent launcher turns it into its grid by its own, measured rule.
+template <class... Params>
+int64_t resident_workgroups(void (*kernel)(Params...), int threads, size_t smem) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel), threads, smem) != hipSuccess || per_cu < 1) {
+        (void)hipGetLastError();
+        per_cu = 1;
+    }
+    return (int64_t)device_cu_count() * per_cu;
+}
+
+// Launch, check, set the error string.  A request beyond the 64 KiB a workgroup gets by default first raises the
+// kernel's dynamic-LDS attribute to `lds_cap` (per device and cheap: no cached flag, so every GPU of a process gets it);
+// LDS_NO_RAISE is for kernels whose shape limits keep them within the default.
+static constexpr size_t LDS_NO_RAISE = 0;
 template <class... Params, class... Args>
-int launch_dyn_lds(void (*kernel)(Params...), const char* name, dim3 g, dim3 b, size_t smem, hipStream_t stream, const Args&... args) {
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WAVE_LDS_MAX);
+int launch_dyn_lds(void (*kernel)(Params...), const char* name, dim3 g, dim3 b, size_t smem, size_t lds_cap, hipStream_t stream,
+                   const Args&... args) {
+    if (smem > 64 * 1024 && lds_cap != LDS_NO_RAISE) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap);
         if (e != hipSuccess) { set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
     }
     hipLaunchKernelGGL(kernel, g, b, smem, stream, args...);
@@ -112,9 +132,6 @@ int launch_dyn_lds(void (*kernel)(Params...), const char* name, dim3 g, dim3 b, 
     if (e != hipSuccess) { set_error("%s launch failed: %s", name, hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
     return DMX_OK;
 }
-
-// compute units of the current device (persistent grids are sized from it)
-int device_cu_count();
 
 // stage launchers (defined next to their kernels)
 int launch_path_prep(const dmx_rays& rays, const dmx_params& prm, const WsView& ws, const dmx_side& side,
@@ -138,5 +155,30 @@ int launch_channels_td(const dmx_params& prm, const WsView& ws, int64_t user_beg
 int cov_waves_per_block(const dmx_params& prm, int P, int side, int* kc_out);
 int launch_covariance(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, int side,
                       float2* out, hipStream_t stream);
+
+// between the stage-2 files: the kernels variant 0 chooses from (k2_channel_fd.hip), their predicates and launchers
+bool fd_mfma_preferred(const dmx_params& prm, const WsView& ws);
+bool fd_small_preferred(const dmx_params& prm, const WsView& ws);
+bool fd_fold_preferred(const dmx_params& prm, const WsView& ws);
+int launch_channels_fd_mfma(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
+                            float2* out, int config, hipStream_t stream);
+int launch_channels_fd_small(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
+                             float2* out, hipStream_t stream);
+int launch_channels_fd_fold(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, float2* out,
+                            int chunk_blocks, hipStream_t stream);
+// rx_filter: the contraction over a gains table (float, or packed f16 where lpf_table_packed says the matrix-core
+// kernel is its only reader)
+bool lpf_table_packed(const dmx_params& prm, const WsView& ws);
+int launch_channels_fd_mfma_gload(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
+                                  const float2* gtab, float2* out, hipStream_t stream, bool packed);
+int launch_channels_fd_lpf_contract(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
+                                    const float2* gtab, float2* out, hipStream_t stream, bool packed);
+// k2b_beam_project's output inside the beam workspace, read by the beam-space contraction and by k2c_beam_power
+struct BeamTabs {
+    const float2* ftab;      // [user_count, n_beams, P]  f[b,l] = sum_tx F[b,tx] a_tx[tx,l]
+    const int32_t* fexp;     // [user_count]              exponent of max |f| per user
+};
+int launch_beam_project(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
+                        const float2* codebook, int n_beams, void* beam_ws, hipStream_t stream, BeamTabs* tabs);
 
 }  // namespace dmx

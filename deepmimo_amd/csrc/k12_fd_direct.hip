@@ -115,9 +115,9 @@ int fd_direct_waves_per_block(const dmx_params& prm, int32_t n_paths_loaded) {
 
 template <int MODE>
 static int launch_direct_m(const DirectArgs& a, dim3 g, dim3 b, size_t smem, float2* out, hipStream_t stream) {
-    if (a.s2.K >= 4) return launch_dyn_lds(k12_fd_direct<4, MODE>, "k12_fd_direct", g, b, smem, stream, a, out);
-    if (a.s2.K >= 2) return launch_dyn_lds(k12_fd_direct<2, MODE>, "k12_fd_direct", g, b, smem, stream, a, out);
-    return launch_dyn_lds(k12_fd_direct<1, MODE>, "k12_fd_direct", g, b, smem, stream, a, out);
+    if (a.s2.K >= 4) return launch_dyn_lds(k12_fd_direct<4, MODE>, "k12_fd_direct", g, b, smem, WAVE_LDS_MAX, stream, a, out);
+    if (a.s2.K >= 2) return launch_dyn_lds(k12_fd_direct<2, MODE>, "k12_fd_direct", g, b, smem, WAVE_LDS_MAX, stream, a, out);
+    return launch_dyn_lds(k12_fd_direct<1, MODE>, "k12_fd_direct", g, b, smem, WAVE_LDS_MAX, stream, a, out);
 }
 
 int launch_channels_fd_direct(const dmx_rays& rays, const dmx_params& prm, const dmx_side& side, int64_t user_begin,

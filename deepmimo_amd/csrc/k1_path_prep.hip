@@ -369,19 +369,13 @@ int launch_path_prep(const dmx_rays& rays, const dmx_params& prm, const WsView& 
         a.bs_spacing = s1.bs_spacing; a.ue_spacing = s1.ue_spacing;
         a.P = s1.P; a.freq_domain = prm.freq_domain; a.n_sc = s1.n_sc; a.ts32 = s1.ts32;
         a.doppler = s1.doppler; a.rx_filter = rx_filter; a.need_angles = need_angles; a.sort_paths = sort_paths; a.fc = s1.fc;
-        if (two) hipLaunchKernelGGL((k1_path_prep_full<32>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((k1_path_prep_full<64>), grid, block, 0, stream, a);
-    } else {
-        PrepArgs a;
-        a.rays = rays; a.side = side; a.ws = ws; a.s1 = s1;
-        a.freq_domain = prm.freq_domain; a.rx_filter = rx_filter; a.need_angles = need_angles; a.sort_paths = sort_paths;
-        if (!two) hipLaunchKernelGGL((k1_path_prep<64>), grid, block, 0, stream, a);
-        else if (form == STAGE1_LEAN_ZROT) hipLaunchKernelGGL((k1_path_prep<32, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((k1_path_prep<32>), grid, block, 0, stream, a);
+        return launch_dyn_lds(two ? k1_path_prep_full<32> : k1_path_prep_full<64>, "k1_path_prep", grid, block, 0, LDS_NO_RAISE, stream, a);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("k1_path_prep launch failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
-    return DMX_OK;
+    PrepArgs a;
+    a.rays = rays; a.side = side; a.ws = ws; a.s1 = s1;
+    a.freq_domain = prm.freq_domain; a.rx_filter = rx_filter; a.need_angles = need_angles; a.sort_paths = sort_paths;
+    const auto lean = !two ? k1_path_prep<64> : (form == STAGE1_LEAN_ZROT ? k1_path_prep<32, true> : k1_path_prep<32>);
+    return launch_dyn_lds(lean, "k1_path_prep", grid, block, 0, LDS_NO_RAISE, stream, a);
 }
 
 }  // namespace dmx

@@ -210,11 +210,8 @@ static int launch_valu_w(const WsView& ws, FdArgs a, int64_t user_count, float2*
     a.txt = txt;
     const size_t per_user = align_up(fixed + (size_t)txt * 2 * LP * 4, 16);
     const int64_t blocks = (user_count + UPW - 1) / UPW;
-    hipLaunchKernelGGL((k2_fd_valu<LP, RB, GLOAD, WPU>), dim3((unsigned)blocks), dim3(256), per_user * UPW, stream, ws, a, out,
-                       user_count, (int)per_user);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("k2_fd_valu launch failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
-    return DMX_OK;
+    return launch_dyn_lds(k2_fd_valu<LP, RB, GLOAD, WPU>, "k2_fd_valu", dim3((unsigned)blocks), dim3(256), per_user * UPW, LDS_NO_RAISE,
+                          stream, ws, a, out, user_count, (int)per_user);
 }
 
 template <int LP, int RB, bool GLOAD = false>
@@ -275,17 +272,6 @@ static int launch_extra_path_passes(const dmx_params& prm, const WsView& ws, int
     return DMX_OK;
 }
 
-int launch_channels_fd_mfma(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
-                            float2* out, int config, hipStream_t stream);
-bool fd_mfma_supported(const dmx_params& prm, const WsView& ws);
-bool fd_mfma_preferred(const dmx_params& prm, const WsView& ws);
-int launch_channels_fd_small(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
-                             float2* out, hipStream_t stream);
-bool fd_small_preferred(const dmx_params& prm, const WsView& ws);
-int launch_channels_fd_fold(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, float2* out,
-                            int chunk_blocks, hipStream_t stream);
-bool fd_fold_preferred(const dmx_params& prm, const WsView& ws);
-
 // what variant 0 runs for this shape: 9 small-output kernel, 12 folded matrix-core kernel (few antenna pairs, uniformly
 // spaced subcarriers), 2 matrix cores, 1 fp32 vector kernel.  Indices at or beyond DMX_SC_ABS_MAX_F32: only the
 // float64-phase kernels, 9 and 1
@@ -316,9 +302,6 @@ int launch_channels_fd(const dmx_params& prm, const WsView& ws, int64_t user_beg
         rc = launch_fd_valu_any(prm, ws, user_begin, user_count, nullptr, out, stream);
     return rc ? rc : launch_extra_path_passes(prm, ws, user_begin, user_count, nullptr, out, stream);
 }
-
-int launch_channels_fd_mfma_gload(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
-                                  const float2* gtab, float2* out, hipStream_t stream, bool packed);
 
 // the gains table may be written in the packed f16 form when the matrix-core kernel is its only reader (at most 32 path
 // slots: further slots go through the fp32 vector kernel's accumulate passes, which read floats)

@@ -688,24 +688,11 @@ int launch_channels_fd_fold(const dmx_params& prm, const WsView& ws, int64_t use
     if (smem > 160 * 1024) { set_error("folded kernel tables of %zu bytes exceed LDS", smem); return DMX_ERR_SHAPE; }
     if (smem < FOLD_MIN_LDS) smem = FOLD_MIN_LDS;                   // at most four workgroups per CU (see FOLD_MIN_LDS)
     const int64_t items = user_count * a.nsuper;
-    const void* kfn = shared ? reinterpret_cast<const void*>(k2_fd_fold<true, 4>) : reinterpret_cast<const void*>(k2_fd_fold<true, 1>);
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
-    }
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 256, smem) != hipSuccess || per_cu < 1) {
-        (void)hipGetLastError();
-        per_cu = 1;
-    }
-    int64_t grid = (int64_t)device_cu_count() * per_cu;
+    const auto kernel = shared ? k2_fd_fold<true, 4> : k2_fd_fold<true, 1>;
+    int64_t grid = resident_workgroups(kernel, 256, smem);
     const int64_t need = shared ? items : (items + 3) / 4;
     if (grid > need) grid = need;
-    if (shared) hipLaunchKernelGGL((k2_fd_fold<true, 4>), dim3((unsigned)grid), dim3(256), smem, stream, ws, a, reinterpret_cast<float*>(out), items);
-    else hipLaunchKernelGGL((k2_fd_fold<true, 1>), dim3((unsigned)grid), dim3(256), smem, stream, ws, a, reinterpret_cast<float*>(out), items);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("k2_fd_fold launch failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
-    return DMX_OK;
+    return launch_dyn_lds(kernel, "k2_fd_fold", dim3((unsigned)grid), dim3(256), smem, smem, stream, ws, a, reinterpret_cast<float*>(out), items);
 }
 
 }  // namespace dmx

@@ -851,13 +851,7 @@ bool fd_mfma_preferred(const dmx_params& prm, const WsView& ws) {
 // 12 17.1, 24 17.4 (tools/ab_bench.py, one process, interleaved).
 static constexpr int ITEMS_PER_WG = 4;
 static constexpr int ITEMS_PER_WG8 = 8;     // 8-wave workgroups: 0 (resident grid) 17.3 ms, 2 17.2, 4 16.4, 8 16.4, 16 16.5; config 5: 32.8, 32.8, 32.3, 31.2, 31.7
-static int64_t resident_grid(const void* kfn, int threads, size_t smem, int64_t blocks, int items_per_wg) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, threads, smem) != hipSuccess || per_cu < 1) {
-        (void)hipGetLastError();
-        per_cu = 1;
-    }
-    int64_t grid = (int64_t)device_cu_count() * per_cu;
+static int64_t resident_grid(int64_t grid, int64_t blocks, int items_per_wg) {     // grid: resident_workgroups of the kernel
     if (items_per_wg > 0) {
         // a few items per workgroup, but never fewer than four grids' worth of workgroups when the work allows it
         // (config 2 = 10k items: 0.43 ms with 2500 workgroups, 0.48 with 1250)
@@ -871,19 +865,12 @@ static int64_t resident_grid(const void* kfn, int threads, size_t smem, int64_t 
 template <bool NT, int NW, int MODE = 0, int GSRC = 0>
 static int launch_mfma_t(const WsView& ws, const MfmaArgs& a, int64_t blocks, size_t smem, float2* out, hipStream_t stream,
                          bool persistent = true, int items_per_wg = ITEMS_PER_WG) {
-    const void* kfn = reinterpret_cast<const void*>(k2_fd_mfma<NT, NW, MODE, GSRC>);
+    const auto kernel = k2_fd_mfma<NT, NW, MODE, GSRC>;
     static_assert(GSRC != 4 || NW <= 8, "the factorised tables of 16 waves do not fit beside 256 rows of A'");
     if constexpr (GSRC == 4) smem += fact_lds_bytes(NW);
-    if (smem > 64 * 1024) {     // per device and cheap: no cached flag, so every GPU of a process gets it
-        hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, MFMA_LDS_MAX);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
-    }
-    int64_t grid = blocks;
-    if (persistent) grid = resident_grid(kfn, NW * 64, smem, blocks, items_per_wg);
-    hipLaunchKernelGGL((k2_fd_mfma<NT, NW, MODE, GSRC>), dim3((unsigned)grid), dim3(NW * 64), smem, stream, ws, a, reinterpret_cast<float*>(out), blocks);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("k2_fd_mfma launch failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
-    return DMX_OK;
+    const int64_t grid = persistent ? resident_grid(resident_workgroups(kernel, NW * 64, smem), blocks, items_per_wg) : blocks;
+    return launch_dyn_lds(kernel, "k2_fd_mfma", dim3((unsigned)grid), dim3(NW * 64), smem, MFMA_LDS_MAX, stream, ws, a,
+                          reinterpret_cast<float*>(out), blocks);
 }
 
 static int launch_mfma_any(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
@@ -920,6 +907,8 @@ int launch_beam_project(const dmx_params& prm, const WsView& ws, int64_t user_be
     b.ftab = reinterpret_cast<float2*>(beam_ws);
     b.fexp = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(beam_ws) +
                                         align_up((size_t)user_count * (size_t)n_beams * (size_t)ws.P * 8, 256));
+    tabs->ftab = b.ftab;
+    tabs->fexp = b.fexp;
     // matrix-core projection when the codebook's f16 hi/lo image fits 64 KiB of LDS, scalar kernel otherwise
     const int kkpad = (2 * b.m_tx + 15) / 16 * 16;
     const int fstride = kkpad * 2 + 16;
@@ -928,19 +917,13 @@ int launch_beam_project(const dmx_params& prm, const WsView& ws, int64_t user_be
     if (nbt <= 4 && smem_m <= 64 * 1024) {
         int64_t grid = (user_count + 3) / 4;
         if (grid > 2048) grid = 2048;                      // persistent: the codebook is staged once per workgroup
-        if (nbt <= 1) hipLaunchKernelGGL(k2b_beam_project_mfma<1>, dim3((unsigned)grid), dim3(256), smem_m, stream, ws, b, user_count, kkpad, fstride);
-        else if (nbt <= 2) hipLaunchKernelGGL(k2b_beam_project_mfma<2>, dim3((unsigned)grid), dim3(256), smem_m, stream, ws, b, user_count, kkpad, fstride);
-        else hipLaunchKernelGGL(k2b_beam_project_mfma<4>, dim3((unsigned)grid), dim3(256), smem_m, stream, ws, b, user_count, kkpad, fstride);
-    } else {
-        const size_t smem = (size_t)b.m_tx * (ws.P > 0 ? ws.P : 1) * 8;
-        if (smem > 64 * 1024) { set_error("BS panel of %d elements x %d paths does not fit the beam-projection table", b.m_tx, ws.P); return DMX_ERR_SHAPE; }
-        hipLaunchKernelGGL(k2b_beam_project, dim3((unsigned)user_count), dim3(256), smem, stream, ws, b);
+        const auto kernel = nbt <= 1 ? k2b_beam_project_mfma<1> : (nbt <= 2 ? k2b_beam_project_mfma<2> : k2b_beam_project_mfma<4>);
+        return launch_dyn_lds(kernel, "k2b_beam_project", dim3((unsigned)grid), dim3(256), smem_m, LDS_NO_RAISE, stream, ws, b, user_count,
+                              kkpad, fstride);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("k2b_beam_project launch failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
-    tabs->ftab = b.ftab;
-    tabs->fexp = b.fexp;
-    return DMX_OK;
+    const size_t smem = (size_t)b.m_tx * (ws.P > 0 ? ws.P : 1) * 8;
+    if (smem > 64 * 1024) { set_error("BS panel of %d elements x %d paths does not fit the beam-projection table", b.m_tx, ws.P); return DMX_ERR_SHAPE; }
+    return launch_dyn_lds(k2b_beam_project, "k2b_beam_project", dim3((unsigned)user_count), dim3(256), smem, LDS_NO_RAISE, stream, ws, b);
 }
 
 int launch_channels_fd_beams(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,

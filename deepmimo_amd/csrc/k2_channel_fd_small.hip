@@ -69,9 +69,9 @@ int launch_channels_fd_small(const dmx_params& prm, const WsView& ws, int64_t us
     int64_t grid = (user_count + wpb - 1) / wpb;
     if (grid > (int64_t)256 * per_cu) grid = (int64_t)256 * per_cu;
     const dim3 g((unsigned)grid), b(64 * wpb);
-    if (a.K >= 4) return launch_dyn_lds(k2_fd_small<4>, "k2_fd_small", g, b, smem, stream, ws, a, out);
-    if (a.K >= 2) return launch_dyn_lds(k2_fd_small<2>, "k2_fd_small", g, b, smem, stream, ws, a, out);
-    return launch_dyn_lds(k2_fd_small<1>, "k2_fd_small", g, b, smem, stream, ws, a, out);
+    if (a.K >= 4) return launch_dyn_lds(k2_fd_small<4>, "k2_fd_small", g, b, smem, WAVE_LDS_MAX, stream, ws, a, out);
+    if (a.K >= 2) return launch_dyn_lds(k2_fd_small<2>, "k2_fd_small", g, b, smem, WAVE_LDS_MAX, stream, ws, a, out);
+    return launch_dyn_lds(k2_fd_small<1>, "k2_fd_small", g, b, smem, WAVE_LDS_MAX, stream, ws, a, out);
 }
 
 }  // namespace dmx

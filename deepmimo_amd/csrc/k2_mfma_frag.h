@@ -214,10 +214,4 @@ __device__ __forceinline__ void load_b_step_packed(int s, const BLane& bl, int h
     }
 }
 
-// k2b_beam_project's output inside the beam workspace
-struct BeamTabs {
-    const float2* ftab;      // [user_count, n_beams, P]  f[b,l] = sum_tx F[b,tx] a_tx[tx,l]
-    const int32_t* fexp;     // [user_count]              exponent of max |f| per user
-};
-
 }  // namespace dmx

@@ -262,9 +262,6 @@ __global__ __launch_bounds__(NW * 64, 4) void k2c_beam_power(WsView ws, BeamPowA
     }
 }
 
-int launch_beam_project(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
-                        const float2* codebook, int n_beams, void* beam_ws, hipStream_t stream, BeamTabs* tabs);
-
 int launch_beam_power(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
                       const float2* codebook, int n_beams, void* beam_ws, float* out_amp, int32_t* out_best, hipStream_t stream) {
     if (user_count == 0 || n_beams == 0) return DMX_OK;
@@ -288,24 +285,13 @@ int launch_beam_power(const dmx_params& prm, const WsView& ws, int64_t user_begi
     const int nw = tuning_int("DMX_BEAM_WAVES", 8) == 4 ? 4 : 8;    // tuning build only
     const size_t smem = beam_pow_lds_bytes(a.M, nw);
     if (smem > 160 * 1024) { set_error("%d x %d (rx, beam) rows are too many for the beam-power kernel", a.m_rx, n_beams); return DMX_ERR_SHAPE; }
-    const void* kfn = nw == 4 ? reinterpret_cast<const void*>(k2c_beam_power<4>) : reinterpret_cast<const void*>(k2c_beam_power<8>);
-    hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, nw * 64, smem) != hipSuccess || per_cu < 1) {
-        (void)hipGetLastError();
-        per_cu = 1;
-    }
-    int64_t grid = (int64_t)device_cu_count() * per_cu;
+    const auto kernel = nw == 4 ? k2c_beam_power<4> : k2c_beam_power<8>;
+    int64_t grid = resident_workgroups(kernel, nw * 64, smem);
     // a few users per workgroup let the dispatcher balance the tail (k2_channel_fd_mfma.hip: ITEMS_PER_WG)
     const int64_t g4 = user_count / 4;
     if (g4 > grid) grid = g4 < 4 * grid ? g4 : 4 * grid;
     if (grid > user_count) grid = user_count;
-    if (nw == 4) hipLaunchKernelGGL(k2c_beam_power<4>, dim3((unsigned)grid), dim3(256), smem, stream, ws, a, user_count);
-    else hipLaunchKernelGGL(k2c_beam_power<8>, dim3((unsigned)grid), dim3(512), smem, stream, ws, a, user_count);
-    e = hipGetLastError();
-    if (e != hipSuccess) { set_error("k2c_beam_power launch failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
-    return DMX_OK;
+    return launch_dyn_lds(kernel, "k2c_beam_power", dim3((unsigned)grid), dim3(nw * 64), smem, smem, stream, ws, a, user_count);
 }
 
 }  // namespace dmx

@@ -765,10 +765,6 @@ __global__ __launch_bounds__(256) void k3_lpf_fft_pow2(WsView ws, LpfArgs a, int
     }
 }
 
-int launch_channels_fd_lpf_contract(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
-                                    const float2* gtab, float2* out, hipStream_t stream, bool packed);
-bool lpf_table_packed(const dmx_params& prm, const WsView& ws);
-
 static int launch_channels_fd_lpf_once(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
                                        float2* gtab, float2* out, hipStream_t stream);
 
@@ -793,10 +789,20 @@ int launch_channels_fd_lpf(const dmx_params& prm, const WsView& ws, int64_t user
     return DMX_OK;
 }
 
+// the wave-per-user kernels (k3_lpf_fft512, k3_lpf_fft_pow2): persistent, four users per workgroup
+using WaveFftKernel = void (*)(WsView, LpfArgs, int64_t);
+static int launch_wave_fft(WaveFftKernel kernel, const char* name, size_t smem, const WsView& ws, const LpfArgs& a, int64_t user_count,
+                           hipStream_t stream) {
+    int64_t grid = resident_workgroups(kernel, 256, smem);
+    if (grid > (user_count + 3) / 4) grid = (user_count + 3) / 4;
+    return launch_dyn_lds(kernel, name, dim3((unsigned)grid), dim3(256), smem, LDS_NO_RAISE, stream, ws, a, user_count);
+}
+
 static int launch_channels_fd_lpf_once(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
                                        float2* gtab, float2* out, hipStream_t stream) {
     bool packed = false;
     if (ws.P > 0) {
+        int rc;
         LpfArgs a;
         a.user_begin = user_begin; a.N = prm.n_subcarriers; a.K = prm.n_selected; a.sc = prm.selected_subcarriers;
         a.gtab = gtab; a.doppler = prm.enable_doppler; a.fc = prm.carrier_freq; a.ts = 1.0 / prm.bandwidth;
@@ -810,65 +816,35 @@ static int launch_channels_fd_lpf_once(const dmx_params& prm, const WsView& ws, 
             // wave per user, N fixed (k3_lpf_fft512); tuning build only: DMX_LPF_GENERIC_FFT=1 takes the generic kernel below
             a.pack = packed = lpf_table_packed(prm, ws) && tuning_int("DMX_LPF_FLOAT_TABLE", 0) != 1;
             const bool ident = prm.sc_stride == 1 && (prm.sc_first & 511) == 0 && a.K <= 512;   // host promise: sc[k] = k (mod N)
-            const void* kfns[8] = {(const void*)k3_lpf_fft512<false, false, false>, (const void*)k3_lpf_fft512<false, false, true>,
-                                   (const void*)k3_lpf_fft512<false, true, false>,  (const void*)k3_lpf_fft512<false, true, true>,
-                                   (const void*)k3_lpf_fft512<true, false, false>,  (const void*)k3_lpf_fft512<true, false, true>,
-                                   (const void*)k3_lpf_fft512<true, true, false>,   (const void*)k3_lpf_fft512<true, true, true>};
-            const void* kfn = kfns[(ident ? 4 : 0) + (packed ? 2 : 0) + (a.doppler ? 1 : 0)];
-            const size_t smem = 4 * lpf_buf_elems(512) * 8;
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 256, smem) != hipSuccess || per_cu < 1) {
-                (void)hipGetLastError();
-                per_cu = 1;
-            }
-            int64_t grid = (int64_t)device_cu_count() * per_cu;
-            if (grid > (user_count + 3) / 4) grid = (user_count + 3) / 4;
-            void* kargs[] = {(void*)&ws, (void*)&a, (void*)&user_count};
-            hipError_t le = hipLaunchKernel(kfn, dim3((unsigned)grid), dim3(256), kargs, smem, stream);
-            if (le != hipSuccess) { set_error("k3_lpf_fft512 launch failed: %s", hipGetErrorString(le)); return DMX_ERR_LAUNCH; }
+            static constexpr WaveFftKernel kfns[8] = {k3_lpf_fft512<false, false, false>, k3_lpf_fft512<false, false, true>,
+                                                      k3_lpf_fft512<false, true, false>,  k3_lpf_fft512<false, true, true>,
+                                                      k3_lpf_fft512<true, false, false>,  k3_lpf_fft512<true, false, true>,
+                                                      k3_lpf_fft512<true, true, false>,   k3_lpf_fft512<true, true, true>};
+            rc = launch_wave_fft(kfns[(ident ? 4 : 0) + (packed ? 2 : 0) + (a.doppler ? 1 : 0)], "k3_lpf_fft512", 4 * lpf_buf_elems(512) * 8,
+                                 ws, a, user_count, stream);
         } else if ((a.N == 64 || a.N == 128 || a.N == 256 || a.N == 1024) && a.K <= a.N && ws.P <= 64 && !old &&
                    tuning_int("DMX_LPF_GENERIC_FFT", 0) != 1) {
             // the other default sizes, same scheme (k3_lpf_fft_pow2)
             a.pack = packed = lpf_table_packed(prm, ws) && tuning_int("DMX_LPF_FLOAT_TABLE", 0) != 1;
             const bool ident = prm.sc_stride == 1 && (prm.sc_first & (a.N - 1)) == 0;          // host promise: sc[k] = k (mod N)
             const int v = (ident ? 4 : 0) + (packed ? 2 : 0) + (a.doppler ? 1 : 0);
-#define DMX_FFT_POW2_ROW(L2) {(const void*)k3_lpf_fft_pow2<L2, false, false, false>, (const void*)k3_lpf_fft_pow2<L2, false, false, true>, \
-                              (const void*)k3_lpf_fft_pow2<L2, false, true, false>,  (const void*)k3_lpf_fft_pow2<L2, false, true, true>,  \
-                              (const void*)k3_lpf_fft_pow2<L2, true, false, false>,  (const void*)k3_lpf_fft_pow2<L2, true, false, true>,  \
-                              (const void*)k3_lpf_fft_pow2<L2, true, true, false>,   (const void*)k3_lpf_fft_pow2<L2, true, true, true>}
-            static const void* const kfns[4][8] = {DMX_FFT_POW2_ROW(6), DMX_FFT_POW2_ROW(7), DMX_FFT_POW2_ROW(8), DMX_FFT_POW2_ROW(10)};
+#define DMX_FFT_POW2_ROW(L2) {k3_lpf_fft_pow2<L2, false, false, false>, k3_lpf_fft_pow2<L2, false, false, true>, \
+                              k3_lpf_fft_pow2<L2, false, true, false>,  k3_lpf_fft_pow2<L2, false, true, true>,  \
+                              k3_lpf_fft_pow2<L2, true, false, false>,  k3_lpf_fft_pow2<L2, true, false, true>,  \
+                              k3_lpf_fft_pow2<L2, true, true, false>,   k3_lpf_fft_pow2<L2, true, true, true>}
+            static constexpr WaveFftKernel kfns[4][8] = {DMX_FFT_POW2_ROW(6), DMX_FFT_POW2_ROW(7), DMX_FFT_POW2_ROW(8), DMX_FFT_POW2_ROW(10)};
 #undef DMX_FFT_POW2_ROW
-            const void* kfn = kfns[a.N == 64 ? 0 : (a.N == 128 ? 1 : (a.N == 256 ? 2 : 3))][v];
             const int pw = a.N >= 512 ? 1 : 512 / a.N;                                          // paths per wave
-            const size_t smem = (size_t)4 * pw * lpf_buf_elems(a.N) * 8;
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 256, smem) != hipSuccess || per_cu < 1) {
-                (void)hipGetLastError();
-                per_cu = 1;
-            }
-            int64_t grid = (int64_t)device_cu_count() * per_cu;
-            if (grid > (user_count + 3) / 4) grid = (user_count + 3) / 4;
-            void* kargs[] = {(void*)&ws, (void*)&a, (void*)&user_count};
-            hipError_t le = hipLaunchKernel(kfn, dim3((unsigned)grid), dim3(256), kargs, smem, stream);
-            if (le != hipSuccess) { set_error("k3_lpf_fft_pow2 launch failed: %s", hipGetErrorString(le)); return DMX_ERR_LAUNCH; }
+            rc = launch_wave_fft(kfns[a.N == 64 ? 0 : (a.N == 128 ? 1 : (a.N == 256 ? 2 : 3))][v], "k3_lpf_fft_pow2",
+                                 (size_t)4 * pw * lpf_buf_elems(a.N) * 8, ws, a, user_count, stream);
         } else if (pow2 && a.N >= 64 && a.N <= 2048 && !old) {
             // tuning build only: DMX_LPF_FLOAT_TABLE=1 keeps the float table
             a.pack = packed = lpf_table_packed(prm, ws) && tuning_int("DMX_LPF_FLOAT_TABLE", 0) != 1;
             // wave-per-path radix-8 FFT; persistent workgroups (the twiddle table is built once per workgroup)
             const size_t smem = lpf_wave_lds_bytes(a.N);
-            const void* kfn = reinterpret_cast<const void*>(k3_lpf_fft_wave);
-            if (smem > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-                if (e != hipSuccess) { set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
-            }
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 256, smem) != hipSuccess || per_cu < 1) {
-                (void)hipGetLastError();
-                per_cu = 1;
-            }
-            int64_t grid = (int64_t)device_cu_count() * per_cu;
+            int64_t grid = resident_workgroups(k3_lpf_fft_wave, 256, smem);
             if (grid > user_count) grid = user_count;
-            hipLaunchKernelGGL(k3_lpf_fft_wave, dim3((unsigned)grid), dim3(256), smem, stream, ws, a, log2n, user_count);
+            rc = launch_dyn_lds(k3_lpf_fft_wave, "k3_lpf_fft_wave", dim3((unsigned)grid), dim3(256), smem, smem, stream, ws, a, log2n, user_count);
         } else if (pow2) {
             // paths transformed together: every stage costs one workgroup barrier whatever PB is, so batch as
             // many paths as 32 KiB of LDS hold (8 at N = 512) - 25 paths then need 4 x 9 barriers instead of 25 x 9
@@ -877,14 +853,13 @@ static int launch_channels_fd_lpf_once(const dmx_params& prm, const WsView& ws, 
             if (PB > 16) PB = 16;
             if (PB > ws.P) PB = ws.P;
             const size_t smem = (size_t)(a.N / 2) * 8 + (size_t)PB * a.N * 8 + (size_t)PB * 4;
-            hipLaunchKernelGGL(k3_lpf_fft, dim3((unsigned)user_count), dim3(256), smem, stream, ws, a, log2n, PB);
+            rc = launch_dyn_lds(k3_lpf_fft, "k3_lpf_fft", dim3((unsigned)user_count), dim3(256), smem, LDS_NO_RAISE, stream, ws, a, log2n, PB);
         } else {
             const int64_t blocks = user_count * ws.P;
             if (blocks > 0x7fffffffLL) { set_error("too many (user, path) pairs for one call"); return DMX_ERR_SHAPE; }
-            hipLaunchKernelGGL(k3_lpf_gains, dim3((unsigned)blocks), dim3(256), (size_t)a.N * 16, stream, ws, a);
+            rc = launch_dyn_lds(k3_lpf_gains, "k3_lpf_gains", dim3((unsigned)blocks), dim3(256), (size_t)a.N * 16, LDS_NO_RAISE, stream, ws, a);
         }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_error("k3 lpf gains launch failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
+        if (rc) return rc;
     }
     return launch_channels_fd_lpf_contract(prm, ws, user_begin, user_count, gtab, out, stream, packed);
 }

@@ -119,15 +119,9 @@ int launch_channels_td(const dmx_params& prm, const WsView& ws, int64_t user_beg
     a.bs_mh = prm.bs_shape[0];
     const size_t smem = (size_t)(a.m_rx + a.m_tx) * ws.P * 8;
     const bool pairs = ((size_t)a.m_rx * a.m_tx * ws.P) % 2 == 0 && ((uintptr_t)out % 16) == 0 && !tuning_set("DMX_TD_NARROW");   // tuning build only: 8-byte stores
-    if (smem <= 64 * 1024 && pairs)
-        hipLaunchKernelGGL(k4_td_tab<true>, dim3((unsigned)user_count), dim3(256), smem, stream, ws, a, out);
-    else if (smem <= 64 * 1024)
-        hipLaunchKernelGGL(k4_td_tab<false>, dim3((unsigned)user_count), dim3(256), smem, stream, ws, a, out);
-    else
-        hipLaunchKernelGGL(k4_td, dim3((unsigned)user_count), dim3(256), 0, stream, ws, a, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("k4_td launch failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
-    return DMX_OK;
+    const bool tab = smem <= 64 * 1024;                                  // the steering tables fit the LDS
+    return launch_dyn_lds(!tab ? k4_td : (pairs ? k4_td_tab<true> : k4_td_tab<false>), "k4_td", dim3((unsigned)user_count), dim3(256),
+                          tab ? smem : 0, LDS_NO_RAISE, stream, ws, a, out);
 }
 
 }  // namespace dmx

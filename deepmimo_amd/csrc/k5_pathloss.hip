@@ -42,8 +42,6 @@ extern "C" int dmx_pathloss(const dmx_rays* rays, int32_t coherent, float* out, 
     if (!out || (rays->n_paths > 0 && (!rays->power || !rays->phase))) { set_error("power/phase/out is NULL"); return DMX_ERR_ARG; }
     const int64_t blocks = (rays->n_ue + 7) / 8;
     if (blocks > 0x7fffffffLL) { set_error("too many users for one call"); return DMX_ERR_SHAPE; }
-    hipLaunchKernelGGL(k5_pathloss, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *rays, (int)coherent, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("k5_pathloss launch failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
-    return DMX_OK;
+    return launch_dyn_lds(k5_pathloss, "k5_pathloss", dim3((unsigned)blocks), dim3(256), 0, LDS_NO_RAISE, (hipStream_t)stream, *rays,
+                          (int)coherent, out);
 }

@@ -192,8 +192,8 @@ int launch_covariance(const dmx_params& prm, const WsView& ws, int64_t user_begi
     a.ld = ws.P;
     const size_t smem = (size_t)wpb * (size_t)(2 * a.m_out + a.m_avg + a.ld + a.kc) * a.ld * sizeof(float2);
     const dim3 g((unsigned)((user_count + wpb - 1) / wpb)), b(64 * wpb);    // flat: one wave per user
-    if (tx) return launch_dyn_lds(k6_covariance<DMX_COV_TX>, "k6_covariance", g, b, smem, stream, ws, a, out);
-    return launch_dyn_lds(k6_covariance<DMX_COV_RX>, "k6_covariance", g, b, smem, stream, ws, a, out);
+    if (tx) return launch_dyn_lds(k6_covariance<DMX_COV_TX>, "k6_covariance", g, b, smem, WAVE_LDS_MAX, stream, ws, a, out);
+    return launch_dyn_lds(k6_covariance<DMX_COV_RX>, "k6_covariance", g, b, smem, WAVE_LDS_MAX, stream, ws, a, out);
 }
 
 }  // namespace dmx

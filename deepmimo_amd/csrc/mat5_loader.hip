@@ -93,11 +93,8 @@ int dmx_mat_to_rowmajor_f32(const void* d_payload, int32_t data_type, int64_t ro
     if (!d_payload || !d_out) { set_error("payload/out is NULL"); return DMX_ERR_ARG; }
     const int64_t gx = (n_sel + 31) / 32;
     if (gx > 0x7fffffffLL) { set_error("too many rows for one call"); return DMX_ERR_SHAPE; }
-    hipLaunchKernelGGL(k_mat_to_rowmajor, dim3((unsigned)gx, (unsigned)((cols_keep + 31) / 32)), dim3(256), 0,
-                       (hipStream_t)stream, d_payload, (int)data_type, rows, cols, d_row_idx, n_sel, (int)cols_keep, d_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("k_mat_to_rowmajor launch failed: %s", hipGetErrorString(e)); return DMX_ERR_LAUNCH; }
-    return DMX_OK;
+    return launch_dyn_lds(k_mat_to_rowmajor, "k_mat_to_rowmajor", dim3((unsigned)gx, (unsigned)((cols_keep + 31) / 32)), dim3(256), 0,
+                          LDS_NO_RAISE, (hipStream_t)stream, d_payload, (int)data_type, rows, cols, d_row_idx, n_sel, (int)cols_keep, d_out);
 }
 
 // include/deepmimo_amd.h: dmx_mats_to_device.  Tasks are (job, slice) in job-major order behind one atomic counter, so

@@ -172,23 +172,31 @@ def covariance_side(side) -> int:
     return nat.COV_SIDES[side]
 
 
+def _fill_shape_fields(p: nat.DmxParams, params, n_selected: int):
+    """The fields of dmx_params that say how large a call is: all the host-only dmx_*_supported queries read."""
+    bs, ue, ofdm = params[c.PARAMSET_ANT_BS], params[c.PARAMSET_ANT_UE], params[c.PARAMSET_OFDM]
+    p.bs_shape[0], p.bs_shape[1] = int(bs[c.PARAMSET_ANT_SHAPE][0]), int(bs[c.PARAMSET_ANT_SHAPE][1])
+    p.ue_shape[0], p.ue_shape[1] = int(ue[c.PARAMSET_ANT_SHAPE][0]), int(ue[c.PARAMSET_ANT_SHAPE][1])
+    p.num_paths = int(params[c.PARAMSET_NUM_PATHS])
+    p.freq_domain = int(bool(params[c.PARAMSET_FD_CH]))
+    p.n_subcarriers = int(ofdm[c.PARAMSET_OFDM_SC_NUM])
+    p.n_selected = int(n_selected)
+    p.bandwidth = float(ofdm[c.PARAMSET_OFDM_BANDWIDTH])
+
+
 def check_covariance_call(params, n_paths_loaded: int, side) -> int:
     """Everything `Dataset.compute_covariance` can refuse without a GPU, as ValueError: the side, time domain, rx_filter,
     and a shape dmx_covariance_supported does not take (the message is the library's and names the limit).  `params`:
     validated ChannelGenParameters.  Returns the side id."""
     sid = covariance_side(side)
-    bs, ue, ofdm = params[c.PARAMSET_ANT_BS], params[c.PARAMSET_ANT_UE], params[c.PARAMSET_OFDM]
+    ofdm = params[c.PARAMSET_OFDM]
     if not params[c.PARAMSET_FD_CH]:
         raise ValueError("covariance: needs the frequency-domain channel (freq_domain = 1)")
     if ofdm[c.PARAMSET_OFDM_LPF]:
         raise ValueError("covariance: ofdm.rx_filter = 1 is not covered")
     sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
     p = nat.DmxParams()
-    p.bs_shape[0], p.bs_shape[1] = int(bs[c.PARAMSET_ANT_SHAPE][0]), int(bs[c.PARAMSET_ANT_SHAPE][1])
-    p.ue_shape[0], p.ue_shape[1] = int(ue[c.PARAMSET_ANT_SHAPE][0]), int(ue[c.PARAMSET_ANT_SHAPE][1])
-    p.num_paths, p.freq_domain = int(params[c.PARAMSET_NUM_PATHS]), 1
-    p.n_subcarriers, p.n_selected = int(ofdm[c.PARAMSET_OFDM_SC_NUM]), int(sel.size)
-    p.bandwidth = float(ofdm[c.PARAMSET_OFDM_BANDWIDTH])
+    _fill_shape_fields(p, params, sel.size)
     host_sel = (C.c_int32 * max(1, int(sel.size)))()          # the query reads the count, never the array
     p.selected_subcarriers = C.addressof(host_sel)
     lib = nat.load()
@@ -236,8 +244,7 @@ class ChannelEngine:
                        sc_hint=(0, 0)) -> nat.DmxParams:
         bs, ue, ofdm = params[c.PARAMSET_ANT_BS], params[c.PARAMSET_ANT_UE], params[c.PARAMSET_OFDM]
         p = nat.DmxParams()
-        p.bs_shape[0], p.bs_shape[1] = int(bs[c.PARAMSET_ANT_SHAPE][0]), int(bs[c.PARAMSET_ANT_SHAPE][1])
-        p.ue_shape[0], p.ue_shape[1] = int(ue[c.PARAMSET_ANT_SHAPE][0]), int(ue[c.PARAMSET_ANT_SHAPE][1])
+        _fill_shape_fields(p, params, 0 if sel_dev is None else sel_dev.numel())
         p.bs_spacing, p.ue_spacing = float(bs[c.PARAMSET_ANT_SPACING]), float(ue[c.PARAMSET_ANT_SPACING])
         bs_rot = np.deg2rad(np.asarray(bs[c.PARAMSET_ANT_ROTATION]))          # geometry.py:286
         for i in range(3):
@@ -267,12 +274,7 @@ class ChannelEngine:
             p.bs_fov_restricted, p.ue_fov_restricted = int(not bs_full), int(not ue_full)
             b, u = np.deg2rad(np.asarray(bs_fov)), np.deg2rad(np.asarray(ue_fov))   # geometry.py:184
             p.bs_fov[0], p.bs_fov[1], p.ue_fov[0], p.ue_fov[1] = float(b[0]), float(b[1]), float(u[0]), float(u[1])
-        p.num_paths = int(params[c.PARAMSET_NUM_PATHS])
-        p.freq_domain = int(bool(params[c.PARAMSET_FD_CH]))
-        p.n_subcarriers = int(ofdm[c.PARAMSET_OFDM_SC_NUM])
-        p.n_selected = 0 if sel_dev is None else int(sel_dev.numel())
         p.selected_subcarriers = None if sel_dev is None or sel_dev.numel() == 0 else sel_dev.data_ptr()
-        p.bandwidth = float(ofdm[c.PARAMSET_OFDM_BANDWIDTH])
         p.rx_filter = int(bool(ofdm[c.PARAMSET_OFDM_LPF]))
         p.enable_doppler = int(bool(params[c.PARAMSET_DOPPLER_EN]) and have_doppler)
         p.carrier_freq = float(carrier_freq)
@@ -281,6 +283,52 @@ class ChannelEngine:
 
     def _stream_ptr(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _scratch(self, nbytes: int) -> torch.Tensor:
+        """uint8 view of at least `nbytes` bytes (never empty) whose data_ptr() is 256-byte aligned, as every workspace of
+        the C-ABI has to be.  It may go out of scope right after the call it serves: the launch is on torch's current
+        stream and the caching allocator reuses freed blocks in stream order, so the kernels still own it when they run."""
+        n = max(int(nbytes), 256)
+        buf = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+        off = (-buf.data_ptr()) % 256
+        return buf[off:off + n]
+
+    def _out(self, out: Optional[torch.Tensor], shape) -> torch.Tensor:
+        """`out` when it is the contiguous complex64 tensor of `shape` a kernel writes, a new one when it is None."""
+        if out is None:
+            return torch.empty(shape, dtype=torch.complex64, device=self.device)
+        if out.dtype != torch.complex64 or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous complex64 tensor of shape {shape}")
+        return out
+
+    def _codebook(self, tx_codebook, m_tx: int, min_beams: int = 0) -> torch.Tensor:
+        """[n_beams, M_tx] beamforming matrix as a contiguous complex64 device tensor."""
+        cb = tx_codebook if isinstance(tx_codebook, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tx_codebook))
+        cb = cb.to(device=self.device, dtype=torch.complex64).contiguous()
+        if cb.dim() != 2 or cb.shape[1] != m_tx or cb.shape[0] < min_beams:
+            raise ValueError(f"tx_codebook must be [n_beams, {m_tx}], got {tuple(cb.shape)}")
+        return cb
+
+    def _side_tensors(self, n: int, L: int, fov_enabled, want_side):
+        """Side-product tensors and the dmx_side that points at them.  "light": what is cheap beside the channel
+        generation - LoS, path counts, the FoV mask when a FoV is set (stage 1 then needs the angles as numbers anyway).
+        True (stage 1 only): also the four rotated-angle matrices and the powers (float64 arccos / atan2 per path: ~1 ms
+        per 100k users x 25 paths, 120 MB of stores).  The delay maximum always."""
+        dev, side = self.device, {}
+        if want_side:
+            side["fov_mask"] = torch.empty((n, L), dtype=torch.uint8, device=dev) if fov_enabled else None
+            side["num_paths"] = torch.empty((n,), dtype=torch.int32, device=dev)
+            side["los"] = torch.empty((n,), dtype=torch.int32, device=dev)
+        if want_side is True:
+            for k in ("aod_el_rot", "aod_az_rot", "aoa_el_rot", "aoa_az_rot", "power_linear_ant_gain"):
+                side[k] = torch.empty((n, L), dtype=torch.float64, device=dev)
+            side["power_linear"] = torch.empty((n, L), dtype=torch.float32, device=dev)
+        side["max_delay_key"] = torch.zeros((1,), dtype=torch.int32, device=dev)
+        s = nat.DmxSide()
+        for k, t in side.items():
+            if t is not None and t.numel() > 0:
+                setattr(s, k, t.data_ptr())
+        return side, s
 
     def _call_structs(self, rays: DeviceRays, params, bs_fov=None, ue_fov=None, ue_rotation_per_user=None,
                       carrier_freq: float = 0.0, adaptive_terms: bool = False):
@@ -323,35 +371,15 @@ class ChannelEngine:
         DMX_FLAG_ADAPTIVE_TERMS (include/deepmimo_amd.h: weak last path groups in one product term); the flag travels in
         the parameter block of the preparation, so every stage-2 call on it runs in the same mode.  structs: what
         `_call_structs` returned for the same arguments, when the caller has built them already."""
-        dev = self.device
         n, L = rays.n_ue, rays.n_paths
         p, r, keep, sc_abs_max = structs or self._call_structs(rays, params, bs_fov, ue_fov, ue_rotation_per_user,
                                                                carrier_freq, adaptive_terms)
         keep = list(keep)
 
         nbytes = int(self.lib.dmx_workspace_bytes(C.byref(p), n, L))
-        ws = torch.empty(max(nbytes, 256) + 256, dtype=torch.uint8, device=dev)
-        off = (-ws.data_ptr()) % 256
-        ws = ws[off:off + max(nbytes, 256)]
-
-        side = {}
-        s = nat.DmxSide()
-        if want_side:
-            # "light": what is cheap beside the channel generation - LoS, path counts, the FoV mask when a FoV is set
-            # (stage 1 then needs the angles as numbers anyway).  True: also the four rotated-angle matrices and the
-            # powers (float64 arccos / atan2 per path: ~1 ms per 100k users x 25 paths, 120 MB of stores).
-            side["fov_mask"] = torch.empty((n, L), dtype=torch.uint8, device=dev) if p.fov_enabled else None
-            side["num_paths"] = torch.empty((n,), dtype=torch.int32, device=dev)
-            side["los"] = torch.empty((n,), dtype=torch.int32, device=dev)
-        if want_side is True:
-            for k in ("aod_el_rot", "aod_az_rot", "aoa_el_rot", "aoa_az_rot", "power_linear_ant_gain"):
-                side[k] = torch.empty((n, L), dtype=torch.float64, device=dev)
-            side["power_linear"] = torch.empty((n, L), dtype=torch.float32, device=dev)
-        side["max_delay_key"] = torch.zeros((1,), dtype=torch.int32, device=dev)
-        for k, t in side.items():
-            if t is not None and t.numel() > 0:
-                setattr(s, k, t.data_ptr())
-        with torch.cuda.device(dev):
+        ws = self._scratch(nbytes)
+        side, s = self._side_tensors(n, L, p.fov_enabled, want_side)
+        with torch.cuda.device(self.device):
             rc = self.lib.dmx_path_prep(C.byref(r), C.byref(p), C.c_void_p(ws.data_ptr()), nbytes, C.byref(s),
                                         self._stream_ptr())
         nat.check(rc, "dmx_path_prep")
@@ -364,10 +392,13 @@ class ChannelEngine:
         library cannot see the indices, so variant 0 is resolved here."""
         if prep.sc_abs_max < SC_ABS_MAX_F32:
             return variant
-        p = nat.DmxParams.from_buffer_copy(prep.params_struct)
-        p.sc_first, p.sc_stride = 0, 0                 # the shape's choice without the index range: 9 or not
-        small = self.lib.dmx_fd_kernel_choice(C.byref(p), prep.n_paths_loaded) == 9
-        return bounded_fd_variant(int(variant), prep.sc_abs_max, small)
+        return bounded_fd_variant(int(variant), prep.sc_abs_max, self._small_preferred(prep.params_struct, prep.n_paths_loaded))
+
+    def _small_preferred(self, p: nat.DmxParams, n_paths_loaded: int) -> bool:
+        """Whether variant 0 runs the small-output kernel (9) for the shape alone, the index range left out."""
+        q = nat.DmxParams.from_buffer_copy(p)
+        q.sc_first, q.sc_stride = 0, 0
+        return self.lib.dmx_fd_kernel_choice(C.byref(q), n_paths_loaded) == 9
 
     def relaunch(self, prep: PrepResult, out: torch.Tensor, variant: int = 0) -> torch.Tensor:
         """Re-issue stage 1 + stage 2 of an existing preparation on the current stream, reading whatever the
@@ -377,9 +408,7 @@ class ChannelEngine:
         p = prep.params_struct
         if p.freq_domain and p.rx_filter:
             raise ValueError("relaunch does not cover rx_filter = 1 (it needs a gains table per call)")
-        shape = self.channel_shape(prep)
-        if out.dtype != torch.complex64 or tuple(out.shape) != shape or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous complex64 tensor of shape {shape}")
+        out = self._out(out, self.channel_shape(prep))
         if p.freq_domain:
             variant = self.fd_variant(prep, variant)
         wsp = C.c_void_p(prep.workspace.data_ptr())
@@ -419,19 +448,12 @@ class ChannelEngine:
         shape = self.channel_shape(prep, user_count)
         cb = None
         if tx_codebook is not None:
-            cb = tx_codebook if isinstance(tx_codebook, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tx_codebook))
-            cb = cb.to(device=self.device, dtype=torch.complex64).contiguous()
-            if cb.dim() != 2 or cb.shape[1] != shape[2]:
-                raise ValueError(f"tx_codebook must be [n_beams, {shape[2]}], got {tuple(cb.shape)}")
+            cb = self._codebook(tx_codebook, shape[2])
             if not p.freq_domain or p.rx_filter:
                 raise ValueError("tx_codebook needs freq_domain = 1 and rx_filter = 0")
             check_beam_bound(prep.sc_abs_max)
             shape = (shape[0], shape[1], int(cb.shape[0]), shape[3])
-        if out is None:
-            out = torch.empty(shape, dtype=torch.complex64, device=self.device)
-        else:
-            if out.dtype != torch.complex64 or tuple(out.shape) != shape or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous complex64 tensor of shape {shape}")
+        out = self._out(out, shape)
         if out.numel() == 0:
             return out
         wsp = C.c_void_p(prep.workspace.data_ptr())
@@ -439,21 +461,16 @@ class ChannelEngine:
             if cb is not None:
                 nb = int(cb.shape[0])
                 nbytes = int(self.lib.dmx_beam_workspace_bytes(C.byref(p), user_count, prep.n_paths_loaded, nb))
-                bws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-                off = (-bws.data_ptr()) % 256
+                bws = self._scratch(nbytes)
                 rc = self.lib.dmx_channels_fd_beams(C.byref(p), wsp, prep.n_ue, prep.n_paths_loaded, user_begin,
-                                                    user_count, C.c_void_p(cb.data_ptr()), nb,
-                                                    C.c_void_p(bws.data_ptr() + off), nbytes,
+                                                    user_count, C.c_void_p(cb.data_ptr()), nb, C.c_void_p(bws.data_ptr()), nbytes,
                                                     C.c_void_p(out.data_ptr()), self._stream_ptr())
                 nat.check(rc, "dmx_channels_fd_beams")
-                # bws / cb may go out of scope now: the launch is on torch's current stream and the caching
-                # allocator reuses freed blocks in stream order, so the kernels still own them when they run
             elif p.freq_domain and p.rx_filter:
                 nbytes = int(self.lib.dmx_lpf_workspace_bytes(C.byref(p), user_count, prep.n_paths_loaded))
-                lws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-                off = (-lws.data_ptr()) % 256
+                lws = self._scratch(nbytes)
                 rc = self.lib.dmx_channels_fd_lpf(C.byref(p), wsp, prep.n_ue, prep.n_paths_loaded, user_begin,
-                                                  user_count, C.c_void_p(lws.data_ptr() + off), nbytes,
+                                                  user_count, C.c_void_p(lws.data_ptr()), nbytes,
                                                   C.c_void_p(out.data_ptr()), self._stream_ptr())
                 nat.check(rc, "dmx_channels_fd_lpf")
             elif p.freq_domain:
@@ -482,9 +499,7 @@ class ChannelEngine:
         selections beyond the float32-phase bound that carry no spacing promise)."""
         if sc_abs_max < SC_ABS_MAX_F32:
             return int(self.lib.dmx_fd_kernel_choice(C.byref(p), n_paths_loaded))
-        q = nat.DmxParams.from_buffer_copy(p)
-        q.sc_first, q.sc_stride = 0, 0
-        return 9 if self.lib.dmx_fd_kernel_choice(C.byref(q), n_paths_loaded) == 9 else 1
+        return bounded_fd_variant(0, sc_abs_max, self._small_preferred(p, n_paths_loaded))
 
     def host_copy_chunks(self, n_users: int, per_user_elems: int) -> bool:
         """True when `channels_to_host` would move a tensor of this size in more than one chunk."""
@@ -502,27 +517,13 @@ class ChannelEngine:
         the rows of the users it ran).  structs: as for `direct_supported`.  Raises where the shape is not taken."""
         if want_side not in ("light", False):
             raise ValueError('channels_direct: want_side must be "light" or False (the heavy side products are stage 1\'s)')
-        dev = self.device
         n, L = rays.n_ue, rays.n_paths
         p, r, keep, _ = structs or self._call_structs(rays, params, **prepare_kwargs)
         if user_count is None:
             user_count = n - user_begin
-        shape = (user_count, p.ue_shape[0] * p.ue_shape[1], p.bs_shape[0] * p.bs_shape[1], p.n_selected)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.complex64, device=dev)
-        elif out.dtype != torch.complex64 or tuple(out.shape) != shape or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous complex64 tensor of shape {shape}")
-        side = {}
-        if want_side:
-            side["fov_mask"] = torch.empty((n, L), dtype=torch.uint8, device=dev) if p.fov_enabled else None
-            side["num_paths"] = torch.empty((n,), dtype=torch.int32, device=dev)
-            side["los"] = torch.empty((n,), dtype=torch.int32, device=dev)
-        side["max_delay_key"] = torch.zeros((1,), dtype=torch.int32, device=dev)
-        s = nat.DmxSide()
-        for k, t in side.items():
-            if t is not None and t.numel() > 0:
-                setattr(s, k, t.data_ptr())
-        with torch.cuda.device(dev):
+        out = self._out(out, (user_count, p.ue_shape[0] * p.ue_shape[1], p.bs_shape[0] * p.bs_shape[1], p.n_selected))
+        side, s = self._side_tensors(n, L, p.fov_enabled, want_side)
+        with torch.cuda.device(self.device):
             rc = self.lib.dmx_channels_fd_direct(C.byref(r), C.byref(p), C.byref(s), int(user_begin), int(user_count),
                                                  C.c_void_p(out.data_ptr()), self._stream_ptr())
         nat.check(rc, "dmx_channels_fd_direct")
@@ -550,8 +551,8 @@ class ChannelEngine:
         n, per_user = shape[0], int(np.prod(shape[1:]))
         if n == 0 or per_user == 0:
             return np.empty(shape, dtype=np.complex64)
-        if tx_codebook is not None and not isinstance(tx_codebook, torch.Tensor):
-            tx_codebook = torch.from_numpy(np.ascontiguousarray(tx_codebook)).to(device=self.device, dtype=torch.complex64)
+        if tx_codebook is not None:
+            tx_codebook = self._codebook(tx_codebook, self.channel_shape(prep, 0)[2])
         chunk_bytes = int(chunk_bytes or self.HOST_CHUNK_BYTES)
         cu = max(1, chunk_bytes // (per_user * 8))
         if cu >= n:                                               # one chunk: nothing to overlap
@@ -618,10 +619,7 @@ class ChannelEngine:
         if user_count is None:
             user_count = prep.n_ue - user_begin
         m_tx = p.bs_shape[0] * p.bs_shape[1]
-        cb = tx_codebook if isinstance(tx_codebook, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tx_codebook))
-        cb = cb.to(device=self.device, dtype=torch.complex64).contiguous()
-        if cb.dim() != 2 or cb.shape[1] != m_tx or cb.shape[0] < 1:
-            raise ValueError(f"tx_codebook must be [n_beams, {m_tx}], got {tuple(cb.shape)}")
+        cb = self._codebook(tx_codebook, m_tx, min_beams=1)
         if not p.freq_domain or p.rx_filter:
             raise ValueError("beam_power needs freq_domain = 1 and rx_filter = 0")
         check_beam_bound(prep.sc_abs_max)
@@ -632,11 +630,10 @@ class ChannelEngine:
             return amp, best
         with torch.cuda.device(self.device):
             nbytes = int(self.lib.dmx_beam_workspace_bytes(C.byref(p), user_count, prep.n_paths_loaded, nb))
-            bws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-            off = (-bws.data_ptr()) % 256
+            bws = self._scratch(nbytes)
             rc = self.lib.dmx_beam_power(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue, prep.n_paths_loaded,
                                          user_begin, user_count, C.c_void_p(cb.data_ptr()), nb,
-                                         C.c_void_p(bws.data_ptr() + off), nbytes, C.c_void_p(amp.data_ptr()),
+                                         C.c_void_p(bws.data_ptr()), nbytes, C.c_void_p(amp.data_ptr()),
                                          C.c_void_p(best.data_ptr()) if want_best else None, self._stream_ptr())
             nat.check(rc, "dmx_beam_power")
         return amp, best
@@ -659,11 +656,7 @@ class ChannelEngine:
         if user_count is None:
             user_count = prep.n_ue - user_begin
         m = p.bs_shape[0] * p.bs_shape[1] if sid == 0 else p.ue_shape[0] * p.ue_shape[1]
-        shape = (user_count, m, m)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.complex64, device=self.device)
-        elif out.dtype != torch.complex64 or tuple(out.shape) != shape or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous complex64 tensor of shape {shape}")
+        out = self._out(out, (user_count, m, m))
         with torch.cuda.device(self.device):
             rc = self.lib.dmx_channel_covariance(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
                                                  prep.n_paths_loaded, int(user_begin), int(user_count), sid,

@@ -101,7 +101,7 @@ def m_pairs(route):
 def items_per_user(route, launch):
     """work items per user of one launch"""
     if launch.kind == "mfma":
-        return _cdiv(m_pairs(route), MAX_ROWS)                                         # k2_channel_fd_mfma.hip:979
+        return _cdiv(m_pairs(route), MAX_ROWS)                                         # k2_channel_fd_mfma.hip:963
     if launch.kind == "fold":
         nblk = _cdiv(len(selection(route)), 16)                                         # k2_channel_fd_fold.hip:673-679
         return max(1, _cdiv(nblk, 64))                                                  # FOLD_SUPER: sch = 64 or >= nblk
@@ -112,7 +112,7 @@ def grid_upper_bound(route, launch, items, cu):
     """Largest grid (workgroups) the launcher of `launch` can choose for `items` work items on `cu` CUs."""
     k = launch.kind
     if k == "mfma":
-        # k2_channel_fd_mfma.hip:853-867 (resident_grid) and :880-881
+        # k2_channel_fd_mfma.hip:854-863 (resident_grid) and :871
         if not launch.persistent:
             return items
         grid = cu * _per_cu(launch.nw, launch.lds)
@@ -123,23 +123,23 @@ def grid_upper_bound(route, launch, items, cu):
             grid = max(grid, g)
         return min(items, grid)
     if k == "beam_project":
-        return min(_cdiv(items, 4), 2048)                                               # k2_channel_fd_mfma.hip:928-929
+        return min(_cdiv(items, 4), 2048)                                               # k2_channel_fd_mfma.hip:918-919
     if k == "beam_power":
-        grid = cu * _per_cu(launch.nw, launch.lds)                                      # k2c_beam_power.hip:294-302
+        grid = cu * _per_cu(launch.nw, launch.lds)                                      # k2c_beam_power.hip:289-293
         g4 = items // 4
         if g4 > grid:
             grid = min(g4, 4 * grid)
         return min(items, grid)
-    if k == "fft_wave_per_user":                                                        # k3_lpf_gains.hip:819-825, 844-850
+    if k == "fft_wave_per_user":                                                        # k3_lpf_gains.hip:794-797 (launch_wave_fft)
         return min(cu * _per_cu(4, launch.lds), _cdiv(items, 4))
     if k == "fft_wave":
-        return min(cu * _per_cu(4, launch.lds), items)                                  # k3_lpf_gains.hip:864-870
+        return min(cu * _per_cu(4, launch.lds), items)                                  # k3_lpf_gains.hip:845-846
     if k == "fold":
-        # k2_channel_fd_fold.hip:689 (smem >= FOLD_MIN_LDS = 160 KiB / 5 + 64: at most four per CU) and :696-703
+        # k2_channel_fd_fold.hip:689 (smem >= FOLD_MIN_LDS = 160 KiB / 5 + 64: at most four per CU) and :692-694
         grid = cu * _per_cu(4, LDS_PER_CU // 5 + 64)
         return min(grid, items if launch.shared else _cdiv(items, 4))
     if k == "small":
-        # k2_channel_fd_small.hip:166-171: the CU count is a constant 256 there
+        # k2_channel_fd_small.hip:65-70: the CU count is a constant 256 there
         per_cu = max(1, min(LDS_PER_CU // launch.lds, WAVES_PER_CU // launch.wpb))
         return min(_cdiv(items, launch.wpb), 256 * per_cu)
     raise ValueError(k)
@@ -169,8 +169,8 @@ def _mfma(nw, mode, gsrc, rows, ipw, persistent=True):
                   persistent=persistent, gsrc=gsrc, mode=mode)
 
 
-_FFT512 = Launch("k3_lpf_fft512", "fft_wave_per_user", lds=4 * (512 + 512 // 16 + 1) * 8)          # k3_lpf_gains.hip:817
-_FFT128 = Launch("k3_lpf_fft_pow2", "fft_wave_per_user", lds=4 * 4 * (128 + 128 // 16 + 1) * 8)    # :841-842
+_FFT512 = Launch("k3_lpf_fft512", "fft_wave_per_user", lds=4 * (512 + 512 // 16 + 1) * 8)          # k3_lpf_gains.hip:823
+_FFT128 = Launch("k3_lpf_fft_pow2", "fft_wave_per_user", lds=4 * 4 * (128 + 128 // 16 + 1) * 8)    # :837-839
 _FFTW512 = Launch("k3_lpf_fft_wave", "fft_wave", lds=512 * 8 + 4 * 2 * (512 + 512 // 16 + 1) * 8)  # :263
 
 ROUTES = (
@@ -190,7 +190,7 @@ ROUTES = (
           (_mfma(8, 0, 0, 64, 8),), variant=2, auto=2),
     Route("g", "mfma GSRC 0, 4 waves, resident grid", (8, 4), (1, 1), 25, 512, ("random", 96, 13), 8192,
           (_mfma(4, 0, 0, 32, 0),), variant=2, auto=2),
-    # the forced variants on the shapes of a and e (k2_channel_fd_mfma.hip:1038-1044): 4 = go4 x ITEMS_PER_WG,
+    # the forced variants on the shapes of a and e (k2_channel_fd_mfma.hip:1022-1028): 4 = go4 x ITEMS_PER_WG,
     # 5 = go8, 3 = 16 waves with plain stores, 10 = go16 x ITEMS_PER_WG, 11 = go16 on the resident grid; variant 8 (go16,
     # one workgroup per item) is the loop-free instantiation 10 and 11 must equal bit for bit
     Route("h_fact", "variants 4, 5, 3, 10, 11 vs 8 on a", (8, 8), (2, 2), 25, 512, ("range", 0, 128, 1), 8192,
@@ -222,7 +222,7 @@ ROUTES = (
     Route("o", "k3_lpf_fft_wave (K = 600 > N = 512)", (2, 1), (1, 1), 25, 512, ("range", 0, 600, 1), 8192,
           (_FFTW512,), kind="lpf"),
     # GSRC 1 (the float gains table with matrix cores): rx_filter with more than 32 path slots (lpf_table_packed is
-    # false, k2_channel_fd.hip:320); the first 32 kept paths go through the matrix cores, the rest through the vector
+    # false, k2_channel_fd.hip:308); the first 32 kept paths go through the matrix cores, the rest through the vector
     # kernel's accumulate passes
     Route("s", "rx_filter GSRC 1 (40 paths), 8 waves + k3_lpf_fft512 float table", (4, 4), (2, 1), 40, 512,
           ("range", 0, 256, 1), 16384, (_mfma(8, 0, 1, 32, 8), _FFT512), kind="lpf"),

@@ -679,13 +679,15 @@ def test_rx_filter_fft512_variants(selection, arrays):
 
 
 @pytest.mark.parametrize("arrays", ["mfma", "valu"])
-@pytest.mark.parametrize("selection", ["all", "first_half", "random", "offset"])
-@pytest.mark.parametrize("N", [64, 128, 256, 1024])
+@pytest.mark.parametrize("N,selection", [(N, s) for N in (64, 128, 256, 1024) for s in ("all", "first_half", "random", "offset")] +
+                         [(1024, "wrap")])
 def test_rx_filter_fft_pow2_variants(N, selection, arrays):
     """k3_lpf_fft_pow2: the register FFT of the other default OFDM sizes - 8, 4 and 2 paths per wave (N = 64, 128, 256:
     the last lane group runs past a user's path count) and 16 points per lane with a radix-16 last pass (N = 1024);
     selections stored from registers or through the buffer, packed or float table, Doppler on and off, users with 0, 1, 2
-    and all paths, whole-sample delays."""
+    and all paths, whole-sample delays.  1024-wrap: more subcarriers than bins leave this kernel for the generic
+    k3_lpf_fft_wave, whose tables at N = 1024 (77,888 bytes) are its smallest request beyond the 64 KiB a workgroup gets
+    by default - the launch that first raises the kernel's dynamic-LDS limit."""
     import deepmimo_amd as dm
     from oracle import oracle_np as onp
     n_ue = 9 if N == 1024 else 14
@@ -699,7 +701,7 @@ def test_rx_filter_fft_pow2_variants(N, selection, arrays):
             rays[k][7, 2:] = np.nan
     rays["power"][8, ~np.isnan(rays["power"][8])] = -80.0            # equal powers: a lost path (the last one sits alone in its
     #                                                                  lane-group iteration) is an error of 1 / n_paths, not of its luck
-    sel = {"all": np.arange(N), "first_half": np.arange(N // 2), "offset": np.arange(N, 2 * N),
+    sel = {"all": np.arange(N), "first_half": np.arange(N // 2), "offset": np.arange(N, 2 * N), "wrap": np.arange(N + 6),
            "random": np.sort(np.random.default_rng(N).choice(N, max(5, N // 5), replace=False))}[selection]
     bs, ue = ([8, 4], [2, 2]) if arrays == "mfma" else ([2, 1], [1, 1])
     case = dict(bs_shape=bs, ue_shape=ue, bs_spacing=0.5, ue_spacing=0.5, bs_rot=[0, 10, 45],
