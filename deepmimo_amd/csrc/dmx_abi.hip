@@ -306,6 +306,61 @@ int dmx_channel_covariance(const dmx_params* prm, const void* workspace, int64_t
     return launch_covariance(*prm, ws, user_begin, user_count, side, (float2*)out_c64, (hipStream_t)stream);
 }
 
+// 1: taken; 0: not taken, with the limit in the error string; negative: bad argument
+static int rate_shape(const dmx_params* prm, int32_t n_paths_loaded) {
+    if (n_paths_loaded < 0) { set_error("n_paths_loaded must be >= 0"); return DMX_ERR_ARG; }
+    if (!prm->freq_domain || prm->rx_filter) { set_error("the rate needs freq_domain = 1 and rx_filter = 0"); return 0; }
+    const int P = used_paths(prm, n_paths_loaded);
+    if (P < 1 || P > 32) {
+        set_error("rate: min(num_paths, loaded paths) = %d is outside the 1..32 paths the kernel supports", P);
+        return 0;
+    }
+    if (prm->n_selected < 1) { set_error("rate: at least one selected subcarrier is needed"); return 0; }
+    const long long m_tx = (long long)prm->bs_shape[0] * prm->bs_shape[1], m_rx = (long long)prm->ue_shape[0] * prm->ue_shape[1];
+    const long long m = m_rx <= m_tx ? m_rx : m_tx, big = m_rx <= m_tx ? m_tx : m_rx;
+    if (m > 8) {
+        set_error("rate: min(M_rx, M_tx) = %lld exceeds the 8 elements of the smaller array the kernel supports", m);
+        return 0;
+    }
+    if (rate_waves_per_block(*prm, P) == 0) {
+        const int kc = prm->n_selected < 64 ? prm->n_selected : 64;
+        set_error("rate: one user's tables, (%lld + %lld + %d) * %d * 8 = %lld bytes, exceed the %zu bytes of LDS a wave can get",
+                  m, big, kc, P, (m + big + kc) * P * 8, WAVE_LDS_MAX);
+        return 0;
+    }
+    return 1;
+}
+
+int dmx_rate_supported(const dmx_params* prm, int32_t n_paths_loaded) {
+    int rc = check_params(prm);
+    if (rc) return rc;
+    return rate_shape(prm, n_paths_loaded);
+}
+
+int dmx_channel_rate(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
+                     int64_t user_begin, int64_t user_count, double snr_linear, float* out_rate, float* out_rate_k,
+                     void* stream) {
+    // the checks of stage2_common, with float outputs: rows of a float32 tensor are 4-byte aligned
+    int rc = check_params(prm);
+    if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
+    if (user_count > 0 && (!workspace || !out_rate)) { set_error("workspace/out is NULL"); return DMX_ERR_ARG; }
+    if ((rc = check_workspace_aligned(workspace))) return rc;
+    if (((uintptr_t)out_rate & 3u) || ((uintptr_t)out_rate_k & 3u)) { set_error("out_rate / out_rate_k must be 4-byte aligned"); return DMX_ERR_ARG; }
+    if (!prm->freq_domain) { set_error("dmx_channel_rate called with freq_domain = 0"); return DMX_ERR_ARG; }
+    if (prm->rx_filter) { set_error("dmx_channel_rate does not cover rx_filter = 1"); return DMX_ERR_ARG; }
+    // finite and > 0, and so is its square root in float32 (the kernel's scale of the path coefficients)
+    if (!(snr_linear >= 1e-70) || !(snr_linear <= 1e70)) {
+        set_error("dmx_channel_rate: snr_linear must be finite and > 0 (1e-70 .. 1e70), got %g", snr_linear); return DMX_ERR_ARG;
+    }
+    rc = rate_shape(prm, n_paths_loaded);
+    if (rc < 0) return rc;
+    if (rc == 0) return DMX_ERR_SHAPE;
+    if (user_count == 0) return DMX_OK;
+    WsView ws;
+    ws_carve(const_cast<void*>(workspace), n_ue, used_paths(prm, n_paths_loaded), &ws);
+    return launch_rate(*prm, ws, user_begin, user_count, snr_linear, out_rate, out_rate_k, (hipStream_t)stream);
+}
+
 int dmx_channels_td(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                     int64_t user_begin, int64_t user_count, void* out_c64, void* stream) {
     WsView ws;

@@ -155,6 +155,10 @@ int launch_channels_td(const dmx_params& prm, const WsView& ws, int64_t user_beg
 int cov_waves_per_block(const dmx_params& prm, int P, int side, int* kc_out);
 int launch_covariance(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, int side,
                       float2* out, hipStream_t stream);
+size_t rate_lds_bytes(const dmx_params& prm, int P);
+int rate_waves_per_block(const dmx_params& prm, int P);
+int launch_rate(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, double snr_linear,
+                float* out_rate, float* out_rate_k, hipStream_t stream);
 
 // between the stage-2 files: the kernels variant 0 chooses from (k2_channel_fd.hip), their predicates and launchers
 bool fd_mfma_preferred(const dmx_params& prm, const WsView& ws);

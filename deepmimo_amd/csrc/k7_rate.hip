@@ -1,0 +1,241 @@
+// Fused consumer of the per-path records: the per-user achievable rate of the frequency-domain channel
+// with equal power on every transmit antenna and no channel knowledge at the transmitter, without the channel tensor:
+//   H_k[r,t]     = sum_l c_l a_rx[r,l] a_tx[t,l] g[l,k],            g[l,k] = exp(-j 2pi dn_l sc_k / N)
+//   rate_k[u,k]  = log2 det(I + (snr / M_tx) H_k H_k^H) = log2 det(I + G_k),   rate[u] = 1/K sum_k rate_k[u,k]
+//   G_k[i,j]     = sum_t h_i[t] conj(h_j[t]),   h_i[t] = sum_l a_small[i,l] a_big[t,l] w[l,k],   w[l,k] = sqrt(snr / M_tx) c_l g[l,k]
+// det(I + s H H^H) = det(I + s H^H H): the Gram matrix is formed over the SMALLER array (m = min(M_rx, M_tx) <= 8 elements,
+// the UE side on a tie), t runs over the larger one.  G is the Gram of the rows h_i and so positive semidefinite by
+// construction, whatever fp32 does to the rows; the P x P path-coupling route (G = V T V^H) is cheaper but loses that, and a
+// rank-1 user at high SNR then shows a spurious second eigenvalue of either sign.
+// One WAVE per user as k6_covariance: no workgroup barrier, the wave's tables in its own LDS slice, a flat grid.
+//   1  array tables a_small[m][l], a_big[M_big][l]: float64 phase reduction + sincos_rev
+//   2  per chunk of kc = min(K, 64) subcarriers: w[l][k] PATH-MAJOR in LDS (phase = fma(x, k, -rint(x k)) in float64, any
+//      int32 index), so lanes that own consecutive subcarriers read consecutive words and a_small / a_big reads broadcast
+//   3  a lane owns a subcarrier - or, for K < 64, a (subcarrier, slice s of S) pair, lane = k S + s, S a power of two, slice s
+//      taking t = s, s + S, ... - and adds the upper triangle of G in registers, two t per trip of the path loop; the slices
+//      of a subcarrier are added in a fixed xor tree across the lanes
+//   4  unrolled elimination of I + G (the kernel is templated on m): every pivot is >= 1 in exact arithmetic and is clamped
+//      to that, rate_k = sum log2(pivot); rate_k is stored coalesced if wanted; the lane sums its chunks in chunk order, the
+//      wave adds the lanes in a fixed xor tree
+// fp32 vector arithmetic, no atomics, every sum in a fixed order that does not depend on where the user sits in the launch.
+// LDS of one wave: (m + M_big + kc) * P * 8 bytes, P = min(num_paths, loaded paths) <= 32; rate_lds_bytes has the rule.
+// Bound: fp32 VALU issue of phase 3 (M_big * P * (1 + m) complex products per subcarrier), far below HBM.
+#include "dmx_common.h"
+#include "k2_small_body.h"
+#include <math.h>
+
+namespace dmx {
+
+struct RateArgs {
+    int64_t user_begin, user_count;
+    int m_big, big_mh, small_mh;
+    int small_is_rx;     // the Gram runs over the UE array (M_rx <= M_tx), else over the BS array
+    int K, kc;           // selected subcarriers, subcarriers per chunk = w row stride
+    int S, log2_S;       // slices of the large array per subcarrier (1 unless K < 64)
+    const int32_t* sc;
+    double inv_n;
+    float scale;         // sqrt(snr / M_tx)
+    float inv_k;
+    int ld;              // table row stride in path slots (= P)
+};
+
+template <int M>
+__global__ __launch_bounds__(256) void k7_rate(WsView ws, RateArgs a, float* __restrict__ out_rate, float* __restrict__ out_rate_k) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+    const int64_t ul = (int64_t)blockIdx.x * wpb + wave;
+    if (ul >= a.user_count) return;                                          // waves never talk to each other
+    const int ld = a.ld, Mb = a.m_big, K = a.K, kc = a.kc, S = a.S;
+    const size_t per_wave = (size_t)(M + Mb + kc) * ld;
+    float2* as = reinterpret_cast<float2*>(smem_raw) + (size_t)wave * per_wave;     // [M][ld]
+    float2* ab = as + (size_t)M * ld;                                                // [Mb][ld]
+    float2* w = ab + (size_t)Mb * ld;                                                // [ld][kc]
+    const int64_t u = a.user_begin + ul;
+    float* ok = out_rate_k ? out_rate_k + (size_t)ul * K : nullptr;
+    int n = __builtin_amdgcn_readfirstlane(ws.n_keep[u]);
+    n = n < ld ? n : ld;
+    if (n <= 0) {                                                            // no kept path: +0.0 everywhere
+        if (ok) for (int i = lane; i < K; i += 64) ok[i] = 0.f;
+        if (lane == 0) out_rate[ul] = 0.f;
+        return;
+    }
+    const WsRecords rec{ws, (size_t)u * ws.P};
+
+    // 1  array tables
+    for (int i = lane; i < M * n; i += 64) {
+        const int t = i / n, l = i - t * n;
+        const double sy = a.small_is_rx ? rec.rx_y(l) : rec.tx_y(l), sz = a.small_is_rx ? rec.rx_z(l) : rec.tx_z(l);
+        float s, c;
+        sincos_rev(frac_rev(__builtin_fma((double)(t % a.small_mh), sy, (double)(t / a.small_mh) * sz)), s, c);
+        as[t * ld + l] = make_float2(c, s);
+    }
+    for (int i = lane; i < Mb * n; i += 64) {
+        const int t = i / n, l = i - t * n;
+        const double sy = a.small_is_rx ? rec.tx_y(l) : rec.rx_y(l), sz = a.small_is_rx ? rec.tx_z(l) : rec.rx_z(l);
+        float s, c;
+        sincos_rev(frac_rev(__builtin_fma((double)(t % a.big_mh), sy, (double)(t / a.big_mh) * sz)), s, c);
+        ab[t * ld + l] = make_float2(c, s);
+    }
+
+    const int kl = lane >> a.log2_S, sl = lane & (S - 1);                    // this lane's subcarrier of the chunk and slice
+    float rate_sum = 0.f;
+    for (int k0 = 0; k0 < K; k0 += kc) {
+        const int kn = K - k0 < kc ? K - k0 : kc;
+        // 2  w of the chunk
+        wave_lds_fence();                                                    // the last chunk's reads before this chunk's writes
+        for (int i = lane; i < n * kn; i += 64) {
+            const int l = i / kn, k = i - l * kn;
+            float s, c;
+            // the fractional part of the EXACT product x * k (k2_small_body.h)
+            const double x = (double)rec.dn(l) * a.inv_n, kd = (double)a.sc[k0 + k];
+            sincos_rev((float)__builtin_fma(x, kd, -rint(x * kd)), s, c);
+            const float cr = rec.c_re(l) * a.scale, ci = rec.c_im(l) * a.scale;
+            w[l * kc + k] = make_float2(fmaf(cr, c, ci * s), fmaf(ci, c, -(cr * s)));     // c_l (cos - j sin)
+        }
+        wave_lds_fence();
+
+        // 3  this lane's share of the upper triangle of G
+        float gr[M * M], gi[M * M];
+#pragma unroll
+        for (int i = 0; i < M * M; ++i) gr[i] = gi[i] = 0.f;
+        const bool active = kl < kn;
+        if (active) {
+            const float2* wk = w + kl;
+            for (int t = sl; t < Mb; t += 2 * S) {
+                const bool two = t + S < Mb;
+                const float2* b0 = ab + (size_t)t * ld;
+                const float2* b1 = ab + (size_t)(two ? t + S : t) * ld;
+                float2 h0[M], h1[M];
+#pragma unroll
+                for (int i = 0; i < M; ++i) h0[i] = h1[i] = make_float2(0.f, 0.f);
+#pragma unroll 2
+                for (int l = 0; l < n; ++l) {
+                    const float2 x = wk[l * kc], p0 = b0[l], p1 = b1[l];
+                    const float2 q0 = make_float2(fmaf(x.x, p0.x, -(x.y * p0.y)), fmaf(x.x, p0.y, x.y * p0.x));
+                    const float2 q1 = make_float2(fmaf(x.x, p1.x, -(x.y * p1.y)), fmaf(x.x, p1.y, x.y * p1.x));
+#pragma unroll
+                    for (int i = 0; i < M; ++i) {
+                        const float2 v = as[i * ld + l];
+                        h0[i].x = fmaf(v.x, q0.x, fmaf(-v.y, q0.y, h0[i].x));
+                        h0[i].y = fmaf(v.x, q0.y, fmaf(v.y, q0.x, h0[i].y));
+                        h1[i].x = fmaf(v.x, q1.x, fmaf(-v.y, q1.y, h1[i].x));
+                        h1[i].y = fmaf(v.x, q1.y, fmaf(v.y, q1.x, h1[i].y));
+                    }
+                }
+                if (!two) {
+#pragma unroll
+                    for (int i = 0; i < M; ++i) h1[i] = make_float2(0.f, 0.f);
+                }
+#pragma unroll
+                for (int i = 0; i < M; ++i) {
+#pragma unroll
+                    for (int j = i; j < M; ++j) {                            // G_ij += h_i conj(h_j), first t then t + S
+                        float r = gr[i * M + j], im = gi[i * M + j];
+                        r = fmaf(h0[i].x, h0[j].x, fmaf(h0[i].y, h0[j].y, r));
+                        r = fmaf(h1[i].x, h1[j].x, fmaf(h1[i].y, h1[j].y, r));
+                        if (j > i) {
+                            im = fmaf(h0[i].y, h0[j].x, fmaf(-h0[i].x, h0[j].y, im));
+                            im = fmaf(h1[i].y, h1[j].x, fmaf(-h1[i].x, h1[j].y, im));
+                        }
+                        gr[i * M + j] = r; gi[i * M + j] = im;
+                    }
+                }
+            }
+        }
+        // the slices of a subcarrier sit in S neighbouring lanes: a fixed xor tree leaves the sum in each of them
+        for (int d = 1; d < S; d <<= 1) {
+#pragma unroll
+            for (int i = 0; i < M; ++i) {
+#pragma unroll
+                for (int j = i; j < M; ++j) {
+                    gr[i * M + j] += __shfl_xor(gr[i * M + j], d, 64);
+                    if (j > i) gi[i * M + j] += __shfl_xor(gi[i * M + j], d, 64);
+                }
+            }
+        }
+
+        // 4  pivots of I + G by elimination on the upper triangle, each clamped to >= 1
+        float lg = 0.f;
+#pragma unroll
+        for (int p = 0; p < M; ++p) {
+            const float d = fmaxf(gr[p * M + p] + (p == 0 ? 1.f : 0.f), 1.f);
+            lg += log2f(d);
+            const float inv = 1.f / d;
+#pragma unroll
+            for (int i = p + 1; i < M; ++i) {
+                const float er = gr[p * M + i] * inv, ei = -gi[p * M + i] * inv;         // conj(A_pi) / d
+#pragma unroll
+                for (int j = i; j < M; ++j) {
+                    const float xr = gr[p * M + j], xi = gi[p * M + j];
+                    gr[i * M + j] -= fmaf(er, xr, -(ei * xi));
+                    if (j > i) gi[i * M + j] -= fmaf(er, xi, ei * xr);
+                }
+                if (p == 0) gr[i * M + i] += 1.f;                            // the identity, once per diagonal entry
+            }
+        }
+        if (active && sl == 0) {
+            if (ok) ok[k0 + kl] = lg;
+            rate_sum += lg;
+        }
+    }
+    for (int d = 1; d < 64; d <<= 1) rate_sum += __shfl_xor(rate_sum, d, 64);
+    if (lane == 0) out_rate[ul] = rate_sum * a.inv_k;
+}
+
+// LDS bytes of one wave for P path slots (0: the shape is not taken): both array tables and one chunk of w,
+//   (m + M_big + kc) * P * 8,   m = min(M_rx, M_tx) <= 8,  M_big = max(M_rx, M_tx),  kc = min(n_selected, 64)
+// lds_waves_per_block turns that into 4 / 2 / 1 waves per workgroup (16 KB / 32 KB / 156 KB per wave).
+size_t rate_lds_bytes(const dmx_params& prm, int P) {
+    if (P < 1 || P > 32 || prm.n_selected < 1) return 0;
+    const size_t m_tx = (size_t)prm.bs_shape[0] * prm.bs_shape[1], m_rx = (size_t)prm.ue_shape[0] * prm.ue_shape[1];
+    const size_t m = m_rx <= m_tx ? m_rx : m_tx, big = m_rx <= m_tx ? m_tx : m_rx;
+    if (m > 8) return 0;
+    const size_t kc = prm.n_selected < 64 ? prm.n_selected : 64;
+    return (m + big + kc) * (size_t)P * sizeof(float2);
+}
+
+int rate_waves_per_block(const dmx_params& prm, int P) { return lds_waves_per_block(rate_lds_bytes(prm, P)); }
+
+template <int M>
+static int launch_rate_m(const dim3 g, const dim3 b, size_t smem, hipStream_t stream, const WsView& ws, const RateArgs& a,
+                         float* out_rate, float* out_rate_k) {
+    return launch_dyn_lds(k7_rate<M>, "k7_rate", g, b, smem, WAVE_LDS_MAX, stream, ws, a, out_rate, out_rate_k);
+}
+
+int launch_rate(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, double snr_linear,
+                float* out_rate, float* out_rate_k, hipStream_t stream) {
+    const int wpb = rate_waves_per_block(prm, ws.P);
+    if (!wpb) { set_error("rate kernel: tables of one user do not fit the LDS"); return DMX_ERR_SHAPE; }
+    const int m_tx = prm.bs_shape[0] * prm.bs_shape[1], m_rx = prm.ue_shape[0] * prm.ue_shape[1];
+    const bool rx_small = m_rx <= m_tx;
+    const int m = rx_small ? m_rx : m_tx;
+    RateArgs a;
+    a.user_begin = user_begin; a.user_count = user_count;
+    a.m_big = rx_small ? m_tx : m_rx;
+    a.big_mh = rx_small ? prm.bs_shape[0] : prm.ue_shape[0];
+    a.small_mh = rx_small ? prm.ue_shape[0] : prm.bs_shape[0];
+    a.small_is_rx = rx_small ? 1 : 0;
+    a.K = prm.n_selected; a.kc = a.K < 64 ? a.K : 64;
+    a.log2_S = 0;                                                            // the largest power of two with K S <= 64, S <= M_big
+    while (a.K * (2 << a.log2_S) <= 64 && (2 << a.log2_S) <= a.m_big) ++a.log2_S;
+    a.S = 1 << a.log2_S;
+    a.sc = prm.selected_subcarriers;
+    a.inv_n = 1.0 / (double)prm.n_subcarriers;
+    a.scale = (float)sqrt(snr_linear / (double)m_tx);
+    a.inv_k = (float)(1.0 / (double)a.K);
+    a.ld = ws.P;
+    const size_t smem = (size_t)wpb * rate_lds_bytes(prm, ws.P);
+    const dim3 g((unsigned)((user_count + wpb - 1) / wpb)), b(64 * wpb);    // flat: one wave per user
+    switch (m) {
+        case 1: return launch_rate_m<1>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
+        case 2: return launch_rate_m<2>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
+        case 3: return launch_rate_m<3>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
+        case 4: return launch_rate_m<4>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
+        case 5: return launch_rate_m<5>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
+        case 6: return launch_rate_m<6>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
+        case 7: return launch_rate_m<7>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
+        default: return launch_rate_m<8>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
+    }
+}
+
+}  // namespace dmx

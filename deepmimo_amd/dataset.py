@@ -415,6 +415,34 @@ class Dataset(DotDict):
         R = eng.covariance(prep, side=side)
         return R if config.get("channel_output", "numpy") == "torch" else R.cpu().numpy()
 
+    def compute_rate(self, params: Optional[ChannelGenParameters] = None, *, snr_db=None, per_subcarrier: bool = False):
+        """Per-user achievable rate (spectral efficiency) in bit/s/Hz, with no channel tensor written anywhere
+        (extension) - equal power on every BS antenna, no channel knowledge at the transmitter:
+
+            s = 10 ** (snr_db / 10) / M_tx            # snr_db: total transmit power over noise power per subcarrier
+            rate_k[u, k] = log2 det(I + s * H[u, :, :, k] @ H[u, :, :, k].conj().T)
+            rate[u]      = rate_k[u].mean()
+
+        Returns float32 [n_ue] (with ``per_subcarrier`` the pair ``(rate, rate_k)``, rate_k float32 [n_ue, K]): NumPy arrays
+        by default, the HBM-resident torch tensors when ``config('channel_output') == 'torch'``.  ``snr_db`` is required
+        and keyword-only.  Users without a path get 0.  Frequency domain without ``rx_filter``, at most 32 used paths, the smaller array of at most 8 elements, tables
+        within the LDS (include/deepmimo_amd.h has the rule): anything else raises ValueError before any GPU work.  Not
+        cached."""
+        from .engine import check_rate_call, snr_linear_from_db
+        if snr_db is None:
+            raise ValueError("compute_rate: snr_db (dB, keyword) is required")
+        snr_linear_from_db(snr_db)
+        if params is None:
+            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
+        self.set_channel_params(params)
+        check_rate_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), snr_db)
+        np.random.seed(1001)
+        eng, prep = self._run_prep(want_side="light")
+        res = eng.rate(prep, snr_db, per_subcarrier=per_subcarrier)
+        if config.get("channel_output", "numpy") == "torch":
+            return res
+        return tuple(t.cpu().numpy() for t in res) if per_subcarrier else res.cpu().numpy()
+
     def compute_pathloss(self, coherent: bool = True) -> np.ndarray:
         """Path loss in dB assuming 0 dBm transmitted power (dataset.py:541-566); cached as ``pathloss``."""
         eng = _engine()

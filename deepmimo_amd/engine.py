@@ -10,6 +10,7 @@ include/deepmimo_amd.h and calls the C-ABI:
     dmx_channels_fd -> complex64 [N, M_rx, M_tx, K]     (dmx_channels_fd_lpf when rx_filter = 1)
     dmx_channels_td -> complex64 [N, M_rx, M_tx, P]
     dmx_channel_covariance -> complex64 [N, M, M]       (per-user spatial covariance, no channel tensor)
+    dmx_channel_rate     -> float32 [N] (and [N, K])    (per-user achievable rate, no channel tensor)
 
 It replaces the body of Dataset.compute_channels (deepmimo/generator/dataset.py:224-268).
 No CPU path exists here: without the shared library or without a GPU every entry point raises.
@@ -17,6 +18,7 @@ No CPU path exists here: without the shared library or without a GPU every entry
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass, field
 from typing import Dict, Optional
 
@@ -204,6 +206,35 @@ def check_covariance_call(params, n_paths_loaded: int, side) -> int:
     if rc != 1:
         raise ValueError("covariance: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
     return sid
+
+
+def snr_linear_from_db(snr_db) -> float:
+    """10 ** (snr_db / 10) in float64; ValueError for anything that is not a finite real number."""
+    if isinstance(snr_db, bool) or not isinstance(snr_db, (int, float, np.integer, np.floating)) or not math.isfinite(float(snr_db)):
+        raise ValueError(f"rate: snr_db must be a finite number (dB), got {snr_db!r}")
+    return 10.0 ** (float(snr_db) / 10.0)
+
+
+def check_rate_call(params, n_paths_loaded: int, snr_db) -> float:
+    """Everything `Dataset.compute_rate` can refuse without a GPU, as ValueError: time domain, rx_filter, an snr_db that is
+    not finite, and a shape dmx_rate_supported does not take (the message is the library's and names the limit).  `params`:
+    validated ChannelGenParameters.  Returns the linear SNR."""
+    snr = snr_linear_from_db(snr_db)
+    ofdm = params[c.PARAMSET_OFDM]
+    if not params[c.PARAMSET_FD_CH]:
+        raise ValueError("rate: needs the frequency-domain channel (freq_domain = 1)")
+    if ofdm[c.PARAMSET_OFDM_LPF]:
+        raise ValueError("rate: ofdm.rx_filter = 1 is not covered")
+    sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
+    p = nat.DmxParams()
+    _fill_shape_fields(p, params, sel.size)
+    host_sel = (C.c_int32 * max(1, int(sel.size)))()          # the query reads the count, never the array
+    p.selected_subcarriers = C.addressof(host_sel)
+    lib = nat.load()
+    rc = lib.dmx_rate_supported(C.byref(p), int(n_paths_loaded))
+    if rc != 1:
+        raise ValueError("rate: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
+    return snr
 
 
 class ChannelEngine:
@@ -663,6 +694,42 @@ class ChannelEngine:
                                                  C.c_void_p(out.data_ptr()), self._stream_ptr())
         nat.check(rc, "dmx_channel_covariance")
         return out
+
+    def rate_supported(self, prep: PrepResult) -> bool:
+        """dmx_rate_supported for this preparation (host-only query; `rate` raises where it says no)."""
+        rc = self.lib.dmx_rate_supported(C.byref(prep.params_struct), prep.n_paths_loaded)
+        if rc < 0:
+            nat.check(rc, "dmx_rate_supported")
+        return rc == 1
+
+    def rate(self, prep: PrepResult, snr_db, user_begin: int = 0, user_count: Optional[int] = None,
+             per_subcarrier: bool = False, out=None):
+        """dmx_channel_rate: per-user achievable rate in bit/s/Hz at `snr_db` (total transmit power over noise power per
+        subcarrier, equal power per BS antenna), rate[u] = mean over k of log2 det(I + snr / M_tx H_k H_k^H), float32
+        [user_count] in HBM, from the per-path records of `prep` - the channel tensor is not written.  With
+        `per_subcarrier` the pair (rate, rate_k), rate_k float32 [user_count, K].  `out`: the tensor (or the pair of
+        tensors) to write into."""
+        snr = snr_linear_from_db(snr_db)
+        p = prep.params_struct
+        if user_count is None:
+            user_count = prep.n_ue - user_begin
+        out_r, out_k = (out if isinstance(out, (tuple, list)) else (out, None)) if out is not None else (None, None)
+
+        def f32(t, shape):
+            if t is None:
+                return torch.empty(shape, dtype=torch.float32, device=self.device)
+            if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+                raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
+            return t
+        r = f32(out_r, (user_count,))
+        rk = f32(out_k, (user_count, int(p.n_selected))) if per_subcarrier else None
+        with torch.cuda.device(self.device):
+            rc = self.lib.dmx_channel_rate(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
+                                           prep.n_paths_loaded, int(user_begin), int(user_count), snr,
+                                           C.c_void_p(r.data_ptr()), C.c_void_p(rk.data_ptr()) if per_subcarrier else None,
+                                           self._stream_ptr())
+        nat.check(rc, "dmx_channel_rate")
+        return (r, rk) if per_subcarrier else r
 
     def pathloss(self, rays: DeviceRays, coherent: bool = True) -> torch.Tensor:
         """dmx_pathloss: float32 [n_ue] dB (dataset.py:541-566)."""

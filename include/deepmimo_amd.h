@@ -268,6 +268,37 @@ int dmx_channel_covariance(const dmx_params* prm, const void* workspace, int64_t
                            int64_t user_begin, int64_t user_count, int32_t side, void* out_c64, void* stream);
 
 /*
+ * Fused consumer: the per-user achievable rate (spectral efficiency) of the frequency-domain channel,
+ * equal power on every transmit antenna and no channel knowledge at the transmitter, from the workspace of dmx_path_prep -
+ * H is never written.  With H_k = H[u, :, :, k] (M_rx x M_tx, including the 1/sqrt(N) factor of the channel tensor) and
+ * snr_linear the ratio of the total transmit power to the noise power per subcarrier:
+ *   rate_k[u, k] = log2 det(I + (snr_linear / M_tx) H_k H_k^H)       bit/s/Hz   out_rate_k float32 [user_count, K], may be NULL
+ *   rate[u]      = 1 / K sum_k rate_k[u, k]                                     out_rate   float32 [user_count]
+ * for users [user_begin, user_begin + user_count).  det(I + s H H^H) = det(I + s H^H H): the kernel forms the Gram matrix
+ * over the smaller array, m = min(M_rx, M_tx), as the Gram of the channel's rows (positive semidefinite by construction),
+ * and takes log2 of the pivots of I + G, each clamped to >= 1 (its lower bound in exact arithmetic).  No output is NaN or
+ * negative; a user without kept paths gets +0.0 in both outputs.  fp32 arithmetic in a fixed order, no atomics: launches
+ * repeat bit for bit and a user sub-range equals the same rows of a whole launch.  Subcarrier phases are reduced in
+ * float64: any int32 index is valid (DMX_SC_ABS_MAX_F32 does not apply).  prm->flags changes the order of a user's records
+ * and so the summation order only; the workspace of either arithmetic mode is accepted.
+ *
+ * dmx_rate_supported - host-only: 1 if dmx_channel_rate takes this shape, 0 if not (dmx_last_error() then names the limit),
+ * negative on a bad argument.  No GPU involved.  Taken: freq_domain = 1, rx_filter = 0, P = min(num_paths, n_paths_loaded)
+ * in 1..32, n_selected >= 1, m = min(M_rx, M_tx) <= 8, and one wave's tables within the LDS:
+ *   (m + M_big + kc) * P * 8 bytes <= 156 KB (159744),   M_big = max(M_rx, M_tx),   kc = min(n_selected, 64)
+ * At 25 paths: m + M_big + kc <= 798, e.g. a 64 x 4 BS panel with a 2 x 2 UE at 512 subcarriers (324), DeepMIMO's defaults
+ * (8 x 1 / 1 x 1), or a 2 x 1 BS with a 4 x 4 UE (the Gram then runs over the BS side); a 32 x 32 BS panel is refused.
+ *
+ * dmx_channel_rate - time domain, rx_filter = 1, or an snr_linear that is not finite and > 0 (taken: 1e-70 .. 1e70):
+ * DMX_ERR_ARG; an unsupported shape: DMX_ERR_SHAPE with the limit in the message; user_count = 0: DMX_OK, nothing done.
+ * out_rate / out_rate_k: 4-byte aligned device pointers.
+ */
+int dmx_rate_supported(const dmx_params* prm, int32_t n_paths_loaded);
+int dmx_channel_rate(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
+                     int64_t user_begin, int64_t user_count, double snr_linear, float* out_rate, float* out_rate_k,
+                     void* stream);
+
+/*
  * Stage 2, time domain (replaces channel.py:285-287): out[u, rx, tx, s] = a_rx a_tx sqrt(p) e^{j phase}
  * of the s-th valid path (valid paths compacted to the front, remaining slots zero),
  * complex64 [user_count, M_rx, M_tx, P], P = min(num_paths, n_paths_loaded).

@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""Per-user achievable rate: the fused route against the channel tensor + torch.linalg.slogdet, alternating in ONE process:
+`python tools/rate_bench.py [--out profiles/r6_rate_bench.jsonl]`.
+
+For each shape, on the same uploaded rays:
+  (a) fused    dmx_path_prep + dmx_channel_rate                                  (no channel tensor)
+  (b) slogdet  dmx_path_prep + per user chunk: dmx_channels_fd (variant 0) into a resident tensor, the Gram over the smaller
+               array by torch.einsum, torch.linalg.slogdet of I + s G, the mean over the subcarriers
+Device events around back-to-back launches of one route, the routes alternating `--rounds` times after a warm-up; the
+whole A/B runs twice (`pass` 0 and 1) and the difference between the two passes of the SAME route is the spread a
+difference between the routes has to exceed.  One JSON line per shape: mean, minimum and spread of both routes, the fused
+kernel's algorithmic flops (complex product 6, complex multiply-add 8) and their share of the fp32 vector peak (256 CUs x
+4 SIMDs x 64 flop per clock at 2.4 GHz), and the largest deviation between the two results in bit.  Without a GPU the
+tool fails.
+"""
+import argparse
+import ctypes as C
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import deepmimo_amd as dm  # noqa: E402
+from deepmimo_amd.engine import ChannelEngine  # noqa: E402
+from deepmimo_amd import _native as nat  # noqa: E402
+from oracle import oracle_np as onp  # noqa: E402
+
+# (name, BS panel, UE panel, K, users, users per chunk of route (b)): the headline shape (H would be 105 GB) and DeepMIMO's
+# defaults (one subcarrier)
+SHAPES = [("headline_K512", [64, 4], [2, 2], 512, 100_000, 5_000), ("defaults_K1", [8, 1], [1, 1], 1, 200_000, 200_000)]
+FP32_VALU_PEAK = 256 * 4 * 64 * 2.4e9
+
+
+def timed(fn, launches):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(launches):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / launches
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--paths", type=int, default=25)
+    ap.add_argument("--snr-db", type=float, default=110.0)
+    ap.add_argument("--launches", type=int, default=5, help="back-to-back launches of a route per timing")
+    ap.add_argument("--rounds", type=int, default=2, help="timings per route and pass: 2 passes x rounds x launches launches in all")
+    ap.add_argument("--shapes", default=",".join(s[0] for s in SHAPES))
+    ap.add_argument("--scale", type=float, default=1.0, help="multiply every user count (rehearsals)")
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    eng = ChannelEngine(0)
+    lib, L = eng.lib, args.paths
+    stream = eng._stream_ptr()
+    snr = 10.0 ** (args.snr_db / 10.0)
+    lines = []
+    for name, bs, ue, K, users, chunk in SHAPES:
+        if name not in args.shapes.split(","):
+            continue
+        n = max(1, int(users * args.scale))
+        chunk = min(chunk, n)
+        rays = eng.upload_rays(onp.synth_rays(n, L, seed=1234, all_valid=True))
+        p = dm.ChannelGenParameters()
+        p.bs_antenna.shape, p.ue_antenna.shape = np.array(bs), np.array(ue)
+        p.ofdm.selected_subcarriers = np.arange(K)
+        p.validate(n)
+        prep = eng.prepare(rays, p, want_side="light")
+        ps, rs, ss = prep.params_struct, prep.rays_struct, prep.side_struct
+        m_tx, m_rx = int(np.prod(bs)), int(np.prod(ue))
+        m, big = min(m_tx, m_rx), max(m_tx, m_rx)
+        H = torch.empty((chunk, m_rx, m_tx, K), dtype=torch.complex64, device=eng.device)
+        wsp = C.c_void_p(prep.workspace.data_ptr())
+        r_fused = torch.empty((n,), dtype=torch.float32, device=eng.device)
+        r_ref = torch.empty((n,), dtype=torch.float32, device=eng.device)
+        eye = torch.eye(m, dtype=torch.complex64, device=eng.device)
+        spec = "uitk,ujtk->ukij" if m_rx <= m_tx else "urjk,urik->ukij"
+        s = snr / m_tx
+
+        def fused():
+            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            nat.check(lib.dmx_channel_rate(C.byref(ps), wsp, n, L, 0, n, snr, C.c_void_p(r_fused.data_ptr()), None, stream),
+                      "dmx_channel_rate")
+
+        def slogdet():
+            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            for b in range(0, n, chunk):
+                cnt = min(chunk, n - b)
+                nat.check(lib.dmx_channels_fd(C.byref(ps), wsp, n, L, b, cnt, C.c_void_p(H.data_ptr()), 0, stream), "dmx_channels_fd")
+                G = torch.einsum(spec, H[:cnt], H[:cnt].conj())
+                r_ref[b:b + cnt] = (torch.linalg.slogdet(eye + s * G)[1] / math.log(2.0)).mean(dim=1)
+
+        routes = [("fused", fused), ("slogdet", slogdet)]
+        rec = dict(shape=name, bs=bs, ue=ue, K=K, users=n, paths=L, snr_db=args.snr_db, chunk_users=chunk,
+                   H_bytes=n * m_rx * m_tx * K * 8, launches_per_route=2 * args.rounds * args.launches)
+        rec["fused_flops"] = n * K * big * (L * (6 + 8 * m) + 8 * m * (m + 1) // 2)
+        for ab in range(2):
+            for _, fn in routes:                                         # warm-up
+                timed(fn, 1)
+            ts = {rn: [] for rn, _ in routes}
+            for _ in range(args.rounds):
+                for rn, fn in routes:
+                    ts[rn].append(timed(fn, args.launches))
+            for rn, v in ts.items():
+                rec[f"{rn}_avg_ms_pass{ab}"] = round(float(np.mean(v)), 5)
+                rec[f"{rn}_min_ms_pass{ab}"] = round(float(np.min(v)), 5)
+        for rn, _ in routes:
+            a0, a1 = rec[f"{rn}_avg_ms_pass0"], rec[f"{rn}_avg_ms_pass1"]
+            rec[f"{rn}_avg_ms"] = round((a0 + a1) / 2, 5)
+            rec[f"{rn}_spread_ms"] = round(abs(a0 - a1), 5)
+        rec["speedup"] = round(rec["slogdet_avg_ms"] / rec["fused_avg_ms"], 3)
+        rec["fused_share_of_fp32_valu_peak"] = round(rec["fused_flops"] / (rec["fused_avg_ms"] * 1e-3) / FP32_VALU_PEAK, 4)
+        rec["max_dev_bit"] = float((r_fused - r_ref).abs().max())
+        rec["mean_rate"] = float(r_fused.double().mean())
+        lines.append(json.dumps(rec))
+        print(lines[-1], flush=True)
+        del H, prep, rays
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
