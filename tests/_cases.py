@@ -71,6 +71,34 @@ def assert_channel_close(H, Href, tol_rel=TOL_REL, tol_abs=TOL_ABS, what=""):
     return float(np.max(d / np.maximum(peak, 1e-300))) if d.size else 0.0
 
 
+def assert_taps_close(H, Href, tol_rel=TOL_REL, what=""):
+    """Time-domain tensors [n, M_rx, M_tx, P], one path per slot: every (user, slot) is held to its OWN peak,
+    max over rx, tx |dH| <= tol_rel * max over rx, tx |Href[user, :, :, slot]|.  The per-user peak of `assert_channel_close`
+    is the scale of a sum over all paths; here it would let a tap 1e-4 of the strongest one be wrong by half its amplitude.
+    A slot whose reference is all zero (past the kept count, or a path whose array response is zeroed) must be exactly
+    zero, either sign.  Returns the worst error / (tol_rel * slot peak)."""
+    H, Href = np.asarray(H), np.asarray(Href)
+    assert H.shape == Href.shape, f"{what}: shape {H.shape} vs {Href.shape}"
+    assert H.ndim == 4, f"{what}: expected [n, M_rx, M_tx, P], got {H.shape}"
+    fin = np.isfinite(Href.astype(np.complex128))
+    assert np.array_equal(np.isfinite(H.astype(np.complex128)), fin), f"{what}: NaN pattern differs"
+    if H.size == 0:
+        return 0.0
+    Hd, Rd = np.where(fin, H, 0).astype(np.complex128), np.where(fin, Href, 0).astype(np.complex128)
+    d = np.abs(Hd - Rd).max(axis=(1, 2))                              # [n, P]
+    peak = np.abs(Rd).max(axis=(1, 2))
+    zero = peak == 0
+    nz = np.abs(Hd).max(axis=(1, 2))
+    if (zero & (nz != 0)).any():
+        u, s = np.argwhere(zero & (nz != 0))[0]
+        raise AssertionError(f"{what}: user {u} slot {s} has an all-zero reference but holds {nz[u, s]:.3e}")
+    ratio = np.where(zero, 0.0, d / (tol_rel * np.where(zero, 1.0, peak)))
+    u, s = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+    assert ratio[u, s] <= 1.0, (f"{what}: {(ratio > 1.0).sum()} taps out of tolerance; worst user {u} slot {s}: error "
+                                f"{d[u, s]:.3e}, slot peak {peak[u, s]:.3e}, ratio to the bound {ratio[u, s]:.3e} (tol {tol_rel})")
+    return float(ratio[u, s])
+
+
 # ---- seeded random configurations (shared by the GPU sweep and the C-oracle cross-check) --------------------
 def _random_config(rng):
     bs = [int(rng.integers(1, 13)), int(rng.integers(1, 9))]
