@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from tests._cases import oracle_params, assert_channel_close, channel_err
+from tests._path_count_cases import flat as _flat
 from tests.test_gpu_parity import _dm_params
 
 pytestmark = pytest.mark.gpu
@@ -13,14 +14,6 @@ pytestmark = pytest.mark.gpu
 # dropping the packed step's lo terms would leave ~2^-11 of a path's amplitude (~1e-4 of the peak), the 3-term
 # products leave ~2e-6
 TAIL_TOL = 1e-5
-
-
-def _flat(rays, seed):
-    """the same rays with every valid path's power drawn from [-66, -60] dB instead of [-140, -60]"""
-    r = {k: v.copy() for k, v in rays.items()}
-    ok = np.isfinite(r["power"])
-    r["power"][ok] = np.random.default_rng(seed).uniform(-66, -60, ok.sum()).astype(np.float32)
-    return r
 
 
 def _case(bs, ue, L, N, sel):
