@@ -361,6 +361,37 @@ int dmx_channel_rate(const dmx_params* prm, const void* workspace, int64_t n_ue,
     return launch_rate(*prm, ws, user_begin, user_count, snr_linear, out_rate, out_rate_k, (hipStream_t)stream);
 }
 
+int dmx_spectrum_supported(const dmx_params* prm, int32_t n_paths_loaded) {
+    return dmx_rate_supported(prm, n_paths_loaded);                          // the same kernel body, the same rule
+}
+
+int dmx_channel_spectrum(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
+                         int64_t user_begin, int64_t user_count, double snr_linear, float* out_gamma, float* out_rate,
+                         float* out_rate_k, void* stream) {
+    int rc = check_params(prm);
+    if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
+    if (user_count > 0 && !workspace) { set_error("workspace is NULL"); return DMX_ERR_ARG; }
+    if (user_count > 0 && !out_gamma && !out_rate && !out_rate_k) {
+        set_error("dmx_channel_spectrum: out_gamma, out_rate and out_rate_k are all NULL"); return DMX_ERR_ARG;
+    }
+    if ((rc = check_workspace_aligned(workspace))) return rc;
+    if (((uintptr_t)out_gamma & 3u) || ((uintptr_t)out_rate & 3u) || ((uintptr_t)out_rate_k & 3u)) {
+        set_error("out_gamma / out_rate / out_rate_k must be 4-byte aligned"); return DMX_ERR_ARG;
+    }
+    if (!prm->freq_domain) { set_error("dmx_channel_spectrum called with freq_domain = 0"); return DMX_ERR_ARG; }
+    if (prm->rx_filter) { set_error("dmx_channel_spectrum does not cover rx_filter = 1"); return DMX_ERR_ARG; }
+    if (!(snr_linear >= 1e-70) || !(snr_linear <= 1e70)) {
+        set_error("dmx_channel_spectrum: snr_linear must be finite and > 0 (1e-70 .. 1e70), got %g", snr_linear); return DMX_ERR_ARG;
+    }
+    rc = rate_shape(prm, n_paths_loaded);
+    if (rc < 0) return rc;
+    if (rc == 0) return DMX_ERR_SHAPE;
+    if (user_count == 0) return DMX_OK;
+    WsView ws;
+    ws_carve(const_cast<void*>(workspace), n_ue, used_paths(prm, n_paths_loaded), &ws);
+    return launch_spectrum(*prm, ws, user_begin, user_count, snr_linear, out_gamma, out_rate, out_rate_k, (hipStream_t)stream);
+}
+
 int dmx_channels_td(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                     int64_t user_begin, int64_t user_count, void* out_c64, void* stream) {
     WsView ws;

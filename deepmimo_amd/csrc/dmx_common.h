@@ -159,6 +159,8 @@ size_t rate_lds_bytes(const dmx_params& prm, int P);
 int rate_waves_per_block(const dmx_params& prm, int P);
 int launch_rate(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, double snr_linear,
                 float* out_rate, float* out_rate_k, hipStream_t stream);
+int launch_spectrum(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, double snr_linear,
+                    float* out_gamma, float* out_rate, float* out_rate_k, hipStream_t stream);
 
 // between the stage-2 files: the kernels variant 0 chooses from (k2_channel_fd.hip), their predicates and launchers
 bool fd_mfma_preferred(const dmx_params& prm, const WsView& ws);

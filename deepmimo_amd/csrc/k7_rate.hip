@@ -17,9 +17,28 @@
 //   4  unrolled elimination of I + G (the kernel is templated on m): every pivot is >= 1 in exact arithmetic and is clamped
 //      to that, rate_k = sum log2(pivot); rate_k is stored coalesced if wanted; the lane sums its chunks in chunk order, the
 //      wave adds the lanes in a fixed xor tree
+//   4' the second epilogue on the same body (the kernel is templated on it; dmx_channel_spectrum): w carries sqrt(snr), so G
+//      holds mode SNRs (order 1 .. 1e6, not raw gains near 1e-15); a cyclic complex Jacobi iteration on the upper triangle
+//      in registers leaves the eigenvalues gamma_i = snr lambda_i(H_k H_k^H) on the diagonal - pair (p, q): phase of G_pq,
+//      tau = (G_qq - G_pp) / (2 |G_pq|), t = sign(tau) / (|tau| + sqrt(1 + tau^2)), branch-free with t = 0 where
+//      |G_pq| = 0, no eigenvectors - clamped to >= 0, sorted descending by a compile-time odd-even transposition network,
+//      then the water-filling rate in closed form (at most m steps).  gamma is stored m consecutive floats per lane.
+//      The sweep count is fixed per m, the same for every lane, with no data-dependent exit:
+//          m       1  2  3  4  5  6  7  8
+//          needed  0  1  4  5  5  6  7  7
+//          SWEEPS  0  2  5  6  6  7  8  8
+//      "needed": the smallest count after which a float32 NumPy restatement of jacobi_sweep (tests/_spectrum_ref.py,
+//      jacobi_f32) leaves the off-diagonal Frobenius norm <= 2^-24 |G|_F on 2403 hard synthetic matrices per m (rank one,
+//      two equal eigenvalues, clustered values, a 1e6 spread, diagonal, equal diagonals, Wishart) and on the Grams of every
+//      GPU test case; SWEEPS is that plus one sweep of margin.  tests/test_spectrum_cpu.py holds the table to the model.
+//      A non-zero eigenvalue repeated three times or more stalls that norm at about 40 * 2^-24 |G|_F (the diagonal
+//      differences inside the cluster sit at the float32 spacing of the eigenvalue); the eigenvalues do not move.
 // fp32 vector arithmetic, no atomics, every sum in a fixed order that does not depend on where the user sits in the launch.
 // LDS of one wave: (m + M_big + kc) * P * 8 bytes, P = min(num_paths, loaded paths) <= 32; rate_lds_bytes has the rule.
-// Bound: fp32 VALU issue of phase 3 (M_big * P * (1 + m) complex products per subcarrier), far below HBM.
+// Bound: fp32 VALU issue of phase 3 (M_big * P * (1 + m) complex products per subcarrier), far below HBM.  The Jacobi
+// epilogue adds SWEEPS * m (m - 1) / 2 rotations of about 16 (m - 2) + 40 flops per subcarrier (3e4 at m = 8), a few per
+// cent of phase 3 by flops unless M_big is tiny; measured on an MI355X it is 24 % at the headline shape (m = 4, M_big = 256),
+// the divisions and square roots of a rotation being dependent chains with one wave per SIMD to hide them.
 #include "dmx_common.h"
 #include "k2_small_body.h"
 #include <math.h>
@@ -34,13 +53,114 @@ struct RateArgs {
     int S, log2_S;       // slices of the large array per subcarrier (1 unless K < 64)
     const int32_t* sc;
     double inv_n;
-    float scale;         // sqrt(snr / M_tx)
+    float scale;         // sqrt(snr / M_tx), or sqrt(snr) for the spectrum
     float inv_k;
     int ld;              // table row stride in path slots (= P)
 };
 
+// 4  pivots of I + G by elimination on the upper triangle, each clamped to >= 1: log2 det(I + G)
 template <int M>
-__global__ __launch_bounds__(256) void k7_rate(WsView ws, RateArgs a, float* __restrict__ out_rate, float* __restrict__ out_rate_k) {
+__device__ __forceinline__ float epilogue_logdet(float (&gr)[M * M], float (&gi)[M * M]) {
+    float lg = 0.f;
+#pragma unroll
+    for (int p = 0; p < M; ++p) {
+        const float d = fmaxf(gr[p * M + p] + (p == 0 ? 1.f : 0.f), 1.f);
+        lg += log2f(d);
+        const float inv = 1.f / d;
+#pragma unroll
+        for (int i = p + 1; i < M; ++i) {
+            const float er = gr[p * M + i] * inv, ei = -gi[p * M + i] * inv;         // conj(A_pi) / d
+#pragma unroll
+            for (int j = i; j < M; ++j) {
+                const float xr = gr[p * M + j], xi = gi[p * M + j];
+                gr[i * M + j] -= fmaf(er, xr, -(ei * xi));
+                if (j > i) gi[i * M + j] -= fmaf(er, xi, ei * xr);
+            }
+            if (p == 0) gr[i * M + i] += 1.f;                            // the identity, once per diagonal entry
+        }
+    }
+    return lg;
+}
+
+// One cyclic sweep of the complex Jacobi iteration on the upper triangle (G_kp with k > p is conj of the stored G_pk): the
+// pair (p, q) is rotated to G_pq = 0 by the phase e of G_pq and the angle of t.  Branch-free: t = 0 where |G_pq| = 0, and
+// the NaN of 0 * inf on that path is dropped by the selects.
+template <int M>
+__device__ __forceinline__ void jacobi_sweep(float (&gr)[M * M], float (&gi)[M * M]) {
+#pragma unroll
+    for (int p = 0; p < M - 1; ++p) {
+#pragma unroll
+        for (int q = p + 1; q < M; ++q) {
+            const float ga = gr[p * M + q], gb = gi[p * M + q];
+            const float ag = sqrtf(fmaf(ga, ga, gb * gb));
+            const bool nz = ag > 0.f;
+            const float inv = 1.f / ag;
+            const float er = nz ? ga * inv : 1.f, ei = nz ? gb * inv : 0.f;
+            const float dp = gr[p * M + p], dq = gr[q * M + q];
+            const float tau = (dq - dp) * (0.5f * inv);
+            float t = copysignf(1.f, tau) / (fabsf(tau) + sqrtf(fmaf(tau, tau, 1.f)));
+            t = nz ? t : 0.f;
+            const float c = 1.f / sqrtf(fmaf(t, t, 1.f)), s = t * c;
+            gr[p * M + p] = fmaf(-t, ag, dp);
+            gr[q * M + q] = fmaf(t, ag, dq);
+            gr[p * M + q] = 0.f; gi[p * M + q] = 0.f;
+#pragma unroll
+            for (int k = 0; k < M; ++k) {
+                if (k == p || k == q) continue;
+                const int ip = k < p ? k * M + p : p * M + k, iq = k < q ? k * M + q : q * M + k;
+                const float sp = k < p ? 1.f : -1.f, sq = k < q ? 1.f : -1.f;
+                const float xr = gr[ip], xi = sp * gi[ip], zr = gr[iq], zi = sq * gi[iq];
+                const float yr = fmaf(zr, er, zi * ei), yi = fmaf(zi, er, -(zr * ei));      // y = G_kq conj(e)
+                gr[ip] = fmaf(c, xr, -(s * yr)); gi[ip] = sp * fmaf(c, xi, -(s * yi));      // G_kp = c x - s y
+                gr[iq] = fmaf(s, xr, c * yr);    gi[iq] = sq * fmaf(s, xi, c * yi);         // G_kq = s x + c y
+            }
+        }
+    }
+}
+
+// 4' eigenvalues of G (mode SNRs: w carries sqrt(snr)) by SWEEPS[M] cyclic Jacobi sweeps, clamped to 0 .. FLT_MAX and sorted
+//    descending into d, and the water-filling rate under unit total power from them:
+//      rate_k = sum_{i < a} log2(mu d_i),  mu = (1 + sum_{i < a} 1 / d_i) / a,  a the largest count with mu > 1 / d_{a-1}
+//    Modes <= 1e-30 take no power (1 / d stays finite); mu d_i is >= 1 in exact arithmetic and clamped to 1 .. FLT_MAX.
+template <int M>
+__device__ __forceinline__ float epilogue_spectrum(float (&gr)[M * M], float (&gi)[M * M], float (&d)[M]) {
+    constexpr int SWEEPS[9] = {0, 0, 2, 5, 6, 6, 7, 8, 8};
+#pragma unroll 1
+    for (int sw = 0; sw < SWEEPS[M]; ++sw) jacobi_sweep<M>(gr, gi);
+#pragma unroll
+    for (int i = 0; i < M; ++i) d[i] = fminf(fmaxf(gr[i * M + i], 0.f), 3.402823466e38f);
+#pragma unroll
+    for (int r = 0; r < M; ++r) {                                            // odd-even transposition network
+#pragma unroll
+        for (int i = r & 1; i + 1 < M; i += 2) {
+            const float hi = fmaxf(d[i], d[i + 1]), lo = fminf(d[i], d[i + 1]);
+            d[i] = hi; d[i + 1] = lo;
+        }
+    }
+    float sinv = 0.f, mu = 1.f;
+    int cnt = 0;
+    bool alive = true;
+#pragma unroll
+    for (int a = 1; a <= M; ++a) {
+        const float g = d[a - 1];
+        const bool pos = g > 1e-30f;
+        const float inv = 1.f / (pos ? g : 1.f);
+        const float sa = sinv + inv, mua = (1.f + sa) / (float)a;
+        alive = alive && pos && mua > inv;
+        sinv = alive ? sa : sinv; mu = alive ? mua : mu; cnt += alive ? 1 : 0;
+    }
+    float rk = 0.f;
+#pragma unroll
+    for (int i = 0; i < M; ++i) rk += i < cnt ? log2f(fminf(fmaxf(mu * d[i], 1.f), 3.402823466e38f)) : 0.f;
+    return rk;
+}
+
+enum { EPI_LOGDET = 0, EPI_SPECTRUM = 1 };
+
+// EPI_LOGDET: out_rate is written, out_rate_k may be NULL, out_gamma is not used.  EPI_SPECTRUM: each output may be NULL.
+template <int M, int EPI>
+__global__ __launch_bounds__(256) void k7_rate(WsView ws, RateArgs a, float* __restrict__ out_rate, float* __restrict__ out_rate_k,
+                                               float* __restrict__ out_gamma) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
     const int64_t ul = (int64_t)blockIdx.x * wpb + wave;
@@ -52,11 +172,13 @@ __global__ __launch_bounds__(256) void k7_rate(WsView ws, RateArgs a, float* __r
     float2* w = ab + (size_t)Mb * ld;                                                // [ld][kc]
     const int64_t u = a.user_begin + ul;
     float* ok = out_rate_k ? out_rate_k + (size_t)ul * K : nullptr;
+    float* og = EPI == EPI_SPECTRUM && out_gamma ? out_gamma + (size_t)ul * K * M : nullptr;   // [K][M]
     int n = __builtin_amdgcn_readfirstlane(ws.n_keep[u]);
     n = n < ld ? n : ld;
     if (n <= 0) {                                                            // no kept path: +0.0 everywhere
         if (ok) for (int i = lane; i < K; i += 64) ok[i] = 0.f;
-        if (lane == 0) out_rate[ul] = 0.f;
+        if (og) for (int i = lane; i < K * M; i += 64) og[i] = 0.f;
+        if (lane == 0 && out_rate) out_rate[ul] = 0.f;
         return;
     }
     const WsRecords rec{ws, (size_t)u * ws.P};
@@ -154,23 +276,16 @@ __global__ __launch_bounds__(256) void k7_rate(WsView ws, RateArgs a, float* __r
             }
         }
 
-        // 4  pivots of I + G by elimination on the upper triangle, each clamped to >= 1
-        float lg = 0.f;
+        // 4  the epilogue on the upper triangle: log2 det(I + G), or the eigenvalues of G and the water-filling rate
+        float lg;
+        if constexpr (EPI == EPI_LOGDET) {
+            lg = epilogue_logdet<M>(gr, gi);
+        } else {
+            float d[M];
+            lg = epilogue_spectrum<M>(gr, gi, d);
+            if (og && active && sl == 0) {                                   // M consecutive floats per lane, lanes in k order
 #pragma unroll
-        for (int p = 0; p < M; ++p) {
-            const float d = fmaxf(gr[p * M + p] + (p == 0 ? 1.f : 0.f), 1.f);
-            lg += log2f(d);
-            const float inv = 1.f / d;
-#pragma unroll
-            for (int i = p + 1; i < M; ++i) {
-                const float er = gr[p * M + i] * inv, ei = -gi[p * M + i] * inv;         // conj(A_pi) / d
-#pragma unroll
-                for (int j = i; j < M; ++j) {
-                    const float xr = gr[p * M + j], xi = gi[p * M + j];
-                    gr[i * M + j] -= fmaf(er, xr, -(ei * xi));
-                    if (j > i) gi[i * M + j] -= fmaf(er, xi, ei * xr);
-                }
-                if (p == 0) gr[i * M + i] += 1.f;                            // the identity, once per diagonal entry
+                for (int i = 0; i < M; ++i) og[(size_t)(k0 + kl) * M + i] = d[i];
             }
         }
         if (active && sl == 0) {
@@ -179,7 +294,7 @@ __global__ __launch_bounds__(256) void k7_rate(WsView ws, RateArgs a, float* __r
         }
     }
     for (int d = 1; d < 64; d <<= 1) rate_sum += __shfl_xor(rate_sum, d, 64);
-    if (lane == 0) out_rate[ul] = rate_sum * a.inv_k;
+    if (lane == 0 && out_rate) out_rate[ul] = rate_sum * a.inv_k;
 }
 
 // LDS bytes of one wave for P path slots (0: the shape is not taken): both array tables and one chunk of w,
@@ -196,14 +311,17 @@ size_t rate_lds_bytes(const dmx_params& prm, int P) {
 
 int rate_waves_per_block(const dmx_params& prm, int P) { return lds_waves_per_block(rate_lds_bytes(prm, P)); }
 
-template <int M>
+template <int M, int EPI>
 static int launch_rate_m(const dim3 g, const dim3 b, size_t smem, hipStream_t stream, const WsView& ws, const RateArgs& a,
-                         float* out_rate, float* out_rate_k) {
-    return launch_dyn_lds(k7_rate<M>, "k7_rate", g, b, smem, WAVE_LDS_MAX, stream, ws, a, out_rate, out_rate_k);
+                         float* out_rate, float* out_rate_k, float* out_gamma) {
+    return launch_dyn_lds(k7_rate<M, EPI>, EPI == EPI_LOGDET ? "k7_rate" : "k7_rate (spectrum)", g, b, smem, WAVE_LDS_MAX, stream,
+                          ws, a, out_rate, out_rate_k, out_gamma);
 }
 
-int launch_rate(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, double snr_linear,
-                float* out_rate, float* out_rate_k, hipStream_t stream) {
+// scale: what the path coefficients are multiplied by, sqrt(snr / M_tx) for the determinant and sqrt(snr) for the spectrum
+template <int EPI>
+static int launch_rate_epi(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, float scale,
+                           float* out_rate, float* out_rate_k, float* out_gamma, hipStream_t stream) {
     const int wpb = rate_waves_per_block(prm, ws.P);
     if (!wpb) { set_error("rate kernel: tables of one user do not fit the LDS"); return DMX_ERR_SHAPE; }
     const int m_tx = prm.bs_shape[0] * prm.bs_shape[1], m_rx = prm.ue_shape[0] * prm.ue_shape[1];
@@ -221,21 +339,34 @@ int launch_rate(const dmx_params& prm, const WsView& ws, int64_t user_begin, int
     a.S = 1 << a.log2_S;
     a.sc = prm.selected_subcarriers;
     a.inv_n = 1.0 / (double)prm.n_subcarriers;
-    a.scale = (float)sqrt(snr_linear / (double)m_tx);
+    a.scale = scale;
     a.inv_k = (float)(1.0 / (double)a.K);
     a.ld = ws.P;
     const size_t smem = (size_t)wpb * rate_lds_bytes(prm, ws.P);
     const dim3 g((unsigned)((user_count + wpb - 1) / wpb)), b(64 * wpb);    // flat: one wave per user
     switch (m) {
-        case 1: return launch_rate_m<1>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
-        case 2: return launch_rate_m<2>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
-        case 3: return launch_rate_m<3>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
-        case 4: return launch_rate_m<4>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
-        case 5: return launch_rate_m<5>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
-        case 6: return launch_rate_m<6>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
-        case 7: return launch_rate_m<7>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
-        default: return launch_rate_m<8>(g, b, smem, stream, ws, a, out_rate, out_rate_k);
+        case 1: return launch_rate_m<1, EPI>(g, b, smem, stream, ws, a, out_rate, out_rate_k, out_gamma);
+        case 2: return launch_rate_m<2, EPI>(g, b, smem, stream, ws, a, out_rate, out_rate_k, out_gamma);
+        case 3: return launch_rate_m<3, EPI>(g, b, smem, stream, ws, a, out_rate, out_rate_k, out_gamma);
+        case 4: return launch_rate_m<4, EPI>(g, b, smem, stream, ws, a, out_rate, out_rate_k, out_gamma);
+        case 5: return launch_rate_m<5, EPI>(g, b, smem, stream, ws, a, out_rate, out_rate_k, out_gamma);
+        case 6: return launch_rate_m<6, EPI>(g, b, smem, stream, ws, a, out_rate, out_rate_k, out_gamma);
+        case 7: return launch_rate_m<7, EPI>(g, b, smem, stream, ws, a, out_rate, out_rate_k, out_gamma);
+        default: return launch_rate_m<8, EPI>(g, b, smem, stream, ws, a, out_rate, out_rate_k, out_gamma);
     }
+}
+
+int launch_rate(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, double snr_linear,
+                float* out_rate, float* out_rate_k, hipStream_t stream) {
+    const int m_tx = prm.bs_shape[0] * prm.bs_shape[1];
+    return launch_rate_epi<EPI_LOGDET>(prm, ws, user_begin, user_count, (float)sqrt(snr_linear / (double)m_tx), out_rate,
+                                       out_rate_k, nullptr, stream);
+}
+
+int launch_spectrum(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, double snr_linear,
+                    float* out_gamma, float* out_rate, float* out_rate_k, hipStream_t stream) {
+    return launch_rate_epi<EPI_SPECTRUM>(prm, ws, user_begin, user_count, (float)sqrt(snr_linear), out_rate, out_rate_k,
+                                         out_gamma, stream);
 }
 
 }  // namespace dmx

@@ -415,33 +415,75 @@ class Dataset(DotDict):
         R = eng.covariance(prep, side=side)
         return R if config.get("channel_output", "numpy") == "torch" else R.cpu().numpy()
 
-    def compute_rate(self, params: Optional[ChannelGenParameters] = None, *, snr_db=None, per_subcarrier: bool = False):
+    def compute_rate(self, params: Optional[ChannelGenParameters] = None, *, snr_db=None, per_subcarrier: bool = False,
+                     power_allocation: str = "equal"):
         """Per-user achievable rate (spectral efficiency) in bit/s/Hz, with no channel tensor written anywhere
-        (extension) - equal power on every BS antenna, no channel knowledge at the transmitter:
+        (extension).  ``power_allocation="equal"`` (the default) - equal power on every BS antenna, no
+        channel knowledge at the transmitter:
 
             s = 10 ** (snr_db / 10) / M_tx            # snr_db: total transmit power over noise power per subcarrier
             rate_k[u, k] = log2 det(I + s * H[u, :, :, k] @ H[u, :, :, k].conj().T)
             rate[u]      = rate_k[u].mean()
+
+        ``power_allocation="waterfilling"`` - full channel knowledge at the transmitter, the same total power poured over
+        the eigenmodes of each subcarrier (``compute_eigenmodes`` has them), never below the equal-power rate:
+
+            g = 10 ** (snr_db / 10) * eigvalsh(H[u, :, :, k] @ H[u, :, :, k].conj().T)
+            rate_k[u, k] = max over p >= 0, p.sum() == 1 of log2(1 + p * g).sum()
 
         Returns float32 [n_ue] (with ``per_subcarrier`` the pair ``(rate, rate_k)``, rate_k float32 [n_ue, K]): NumPy arrays
         by default, the HBM-resident torch tensors when ``config('channel_output') == 'torch'``.  ``snr_db`` is required
         and keyword-only.  Users without a path get 0.  Frequency domain without ``rx_filter``, at most 32 used paths, the smaller array of at most 8 elements, tables
         within the LDS (include/deepmimo_amd.h has the rule): anything else raises ValueError before any GPU work.  Not
         cached."""
-        from .engine import check_rate_call, snr_linear_from_db
+        from .engine import check_rate_call, check_spectrum_call, snr_linear_from_db
+        if power_allocation not in ("equal", "waterfilling"):
+            raise ValueError(f"compute_rate: power_allocation must be 'equal' or 'waterfilling', got {power_allocation!r}")
         if snr_db is None:
             raise ValueError("compute_rate: snr_db (dB, keyword) is required")
         snr_linear_from_db(snr_db)
         if params is None:
             params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
         self.set_channel_params(params)
-        check_rate_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), snr_db)
+        n_loaded = int(np.shape(self[c.POWER_PARAM_NAME])[1])
+        if power_allocation == "equal":
+            check_rate_call(params, n_loaded, snr_db)
+        else:
+            check_spectrum_call(params, n_loaded, snr_db)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
-        res = eng.rate(prep, snr_db, per_subcarrier=per_subcarrier)
+        if power_allocation == "equal":
+            res = eng.rate(prep, snr_db, per_subcarrier=per_subcarrier)
+        else:
+            res = eng.spectrum(prep, snr_db, gamma=False, rate=True, per_subcarrier=per_subcarrier)
         if config.get("channel_output", "numpy") == "torch":
             return res
         return tuple(t.cpu().numpy() for t in res) if per_subcarrier else res.cpu().numpy()
+
+    def compute_eigenmodes(self, params: Optional[ChannelGenParameters] = None, *, snr_db=None):
+        """Eigenmodes of every user's channel per subcarrier, with no channel tensor written anywhere (extension;
+        SURVEY.md 8(f)-2): the mode SNRs, sorted descending along the last axis, m = min(M_rx, M_tx):
+
+            gamma[u, k] = 10 ** (snr_db / 10) * eigvalsh(H[u, :, :, k] @ H[u, :, :, k].conj().T)[::-1][:m]
+
+        ``gamma / snr`` is the eigenvalue and its square root the singular value of ``H[u, :, :, k]``; the rank is the
+        count of modes above a threshold and the condition number the ratio of the first to the last.  Returns float32
+        [n_ue, K, m]: a NumPy array by default, the HBM-resident torch tensor when ``config('channel_output') == 'torch'``.
+        ``snr_db`` (total transmit power over noise power per subcarrier) is required and keyword-only.  Users without a
+        path get 0.  The shapes taken are those of ``compute_rate``; anything else raises ValueError before any GPU work.
+        Not cached."""
+        from .engine import check_spectrum_call, snr_linear_from_db
+        if snr_db is None:
+            raise ValueError("compute_eigenmodes: snr_db (dB, keyword) is required")
+        snr_linear_from_db(snr_db)
+        if params is None:
+            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
+        self.set_channel_params(params)
+        check_spectrum_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), snr_db)
+        np.random.seed(1001)
+        eng, prep = self._run_prep(want_side="light")
+        g = eng.spectrum(prep, snr_db)
+        return g if config.get("channel_output", "numpy") == "torch" else g.cpu().numpy()
 
     def compute_pathloss(self, coherent: bool = True) -> np.ndarray:
         """Path loss in dB assuming 0 dBm transmitted power (dataset.py:541-566); cached as ``pathloss``."""

@@ -11,6 +11,7 @@ include/deepmimo_amd.h and calls the C-ABI:
     dmx_channels_td -> complex64 [N, M_rx, M_tx, P]
     dmx_channel_covariance -> complex64 [N, M, M]       (per-user spatial covariance, no channel tensor)
     dmx_channel_rate     -> float32 [N] (and [N, K])    (per-user achievable rate, no channel tensor)
+    dmx_channel_spectrum -> float32 [N, K, m], [N], [N, K]  (eigenmode SNRs and water-filling rate, no channel tensor)
 
 It replaces the body of Dataset.compute_channels (deepmimo/generator/dataset.py:224-268).
 No CPU path exists here: without the shared library or without a GPU every entry point raises.
@@ -234,6 +235,27 @@ def check_rate_call(params, n_paths_loaded: int, snr_db) -> float:
     rc = lib.dmx_rate_supported(C.byref(p), int(n_paths_loaded))
     if rc != 1:
         raise ValueError("rate: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
+    return snr
+
+
+def check_spectrum_call(params, n_paths_loaded: int, snr_db) -> float:
+    """`check_rate_call` for `Dataset.compute_eigenmodes` and the water-filling rate: the same refusals (the spectrum call
+    takes exactly the shapes of the rate), asked of dmx_spectrum_supported.  Returns the linear SNR."""
+    snr = snr_linear_from_db(snr_db)
+    ofdm = params[c.PARAMSET_OFDM]
+    if not params[c.PARAMSET_FD_CH]:
+        raise ValueError("spectrum: needs the frequency-domain channel (freq_domain = 1)")
+    if ofdm[c.PARAMSET_OFDM_LPF]:
+        raise ValueError("spectrum: ofdm.rx_filter = 1 is not covered")
+    sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
+    p = nat.DmxParams()
+    _fill_shape_fields(p, params, sel.size)
+    host_sel = (C.c_int32 * max(1, int(sel.size)))()          # the query reads the count, never the array
+    p.selected_subcarriers = C.addressof(host_sel)
+    lib = nat.load()
+    rc = lib.dmx_spectrum_supported(C.byref(p), int(n_paths_loaded))
+    if rc != 1:
+        raise ValueError("spectrum: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
     return snr
 
 
@@ -730,6 +752,47 @@ class ChannelEngine:
                                            self._stream_ptr())
         nat.check(rc, "dmx_channel_rate")
         return (r, rk) if per_subcarrier else r
+
+    def spectrum_supported(self, prep: PrepResult) -> bool:
+        """dmx_spectrum_supported for this preparation (host-only query; `spectrum` raises where it says no)."""
+        rc = self.lib.dmx_spectrum_supported(C.byref(prep.params_struct), prep.n_paths_loaded)
+        if rc < 0:
+            nat.check(rc, "dmx_spectrum_supported")
+        return rc == 1
+
+    def spectrum(self, prep: PrepResult, snr_db, user_begin: int = 0, user_count: Optional[int] = None,
+                 gamma: bool = True, rate: bool = False, per_subcarrier: bool = False, out=None):
+        """dmx_channel_spectrum: the eigenmodes of every subcarrier's channel and the water-filling rate at `snr_db` (total
+        transmit power over noise power per subcarrier), from the per-path records of `prep` - the channel tensor is not
+        written.  `gamma`: float32 [user_count, K, m] mode SNRs snr * eig(H_k H_k^H), descending, m = min(M_rx, M_tx);
+        `rate`: float32 [user_count], the mean over k of the water-filling rate in bit/s/Hz; `per_subcarrier`: float32
+        [user_count, K].  Returns the requested tensors in that order, HBM-resident - a single tensor when one is asked
+        for, else a tuple.  `out`: the tensor (or the tuple of tensors, in the same order) to write into."""
+        snr = snr_linear_from_db(snr_db)
+        if not (gamma or rate or per_subcarrier):
+            raise ValueError("spectrum: at least one of gamma, rate and per_subcarrier must be asked for")
+        p = prep.params_struct
+        if user_count is None:
+            user_count = prep.n_ue - user_begin
+        K, m = int(p.n_selected), min(p.bs_shape[0] * p.bs_shape[1], p.ue_shape[0] * p.ue_shape[1])
+        shapes = [sh for want, sh in ((gamma, (user_count, K, m)), (rate, (user_count,)), (per_subcarrier, (user_count, K))) if want]
+        given = list(out) if isinstance(out, (tuple, list)) else [out] * (out is not None)
+        if out is not None and len(given) != len(shapes):
+            raise ValueError(f"out must hold {len(shapes)} tensors, one per requested output")
+        res = []
+        for i, shape in enumerate(shapes):
+            t = given[i] if given else torch.empty(shape, dtype=torch.float32, device=self.device)
+            if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+                raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
+            res.append(t)
+        it = iter(res)
+        ptr = [C.c_void_p(next(it).data_ptr()) if want else None for want in (gamma, rate, per_subcarrier)]
+        with torch.cuda.device(self.device):
+            rc = self.lib.dmx_channel_spectrum(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
+                                               prep.n_paths_loaded, int(user_begin), int(user_count), snr,
+                                               ptr[0], ptr[1], ptr[2], self._stream_ptr())
+        nat.check(rc, "dmx_channel_spectrum")
+        return res[0] if len(res) == 1 else tuple(res)
 
     def pathloss(self, rays: DeviceRays, coherent: bool = True) -> torch.Tensor:
         """dmx_pathloss: float32 [n_ue] dB (dataset.py:541-566)."""

@@ -299,6 +299,39 @@ int dmx_channel_rate(const dmx_params* prm, const void* workspace, int64_t n_ue,
                      void* stream);
 
 /*
+ * Fused consumer, the closed-loop view of the same Gram: the eigenmodes of every subcarrier's channel and the rate with full
+ * channel knowledge at the transmitter (water-filling over the modes of a subcarrier), H never written.  H_k and snr_linear
+ * as in dmx_channel_rate, m = min(M_rx, M_tx):
+ *   gamma[u, k, i] = snr_linear * lambda_i(H_k H_k^H),  i = 0 .. m-1, sorted descending     out_gamma  float32 [user_count, K, m]
+ *                    (the mode SNRs: gamma / snr_linear is the eigenvalue, its square root the singular value of H_k)
+ *   rate_k[u, k]   = max over p_i >= 0, sum_i p_i = 1 of sum_i log2(1 + p_i gamma_i)         out_rate_k float32 [user_count, K]
+ *                  = sum_{i < a} log2(mu gamma_i),  mu = (1 + sum_{i < a} 1 / gamma_i) / a,
+ *                    a the largest count of strongest modes with mu > 1 / gamma_{a-1}; modes with gamma_i = 0 take no power
+ *   rate[u]        = 1 / K sum_k rate_k[u, k]                                                out_rate   float32 [user_count]
+ * Each of the three outputs may be NULL (not all of them).  Both rates spend the same total power ((snr / M_tx) I has trace
+ * snr), so this rate_k is never below dmx_channel_rate's, and for m = 1 it is log2(1 + gamma_0).  Every value is finite and
+ * >= 0 (gamma is clamped to 0 .. FLT_MAX; modes below 1e-30 count as zero); a user without kept paths gets +0.0 everywhere.
+ * The kernel is dmx_channel_rate's with another epilogue: the path coefficients are scaled by sqrt(snr_linear), so the Gram
+ * holds mode SNRs, and a cyclic complex Jacobi iteration with a fixed sweep count (m = 1 .. 8: 0, 2, 5, 6, 6, 7, 8, 8; no
+ * data-dependent exit) diagonalises it in registers.  Launches repeat bit for bit, a user sub-range equals the same rows of
+ * a whole launch, and a launch with fewer outputs writes the same bits.
+ * Accuracy: the sweep counts leave the off-diagonal Frobenius norm <= 2^-24 |G|_F except where a non-zero eigenvalue is
+ * repeated three times or more; there only the eigenvalue bound holds (every gamma within c_J 2^-24 |G|_F, c_J = 13 * sweeps *
+ * m (m - 1) / 2), the off-diagonal one does not.  Usable range: the rotation squares the off-diagonal entries in float32,
+ * so mode SNRs (entries of snr_linear * H_k H_k^H) are diagonalised between about 3e-23 and 1.8e19; smaller off-diagonal
+ * entries are treated as zero, larger ones overflow and gamma, still finite and >= 0, is then meaningless.
+ *
+ * dmx_spectrum_supported - the rule of dmx_rate_supported, unchanged.
+ * dmx_channel_spectrum - the argument rules of dmx_channel_rate; all three outputs NULL with user_count > 0: DMX_ERR_ARG.
+ */
+int dmx_spectrum_supported(const dmx_params* prm, int32_t n_paths_loaded);
+int dmx_channel_spectrum(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
+                         int64_t user_begin, int64_t user_count, double snr_linear,
+                         float* out_gamma   /* [user_count, K, m] or NULL */,
+                         float* out_rate    /* [user_count]       or NULL */,
+                         float* out_rate_k  /* [user_count, K]    or NULL */, void* stream);
+
+/*
  * Stage 2, time domain (replaces channel.py:285-287): out[u, rx, tx, s] = a_rx a_tx sqrt(p) e^{j phase}
  * of the s-th valid path (valid paths compacted to the front, remaining slots zero),
  * complex64 [user_count, M_rx, M_tx, P], P = min(num_paths, n_paths_loaded).

@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
-"""Per-user achievable rate: the fused route against the channel tensor + torch.linalg.slogdet, alternating in ONE process:
-`python tools/rate_bench.py [--out profiles/r6_rate_bench.jsonl]`.
+"""Per-user achievable rate and channel eigenmodes: the fused routes against the channel tensor + torch.linalg, alternating in
+ONE process: `python tools/rate_bench.py [--out profiles/r6_rate_bench.jsonl]`.
 
 For each shape, on the same uploaded rays:
-  (a) fused    dmx_path_prep + dmx_channel_rate                                  (no channel tensor)
-  (b) slogdet  dmx_path_prep + per user chunk: dmx_channels_fd (variant 0) into a resident tensor, the Gram over the smaller
-               array by torch.einsum, torch.linalg.slogdet of I + s G, the mean over the subcarriers
+  (a) fused     dmx_path_prep + dmx_channel_rate                                 (no channel tensor)
+  (b) slogdet   dmx_path_prep + per user chunk: dmx_channels_fd (variant 0) into a resident tensor, the Gram over the smaller
+                array by torch.einsum, torch.linalg.slogdet of I + s G, the mean over the subcarriers
+  (c) spectrum  dmx_path_prep + dmx_channel_spectrum, the water-filling rate only: (a)'s kernel with the Jacobi epilogue
+  (d) modes     dmx_path_prep + dmx_channel_spectrum, the mode SNRs [n, K, m] only
+  (e) eigvalsh  (d)'s unfused twin: (b)'s channel chunks and Gram, torch.linalg.eigvalsh of snr G, descending.  The batched
+                solver takes seconds for 1e5 small matrices, so this route runs on the first `--eig-users` users only, one
+                launch per timing; its time is reported for that count and `modes_speedup_per_user` compares time per user,
+                an extrapolation and not a like-for-like run
 Device events around back-to-back launches of one route, the routes alternating `--rounds` times after a warm-up; the
 whole A/B runs twice (`pass` 0 and 1) and the difference between the two passes of the SAME route is the spread a
 difference between the routes has to exceed.  One JSON line per shape: mean, minimum and spread of both routes, the fused
@@ -53,6 +59,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=2, help="timings per route and pass: 2 passes x rounds x launches launches in all")
     ap.add_argument("--shapes", default=",".join(s[0] for s in SHAPES))
     ap.add_argument("--scale", type=float, default=1.0, help="multiply every user count (rehearsals)")
+    ap.add_argument("--eig-users", type=int, default=200, help="users of route (e)")
+    ap.add_argument("--routes", default="fused,slogdet,spectrum,modes,eigvalsh")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     eng = ChannelEngine(0)
@@ -78,6 +86,11 @@ def main():
         wsp = C.c_void_p(prep.workspace.data_ptr())
         r_fused = torch.empty((n,), dtype=torch.float32, device=eng.device)
         r_ref = torch.empty((n,), dtype=torch.float32, device=eng.device)
+        r_wf = torch.empty((n,), dtype=torch.float32, device=eng.device)
+        n_eig = min(n, max(1, args.eig_users))
+        want = args.routes.split(",")
+        g_fused = torch.empty((n, K, m), dtype=torch.float32, device=eng.device) if "modes" in want else None
+        g_ref = torch.empty((n_eig, K, m), dtype=torch.float32, device=eng.device) if "eigvalsh" in want else None
         eye = torch.eye(m, dtype=torch.complex64, device=eng.device)
         spec = "uitk,ujtk->ukij" if m_rx <= m_tx else "urjk,urik->ukij"
         s = snr / m_tx
@@ -95,7 +108,26 @@ def main():
                 G = torch.einsum(spec, H[:cnt], H[:cnt].conj())
                 r_ref[b:b + cnt] = (torch.linalg.slogdet(eye + s * G)[1] / math.log(2.0)).mean(dim=1)
 
-        routes = [("fused", fused), ("slogdet", slogdet)]
+        def spectrum():
+            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            nat.check(lib.dmx_channel_spectrum(C.byref(ps), wsp, n, L, 0, n, snr, None, C.c_void_p(r_wf.data_ptr()), None, stream),
+                      "dmx_channel_spectrum")
+
+        def modes():
+            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            nat.check(lib.dmx_channel_spectrum(C.byref(ps), wsp, n, L, 0, n, snr, C.c_void_p(g_fused.data_ptr()), None, None, stream),
+                      "dmx_channel_spectrum")
+
+        def eigvalsh():
+            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            for b in range(0, n_eig, chunk):
+                cnt = min(chunk, n_eig - b)
+                nat.check(lib.dmx_channels_fd(C.byref(ps), wsp, n, L, b, cnt, C.c_void_p(H.data_ptr()), 0, stream), "dmx_channels_fd")
+                G = torch.einsum(spec, H[:cnt], H[:cnt].conj())
+                g_ref[b:b + cnt] = torch.linalg.eigvalsh(snr * G).flip(-1).clamp_min(0)   # scaled first: raw gains are near 1e-15
+
+        routes = [r for r in (("fused", fused), ("slogdet", slogdet), ("spectrum", spectrum), ("modes", modes), ("eigvalsh", eigvalsh))
+                  if r[0] in want]
         rec = dict(shape=name, bs=bs, ue=ue, K=K, users=n, paths=L, snr_db=args.snr_db, chunk_users=chunk,
                    H_bytes=n * m_rx * m_tx * K * 8, launches_per_route=2 * args.rounds * args.launches)
         rec["fused_flops"] = n * K * big * (L * (6 + 8 * m) + 8 * m * (m + 1) // 2)
@@ -105,7 +137,7 @@ def main():
             ts = {rn: [] for rn, _ in routes}
             for _ in range(args.rounds):
                 for rn, fn in routes:
-                    ts[rn].append(timed(fn, args.launches))
+                    ts[rn].append(timed(fn, 1 if rn == "eigvalsh" else args.launches))
             for rn, v in ts.items():
                 rec[f"{rn}_avg_ms_pass{ab}"] = round(float(np.mean(v)), 5)
                 rec[f"{rn}_min_ms_pass{ab}"] = round(float(np.min(v)), 5)
@@ -113,10 +145,23 @@ def main():
             a0, a1 = rec[f"{rn}_avg_ms_pass0"], rec[f"{rn}_avg_ms_pass1"]
             rec[f"{rn}_avg_ms"] = round((a0 + a1) / 2, 5)
             rec[f"{rn}_spread_ms"] = round(abs(a0 - a1), 5)
-        rec["speedup"] = round(rec["slogdet_avg_ms"] / rec["fused_avg_ms"], 3)
-        rec["fused_share_of_fp32_valu_peak"] = round(rec["fused_flops"] / (rec["fused_avg_ms"] * 1e-3) / FP32_VALU_PEAK, 4)
-        rec["max_dev_bit"] = float((r_fused - r_ref).abs().max())
-        rec["mean_rate"] = float(r_fused.double().mean())
+        have = {rn for rn, _ in routes}
+        if {"fused", "slogdet"} <= have:
+            rec["speedup"] = round(rec["slogdet_avg_ms"] / rec["fused_avg_ms"], 3)
+            rec["max_dev_bit"] = float((r_fused - r_ref).abs().max())
+        if "fused" in have:
+            rec["fused_share_of_fp32_valu_peak"] = round(rec["fused_flops"] / (rec["fused_avg_ms"] * 1e-3) / FP32_VALU_PEAK, 4)
+            rec["mean_rate"] = float(r_fused.double().mean())
+        if "spectrum" in have:
+            rec["mean_rate_waterfilling"] = float(r_wf.double().mean())
+        if {"fused", "spectrum"} <= have:
+            rec["spectrum_over_fused"] = round(rec["spectrum_avg_ms"] / rec["fused_avg_ms"], 4)
+            rec["waterfilling_below_equal_max_bit"] = float((r_fused - r_wf).clamp_min(0).max())
+        if {"modes", "eigvalsh"} <= have:
+            rec["eigvalsh_users"] = n_eig                                 # route (e) covers these users only; (d) all of them
+            rec["modes_speedup_per_user"] = round((rec["eigvalsh_avg_ms"] / n_eig) / (rec["modes_avg_ms"] / n), 3)
+            top = g_ref[..., 0].clamp_min(1e-30)
+            rec["modes_max_dev_rel_to_strongest"] = float(((g_fused[:n_eig] - g_ref).abs().amax(dim=-1) / top).max())
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
         del H, prep, rays
