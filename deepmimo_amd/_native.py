@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = ("dmx_version", "dmx_last_error", "dmx_workspace_bytes", "dmx
                     "dmx_p2m_count_rx", "dmx_p2m_parse_paths", "dmx_fd_kernel_choice", "dmx_beam_power",
                     "dmx_fd_direct_supported", "dmx_channels_fd_direct", "dmx_covariance_supported",
                     "dmx_channel_covariance", "dmx_rate_supported", "dmx_channel_rate",
-                    "dmx_spectrum_supported", "dmx_channel_spectrum")
+                    "dmx_spectrum_supported", "dmx_channel_spectrum", "dmx_precoder_supported", "dmx_channel_precoders")
 
 PATTERN_IDS = {"isotropic": 0, "halfwave-dipole": 1}
 COV_SIDES = {"tx": 0, "rx": 1}            # DMX_COV_TX / DMX_COV_RX
@@ -117,6 +117,11 @@ def load():
     lib.dmx_channel_spectrum.restype = C.c_int
     lib.dmx_channel_spectrum.argtypes = [C.POINTER(DmxParams), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
                                          C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dmx_precoder_supported.restype = C.c_int
+    lib.dmx_precoder_supported.argtypes = [C.POINTER(DmxParams), C.c_int32, C.c_int32]
+    lib.dmx_channel_precoders.restype = C.c_int
+    lib.dmx_channel_precoders.argtypes = [C.POINTER(DmxParams), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
+                                          C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.dmx_decode_max_delay.restype = C.c_float
     lib.dmx_decode_max_delay.argtypes = [C.c_uint32]
     lib.dmx_path_prep.restype = C.c_int

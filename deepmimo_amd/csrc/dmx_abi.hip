@@ -392,6 +392,53 @@ int dmx_channel_spectrum(const dmx_params* prm, const void* workspace, int64_t n
     return launch_spectrum(*prm, ws, user_begin, user_count, snr_linear, out_gamma, out_rate, out_rate_k, (hipStream_t)stream);
 }
 
+// rate_shape and 1 <= n_layers <= min(M_rx, M_tx)
+static int precoder_shape(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_layers) {
+    const int rc = rate_shape(prm, n_paths_loaded);
+    if (rc != 1) return rc;
+    const int m_tx = prm->bs_shape[0] * prm->bs_shape[1], m_rx = prm->ue_shape[0] * prm->ue_shape[1];
+    const int m = m_rx <= m_tx ? m_rx : m_tx;
+    if (n_layers < 1 || n_layers > m) {
+        set_error("precoders: n_layers = %d is outside 1..min(M_rx, M_tx) = 1..%d", n_layers, m);
+        return 0;
+    }
+    return 1;
+}
+
+int dmx_precoder_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_layers) {
+    int rc = check_params(prm);
+    if (rc) return rc;
+    return precoder_shape(prm, n_paths_loaded, n_layers);
+}
+
+int dmx_channel_precoders(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
+                          int64_t user_begin, int64_t user_count, double snr_linear, int32_t n_layers, float* out_gamma,
+                          void* out_tx_c64, void* out_rx_c64, void* stream) {
+    int rc = check_params(prm);
+    if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
+    if (user_count > 0 && !workspace) { set_error("workspace is NULL"); return DMX_ERR_ARG; }
+    if (user_count > 0 && !out_gamma && !out_tx_c64 && !out_rx_c64) {
+        set_error("dmx_channel_precoders: out_gamma, out_tx_c64 and out_rx_c64 are all NULL"); return DMX_ERR_ARG;
+    }
+    if ((rc = check_workspace_aligned(workspace))) return rc;
+    if (((uintptr_t)out_gamma & 3u) || ((uintptr_t)out_tx_c64 & 7u) || ((uintptr_t)out_rx_c64 & 7u)) {
+        set_error("out_gamma must be 4-byte aligned, out_tx_c64 / out_rx_c64 8-byte aligned"); return DMX_ERR_ARG;
+    }
+    if (!prm->freq_domain) { set_error("dmx_channel_precoders called with freq_domain = 0"); return DMX_ERR_ARG; }
+    if (prm->rx_filter) { set_error("dmx_channel_precoders does not cover rx_filter = 1"); return DMX_ERR_ARG; }
+    if (!(snr_linear >= 1e-70) || !(snr_linear <= 1e70)) {
+        set_error("dmx_channel_precoders: snr_linear must be finite and > 0 (1e-70 .. 1e70), got %g", snr_linear); return DMX_ERR_ARG;
+    }
+    rc = precoder_shape(prm, n_paths_loaded, n_layers);
+    if (rc < 0) return rc;
+    if (rc == 0) return DMX_ERR_SHAPE;
+    if (user_count == 0) return DMX_OK;
+    WsView ws;
+    ws_carve(const_cast<void*>(workspace), n_ue, used_paths(prm, n_paths_loaded), &ws);
+    return launch_precoders(*prm, ws, user_begin, user_count, snr_linear, n_layers, out_gamma, (float2*)out_tx_c64,
+                            (float2*)out_rx_c64, (hipStream_t)stream);
+}
+
 int dmx_channels_td(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                     int64_t user_begin, int64_t user_count, void* out_c64, void* stream) {
     WsView ws;

@@ -161,6 +161,8 @@ int launch_rate(const dmx_params& prm, const WsView& ws, int64_t user_begin, int
                 float* out_rate, float* out_rate_k, hipStream_t stream);
 int launch_spectrum(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, double snr_linear,
                     float* out_gamma, float* out_rate, float* out_rate_k, hipStream_t stream);
+int launch_precoders(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, double snr_linear,
+                     int n_layers, float* out_gamma, float2* out_tx, float2* out_rx, hipStream_t stream);
 
 // between the stage-2 files: the kernels variant 0 chooses from (k2_channel_fd.hip), their predicates and launchers
 bool fd_mfma_preferred(const dmx_params& prm, const WsView& ws);

@@ -485,6 +485,44 @@ class Dataset(DotDict):
         g = eng.spectrum(prep, snr_db)
         return g if config.get("channel_output", "numpy") == "torch" else g.cpu().numpy()
 
+    def compute_precoders(self, params: Optional[ChannelGenParameters] = None, *, snr_db=None, n_layers: int = 1,
+                          combiners: bool = False):
+        """Eigenbeam precoders (and combiners) of every user's channel per subcarrier, with no channel tensor written
+        anywhere (extension).  With ``U, s, Vh = svd(H[u, :, :, k])``, strongest modes first,
+        m = min(M_rx, M_tx) and L = ``n_layers`` in 1..m:
+
+            gamma[u, k]    = 10 ** (snr_db / 10) * s[:m] ** 2           # float32   [n_ue, K, m], as compute_eigenmodes
+            w_tx[u, k, i]  = Vh[i].conj()                               # complex64 [n_ue, K, L, M_tx], unit norm
+            w_rx[u, k, i]  = U[:, i]                                    # complex64 [n_ue, K, L, M_rx], with ``combiners``
+
+        so ``w_rx[u, k, i].conj() @ H[u, :, :, k] @ w_tx[u, k, i]`` is ``s[i]``, real and >= 0.  The phase of a pair is
+        fixed on the smaller array: the component of largest modulus of that vector is real and positive.  A layer whose
+        mode lies below the float32 resolution of the entry (about -45 dB of the sum of the modes at m = 4, -38 dB at
+        m = 8; include/deepmimo_amd.h has the rule), e.g. the second layer of a one-path user, is all zeros, and so is a
+        user without a path.  Returns ``(gamma, w_tx)`` or ``(gamma, w_tx, w_rx)``: NumPy arrays by default, the
+        HBM-resident torch tensors when ``config('channel_output') == 'torch'``.  ``snr_db`` (total transmit power over
+        noise power per subcarrier) is required and keyword-only: it puts the Gram matrix into float32 range and is the
+        unit of ``gamma``; the vectors do not depend on it otherwise.  The shapes taken are those of ``compute_rate``;
+        anything else raises ValueError before any GPU work.  Not cached."""
+        from .engine import check_precoder_call, snr_linear_from_db
+        if snr_db is None:
+            raise ValueError("compute_precoders: snr_db (dB, keyword) is required")
+        snr_linear_from_db(snr_db)
+        if params is None:
+            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
+        self.set_channel_params(params)
+        check_precoder_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), snr_db, n_layers)
+        to_host = config.get("channel_output", "numpy") != "torch"
+        if to_host:
+            n_ant = [int(np.prod(params[k][c.PARAMSET_ANT_SHAPE])) for k in (c.PARAMSET_ANT_BS, c.PARAMSET_ANT_UE)]
+            k_sel = int(np.size(params[c.PARAMSET_OFDM][c.PARAMSET_OFDM_SC_SAMP]))
+            per_entry = 4 * min(n_ant) + 8 * int(n_layers) * (n_ant[0] + (n_ant[1] if combiners else 0))
+            self._guard_host_copy(int(self.n_ue) * k_sel * per_entry)
+        np.random.seed(1001)
+        eng, prep = self._run_prep(want_side="light")
+        res = eng.precoders(prep, snr_db, n_layers=int(n_layers), rx=bool(combiners))
+        return tuple(t.cpu().numpy() for t in res) if to_host else res
+
     def compute_pathloss(self, coherent: bool = True) -> np.ndarray:
         """Path loss in dB assuming 0 dBm transmitted power (dataset.py:541-566); cached as ``pathloss``."""
         eng = _engine()

@@ -12,6 +12,7 @@ include/deepmimo_amd.h and calls the C-ABI:
     dmx_channel_covariance -> complex64 [N, M, M]       (per-user spatial covariance, no channel tensor)
     dmx_channel_rate     -> float32 [N] (and [N, K])    (per-user achievable rate, no channel tensor)
     dmx_channel_spectrum -> float32 [N, K, m], [N], [N, K]  (eigenmode SNRs and water-filling rate, no channel tensor)
+    dmx_channel_precoders -> float32 [N, K, m], complex64 [N, K, L, M_tx], [N, K, L, M_rx]  (eigenbeams, no channel tensor)
 
 It replaces the body of Dataset.compute_channels (deepmimo/generator/dataset.py:224-268).
 No CPU path exists here: without the shared library or without a GPU every entry point raises.
@@ -256,6 +257,29 @@ def check_spectrum_call(params, n_paths_loaded: int, snr_db) -> float:
     rc = lib.dmx_spectrum_supported(C.byref(p), int(n_paths_loaded))
     if rc != 1:
         raise ValueError("spectrum: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
+    return snr
+
+
+def check_precoder_call(params, n_paths_loaded: int, snr_db, n_layers) -> float:
+    """`check_spectrum_call` for `Dataset.compute_precoders`: the same refusals, and an `n_layers` that is not an integer
+    in 1..min(M_rx, M_tx), asked of dmx_precoder_supported.  Returns the linear SNR."""
+    snr = snr_linear_from_db(snr_db)
+    if isinstance(n_layers, bool) or not isinstance(n_layers, (int, np.integer)):
+        raise ValueError(f"precoders: n_layers must be an integer, got {n_layers!r}")
+    ofdm = params[c.PARAMSET_OFDM]
+    if not params[c.PARAMSET_FD_CH]:
+        raise ValueError("precoders: needs the frequency-domain channel (freq_domain = 1)")
+    if ofdm[c.PARAMSET_OFDM_LPF]:
+        raise ValueError("precoders: ofdm.rx_filter = 1 is not covered")
+    sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
+    p = nat.DmxParams()
+    _fill_shape_fields(p, params, sel.size)
+    host_sel = (C.c_int32 * max(1, int(sel.size)))()          # the query reads the count, never the array
+    p.selected_subcarriers = C.addressof(host_sel)
+    lib = nat.load()
+    rc = lib.dmx_precoder_supported(C.byref(p), int(n_paths_loaded), int(np.clip(n_layers, -2 ** 31, 2 ** 31 - 1)))
+    if rc != 1:
+        raise ValueError("precoders: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
     return snr
 
 
@@ -792,6 +816,53 @@ class ChannelEngine:
                                                prep.n_paths_loaded, int(user_begin), int(user_count), snr,
                                                ptr[0], ptr[1], ptr[2], self._stream_ptr())
         nat.check(rc, "dmx_channel_spectrum")
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def precoder_supported(self, prep: PrepResult, n_layers: int = 1) -> bool:
+        """dmx_precoder_supported for this preparation (host-only query; `precoders` raises where it says no)."""
+        rc = self.lib.dmx_precoder_supported(C.byref(prep.params_struct), prep.n_paths_loaded, int(n_layers))
+        if rc < 0:
+            nat.check(rc, "dmx_precoder_supported")
+        return rc == 1
+
+    def precoders(self, prep: PrepResult, snr_db, n_layers: int = 1, user_begin: int = 0, user_count: Optional[int] = None,
+                  gamma: bool = True, tx: bool = True, rx: bool = True, out=None):
+        """dmx_channel_precoders: the eigenbeams of every subcarrier's channel at `snr_db`, from the per-path records of
+        `prep` - the channel tensor is not written.  With H_k = U S V^H, strongest modes first, m = min(M_rx, M_tx) and
+        L = `n_layers` in 1..m: `gamma` float32 [user_count, K, m], the mode SNRs snr * s_i^2; `tx` complex64
+        [user_count, K, L, M_tx], the precoders v_i; `rx` complex64 [user_count, K, L, M_rx], the combiners u_i (unit norm,
+        the gauge and the floor below which a layer is all zeros: include/deepmimo_amd.h).  Returns the requested tensors in
+        that order, HBM-resident - a single tensor when one is asked for, else a tuple.  `out`: the tensor (or the tuple
+        of tensors, in the same order) to write into."""
+        snr = snr_linear_from_db(snr_db)
+        if not (gamma or tx or rx):
+            raise ValueError("precoders: at least one of gamma, tx and rx must be asked for")
+        p = prep.params_struct
+        if user_count is None:
+            user_count = prep.n_ue - user_begin
+        m_tx, m_rx = p.bs_shape[0] * p.bs_shape[1], p.ue_shape[0] * p.ue_shape[1]
+        K, L = int(p.n_selected), int(n_layers)
+        wanted = [(sh, dt) for want, sh, dt in ((gamma, (user_count, K, min(m_tx, m_rx)), torch.float32),
+                                                (tx, (user_count, K, L, m_tx), torch.complex64),
+                                                (rx, (user_count, K, L, m_rx), torch.complex64)) if want]
+        given = list(out) if isinstance(out, (tuple, list)) else [out] * (out is not None)
+        if out is not None and len(given) != len(wanted):
+            raise ValueError(f"out must hold {len(wanted)} tensors, one per requested output")
+        if not self.precoder_supported(prep, L):                    # DMX_ERR_SHAPE, before an L < 1 reaches torch.empty
+            nat.check(-2, "dmx_channel_precoders")
+        res = []
+        for i, (shape, dt) in enumerate(wanted):
+            t = given[i] if given else torch.empty(shape, dtype=dt, device=self.device)
+            if t.dtype != dt or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+                raise ValueError(f"out must be a contiguous {dt} tensor of shape {shape}")
+            res.append(t)
+        it = iter(res)
+        ptr = [C.c_void_p(next(it).data_ptr()) if want else None for want in (gamma, tx, rx)]
+        with torch.cuda.device(self.device):
+            rc = self.lib.dmx_channel_precoders(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
+                                                prep.n_paths_loaded, int(user_begin), int(user_count), snr, L,
+                                                ptr[0], ptr[1], ptr[2], self._stream_ptr())
+        nat.check(rc, "dmx_channel_precoders")
         return res[0] if len(res) == 1 else tuple(res)
 
     def pathloss(self, rays: DeviceRays, coherent: bool = True) -> torch.Tensor:

@@ -332,6 +332,50 @@ int dmx_channel_spectrum(const dmx_params* prm, const void* workspace, int64_t n
                          float* out_rate_k  /* [user_count, K]    or NULL */, void* stream);
 
 /*
+ * Fused consumer, the third view of the same Gram: what the transmitter and the receiver apply to reach the water-filling
+ * rate - the singular vectors of every subcarrier's channel, H never written.  H_k, snr_linear and gamma as in
+ * dmx_channel_spectrum, m = min(M_rx, M_tx), L = n_layers in 1..m, H_k = U Sigma V^H with the strongest modes first:
+ *   gamma[u, k, i]   = snr_linear * sigma_i^2                          out_gamma  float32   [user_count, K, m]
+ *   w_tx[u, k, i, :] = v_i  (precoder, unit norm)                       out_tx_c64 complex64 [user_count, K, L, M_tx]
+ *   w_rx[u, k, i, :] = u_i  (combiner, unit norm)                       out_rx_c64 complex64 [user_count, K, L, M_rx]
+ *   H_k v_i = sigma_i u_i,   H_k^H u_i = sigma_i v_i,   sigma_i = sqrt(gamma_i / snr_linear)
+ * so u_i^H H_k v_i = sigma_i, real and >= 0.  Each of the three outputs may be NULL (not all of them).
+ * Gauge: the component of largest modulus (the first on ties) of the SMALLER-side vector of each pair (u_i if M_rx <= M_tx,
+ * else v_i) is real and positive, its imaginary part stored as exactly +0; the other vector follows from the relation above.
+ * Resolved modes: layer i of an entry (u, k) is present iff
+ *   gamma_i > max(c_J * 2^-24 * sum_j gamma_j, 1e-30),   c_J = 13 * sweeps * m (m - 1) / 2  (0 for m = 1)
+ * evaluated in float32 as one constant per m times the sum of the sorted gamma in index order.  Below that floor - about
+ * -45 dB of the entry's total mode SNR at m = 4, -38 dB at m = 8 - an eigenvalue cannot be told from the rounding of the
+ * iteration itself (the accuracy statement of dmx_channel_spectrum).  An absent layer gets +0.0 in every component of both
+ * vectors; a user without kept paths gets +0.0 everywhere.
+ * The kernel is dmx_channel_spectrum's with a third epilogue: the Jacobi rotations (the same sweep counts) are accumulated in
+ * an m x m matrix in registers, whose columns are the smaller-side vectors; the larger-side vectors take a second pass over
+ * the tables in LDS, y_i = B x_i / sqrt(gamma_i), and only when that output is asked for.  A pair (p, q) is rotated only
+ * where |G_pq| >= 2^-50: below that the float32 squares behind |G_pq| leave the normal range and the rotation's phase would
+ * lose its unit modulus.  Usable range therefore: off-diagonal mode-SNR entries below 2^-50 (about 8.9e-16) count as zero;
+ * the upper end is dmx_channel_spectrum's.  Because of this gate gamma is held to dmx_channel_spectrum's accuracy statement
+ * but is not promised bit-equal to its gamma.
+ * Accuracy (float32 model of the iteration on the hard and the repeated-eigenvalue matrices of tests/_spectrum_ref.py): the
+ * smaller-side vectors of an entry are orthonormal to |X^H X - I|_F <= 69 * 2^-24 at m = 8 (7 * 2^-24 at m = 2), and each
+ * satisfies |G x_i - gamma_i x_i|_2 <= 7.5 * 2^-24 |G|_F, G = snr_linear times the Gram of H_k over the smaller array - a
+ * statement about the residual, free of eigenvalue gaps: inside a cluster of equal gamma the vectors span the right subspace
+ * and the choice within it is arbitrary.  The larger-side vector is unit to |gamma|_2 / gamma_i times that residual bound.
+ * Launches repeat bit for bit, a user sub-range equals the same rows of a whole launch, a launch with fewer outputs writes
+ * the same bits, and n_layers = L' writes the first L' layers of n_layers = m.
+ *
+ * dmx_precoder_supported - the rule of dmx_rate_supported, and 1 <= n_layers <= m (else 0, the limit in dmx_last_error()).
+ * dmx_channel_precoders - the argument rules of dmx_channel_spectrum; all three outputs NULL with user_count > 0:
+ * DMX_ERR_ARG; n_layers outside 1..m: DMX_ERR_SHAPE; user_count = 0: DMX_OK.  out_gamma: 4-byte aligned, out_tx_c64 /
+ * out_rx_c64: 8-byte aligned device pointers.
+ */
+int dmx_precoder_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_layers);
+int dmx_channel_precoders(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
+                          int64_t user_begin, int64_t user_count, double snr_linear, int32_t n_layers,
+                          float* out_gamma   /* [user_count, K, m]       or NULL */,
+                          void* out_tx_c64   /* [user_count, K, L, M_tx] or NULL */,
+                          void* out_rx_c64   /* [user_count, K, L, M_rx] or NULL */, void* stream);
+
+/*
  * Stage 2, time domain (replaces channel.py:285-287): out[u, rx, tx, s] = a_rx a_tx sqrt(p) e^{j phase}
  * of the s-th valid path (valid paths compacted to the front, remaining slots zero),
  * complex64 [user_count, M_rx, M_tx, P], P = min(num_paths, n_paths_loaded).

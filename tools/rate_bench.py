@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Per-user achievable rate and channel eigenmodes: the fused routes against the channel tensor + torch.linalg, alternating in
-ONE process: `python tools/rate_bench.py [--out profiles/r6_rate_bench.jsonl]`.
+"""Per-user achievable rate, channel eigenmodes and eigenbeams: the fused routes against the channel tensor + torch.linalg, alternating in
+ONE process: `python tools/rate_bench.py [--out profiles/r7_precoder_bench.jsonl]`.
 
 For each shape, on the same uploaded rays:
   (a) fused     dmx_path_prep + dmx_channel_rate                                 (no channel tensor)
@@ -12,6 +12,13 @@ For each shape, on the same uploaded rays:
                 solver takes seconds for 1e5 small matrices, so this route runs on the first `--eig-users` users only, one
                 launch per timing; its time is reported for that count and `modes_speedup_per_user` compares time per user,
                 an extrapolation and not a like-for-like run
+  (f) beams     dmx_path_prep + dmx_channel_precoders with n_layers = 1, gamma and the smaller-side vector only (the
+                rotations accumulated in registers; no second pass)
+  (g) beams2    (f) with the larger-side vector as well (the second pass over the tables; at the headline shape the
+                precoders of 1e5 users are as large as H itself, so this route runs on the first `--beam-users` users and
+                its time is reported for that count)
+  (h) svd       (g)'s unfused twin: (b)'s channel chunks and torch.linalg.svd of H_k, the first singular pair kept, on the
+                first `--eig-users` users only, one launch per timing; `beams_speedup_per_user` compares time per user
 Device events around back-to-back launches of one route, the routes alternating `--rounds` times after a warm-up; the
 whole A/B runs twice (`pass` 0 and 1) and the difference between the two passes of the SAME route is the spread a
 difference between the routes has to exceed.  One JSON line per shape: mean, minimum and spread of both routes, the fused
@@ -60,7 +67,8 @@ def main():
     ap.add_argument("--shapes", default=",".join(s[0] for s in SHAPES))
     ap.add_argument("--scale", type=float, default=1.0, help="multiply every user count (rehearsals)")
     ap.add_argument("--eig-users", type=int, default=200, help="users of route (e)")
-    ap.add_argument("--routes", default="fused,slogdet,spectrum,modes,eigvalsh")
+    ap.add_argument("--beam-users", type=int, default=20000, help="users of route (g)")
+    ap.add_argument("--routes", default="fused,slogdet,spectrum,modes,eigvalsh,beams,beams2,svd")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     eng = ChannelEngine(0)
@@ -91,6 +99,12 @@ def main():
         want = args.routes.split(",")
         g_fused = torch.empty((n, K, m), dtype=torch.float32, device=eng.device) if "modes" in want else None
         g_ref = torch.empty((n_eig, K, m), dtype=torch.float32, device=eng.device) if "eigvalsh" in want else None
+        n_beam = min(n, max(1, args.beam_users))
+        cplx = lambda *shape: torch.empty(shape, dtype=torch.complex64, device=eng.device)   # noqa: E731
+        b_gamma = torch.empty((n, K, m), dtype=torch.float32, device=eng.device) if {"beams", "beams2"} & set(want) else None
+        b_small = cplx(n, K, 1, m) if {"beams", "beams2"} & set(want) else None
+        b_big = cplx(n_beam, K, 1, big) if "beams2" in want else None
+        v_ref = cplx(n_eig, K, m_tx) if "svd" in want else None
         eye = torch.eye(m, dtype=torch.complex64, device=eng.device)
         spec = "uitk,ujtk->ukij" if m_rx <= m_tx else "urjk,urik->ukij"
         s = snr / m_tx
@@ -126,8 +140,29 @@ def main():
                 G = torch.einsum(spec, H[:cnt], H[:cnt].conj())
                 g_ref[b:b + cnt] = torch.linalg.eigvalsh(snr * G).flip(-1).clamp_min(0)   # scaled first: raw gains are near 1e-15
 
-        routes = [r for r in (("fused", fused), ("slogdet", slogdet), ("spectrum", spectrum), ("modes", modes), ("eigvalsh", eigvalsh))
-                  if r[0] in want]
+        def beam_call(count, with_big):
+            small, bigp = C.c_void_p(b_small.data_ptr()), C.c_void_p(b_big.data_ptr()) if with_big else None
+            tx, rx = (bigp, small) if m_rx <= m_tx else (small, bigp)
+            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            nat.check(lib.dmx_channel_precoders(C.byref(ps), wsp, n, L, 0, count, snr, 1, C.c_void_p(b_gamma.data_ptr()), tx, rx, stream),
+                      "dmx_channel_precoders")
+
+        def beams():
+            beam_call(n, False)
+
+        def beams2():
+            beam_call(n_beam, True)
+
+        def svd():
+            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            for b in range(0, n_eig, chunk):
+                cnt = min(chunk, n_eig - b)
+                nat.check(lib.dmx_channels_fd(C.byref(ps), wsp, n, L, b, cnt, C.c_void_p(H.data_ptr()), 0, stream), "dmx_channels_fd")
+                _, _, vh = torch.linalg.svd(H[:cnt].permute(0, 3, 1, 2) * math.sqrt(snr), full_matrices=False)
+                v_ref[b:b + cnt] = vh[..., 0, :].conj()
+
+        routes = [r for r in (("fused", fused), ("slogdet", slogdet), ("spectrum", spectrum), ("modes", modes), ("eigvalsh", eigvalsh),
+                              ("beams", beams), ("beams2", beams2), ("svd", svd)) if r[0] in want]
         rec = dict(shape=name, bs=bs, ue=ue, K=K, users=n, paths=L, snr_db=args.snr_db, chunk_users=chunk,
                    H_bytes=n * m_rx * m_tx * K * 8, launches_per_route=2 * args.rounds * args.launches)
         rec["fused_flops"] = n * K * big * (L * (6 + 8 * m) + 8 * m * (m + 1) // 2)
@@ -137,7 +172,7 @@ def main():
             ts = {rn: [] for rn, _ in routes}
             for _ in range(args.rounds):
                 for rn, fn in routes:
-                    ts[rn].append(timed(fn, 1 if rn == "eigvalsh" else args.launches))
+                    ts[rn].append(timed(fn, 1 if rn in ("eigvalsh", "svd") else args.launches))
             for rn, v in ts.items():
                 rec[f"{rn}_avg_ms_pass{ab}"] = round(float(np.mean(v)), 5)
                 rec[f"{rn}_min_ms_pass{ab}"] = round(float(np.min(v)), 5)
@@ -162,9 +197,26 @@ def main():
             rec["modes_speedup_per_user"] = round((rec["eigvalsh_avg_ms"] / n_eig) / (rec["modes_avg_ms"] / n), 3)
             top = g_ref[..., 0].clamp_min(1e-30)
             rec["modes_max_dev_rel_to_strongest"] = float(((g_fused[:n_eig] - g_ref).abs().amax(dim=-1) / top).max())
+        if "beams" in have:
+            rec["precoder_out_bytes_small_side"] = n * K * (4 * m + 8 * m)
+        if {"beams", "modes"} <= have:
+            rec["beams_over_modes"] = round(rec["beams_avg_ms"] / rec["modes_avg_ms"], 4)
+        if "beams2" in have:
+            rec["beams2_users"] = n_beam                                  # route (g) covers these users only
+            rec["precoder_out_bytes_both_sides"] = n_beam * K * (4 * m + 8 * m + 8 * big)
+        if {"beams2", "modes"} <= have:
+            rec["beams2_over_modes_per_user"] = round((rec["beams2_avg_ms"] / n_beam) / (rec["modes_avg_ms"] / n), 4)
+        if {"beams2", "svd"} <= have:
+            rec["svd_users"] = n_eig
+            rec["beams_speedup_per_user"] = round((rec["svd_avg_ms"] / n_eig) / (rec["beams2_avg_ms"] / n_beam), 3)
+            k = min(n_eig, n_beam)
+            v_fused = (b_big if m_rx <= m_tx else b_small)[:k, :, 0, :]
+            live = b_gamma[:k, :, 0] > 0
+            overlap = (v_fused.conj() * v_ref[:k]).sum(dim=-1).abs()
+            rec["beams_min_overlap_with_svd"] = float(overlap[live].min()) if bool(live.any()) else None
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
-        del H, prep, rays
+        del H, prep, rays, b_gamma, b_small, b_big, v_ref, g_fused, g_ref
         torch.cuda.empty_cache()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
