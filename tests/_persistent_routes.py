@@ -172,6 +172,7 @@ def _mfma(nw, mode, gsrc, rows, ipw, persistent=True):
 _FFT512 = Launch("k3_lpf_fft512", "fft_wave_per_user", lds=4 * (512 + 512 // 16 + 1) * 8)          # k3_lpf_gains.hip:823
 _FFT128 = Launch("k3_lpf_fft_pow2", "fft_wave_per_user", lds=4 * 4 * (128 + 128 // 16 + 1) * 8)    # :837-839
 _FFTW512 = Launch("k3_lpf_fft_wave", "fft_wave", lds=512 * 8 + 4 * 2 * (512 + 512 // 16 + 1) * 8)  # :263
+_FFTW2048 = Launch("k3_lpf_fft_wave", "fft_wave", lds=2048 * 8 + 4 * 2 * (2048 + 2048 // 16 + 1) * 8)
 
 ROUTES = (
     # GSRC 4 (factorised B', uniform selection); 8-wave workgroups with ITEMS_PER_WG8
@@ -221,6 +222,10 @@ ROUTES = (
           ("range", 0, 512, 1), 20480, (_FFT512,), kind="lpf", doppler=True),
     Route("o", "k3_lpf_fft_wave (K = 600 > N = 512)", (2, 1), (1, 1), 25, 512, ("range", 0, 600, 1), 8192,
           (_FFTW512,), kind="lpf"),
+    # the same kernel at N = 2048, its only route there: 155,712 B of LDS = one workgroup per CU, which reuses its twiddle
+    # table and both transform buffers of every wave across 8 users of changing path counts; last pass of radix 4
+    Route("o2048", "k3_lpf_fft_wave at N = 2048 (one workgroup per CU), Doppler", (2, 1), (1, 1), 25, 2048, ("random", 64, 17),
+          2048, (_FFTW2048,), kind="lpf", doppler=True),
     # GSRC 1 (the float gains table with matrix cores): rx_filter with more than 32 path slots (lpf_table_packed is
     # false, k2_channel_fd.hip:308); the first 32 kept paths go through the matrix cores, the rest through the vector
     # kernel's accumulate passes

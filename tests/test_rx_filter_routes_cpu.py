@@ -1,0 +1,248 @@
+"""CPU tests of what tests/test_gpu_rx_filter_routes.py runs (tests/_lpf_routes.py).
+
+1. The route mirror `lpf_route` and the kernel facts are tied to the text of k3_lpf_gains.hip: a change to the dispatcher
+   fails here instead of silently sending the GPU cases to another kernel.
+2. The case table reaches what it promises, by the mirror: k3_lpf_fft_wave with a last pass of radix 8, 4 and 2, both
+   gather forms, packed and float tables, more than 64 kept paths; k3_lpf_fft with PB = 16 (a full and a ragged batch)
+   and PB = 1; k3_lpf_gains with N > 256 and K > 256; nothing on the two fast kernels the suite already covers.
+3. The reference against itself: the float64 gain rows summed through the float64 array responses are the oracle's
+   channel, and for power-of-two N they are np.fft.fft of the taps at the selected bins.
+4. Sensitivity, a condition on the inputs: for the equal-power user of every case a dropped path and two gain rows in
+   each other's places each move H by at least 2 x TOL_REL of the user's peak, so the GPU parity check sees them.  The
+   seeds of tests/_lpf_routes.py are the first for which this holds (`first_good_seed`); there are no skips.
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from tests import _lpf_routes as R
+from tests._cases import TOL_REL
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "deepmimo_amd", "csrc")
+IDS = [c.id for c in R.CASES]
+
+
+def _src(name):
+    with open(os.path.join(CSRC, name)) as f:
+        return f.read()
+
+
+def test_route_mirror_and_the_dispatchers_text():
+    k3 = _src("k3_lpf_gains.hip")
+    body = k3[k3.index("static int launch_channels_fd_lpf_once(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,\n"
+                       "                                       float2* gtab, float2* out, hipStream_t stream) {"):]
+    pinned = [
+        r"if \(\(size_t\)a\.N \* 16 > 64 \* 1024\) \{ set_error\(\"rx_filter variant supports at most 4096 subcarriers \(got %d\)\", a\.N\); return DMX_ERR_SHAPE; \}",
+        r"const bool pow2 = a\.N >= 2 && \(a\.N & \(a\.N - 1\)\) == 0;",
+        r"while \(\(1 << log2n\) < a\.N\) \+\+log2n;",
+        r"const bool old = tuning_int\(\"DMX_LPF_OLD_FFT\", 0\) == 1;",
+        r"\n        if \(a\.N == 512 && a\.K <= 512 && ws\.P <= 64 && !old && tuning_int\(\"DMX_LPF_GENERIC_FFT\", 0\) != 1\) \{",
+        r"\"k3_lpf_fft512\", 4 \* lpf_buf_elems\(512\) \* 8,",
+        r"\n        \} else if \(\(a\.N == 64 \|\| a\.N == 128 \|\| a\.N == 256 \|\| a\.N == 1024\) && a\.K <= a\.N && ws\.P <= 64 && !old &&\n"
+        r"                   tuning_int\(\"DMX_LPF_GENERIC_FFT\", 0\) != 1\) \{",
+        r"\"k3_lpf_fft_pow2\",",
+        r"\n        \} else if \(pow2 && a\.N >= 64 && a\.N <= 2048 && !old\) \{",
+        r"a\.pack = packed = lpf_table_packed\(prm, ws\) && tuning_int\(\"DMX_LPF_FLOAT_TABLE\", 0\) != 1;\n[^\n]*\n"
+        r"            const size_t smem = lpf_wave_lds_bytes\(a\.N\);",
+        r"launch_dyn_lds\(k3_lpf_fft_wave, \"k3_lpf_fft_wave\", dim3\(\(unsigned\)grid\), dim3\(256\), smem, smem, stream, ws, a, log2n, user_count\);",
+        r"\n        \} else if \(pow2\) \{",
+        r"int PB = 4096 / a\.N;\n            if \(PB < 1\) PB = 1;\n            if \(PB > 16\) PB = 16;\n            if \(PB > ws\.P\) PB = ws\.P;",
+        r"const size_t smem = \(size_t\)\(a\.N / 2\) \* 8 \+ \(size_t\)PB \* a\.N \* 8 \+ \(size_t\)PB \* 4;",
+        r"launch_dyn_lds\(k3_lpf_fft, \"k3_lpf_fft\", dim3\(\(unsigned\)user_count\), dim3\(256\), smem, LDS_NO_RAISE, stream, ws, a, log2n, PB\);",
+        r"\n        \} else \{\n            const int64_t blocks = user_count \* ws\.P;",
+        r"launch_dyn_lds\(k3_lpf_gains, \"k3_lpf_gains\", dim3\(\(unsigned\)blocks\), dim3\(256\), \(size_t\)a\.N \* 16, LDS_NO_RAISE, stream, ws, a\);",
+    ]
+    at = 0
+    for pat in pinned:                                         # each condition, and in this order
+        m = re.compile(pat).search(body, at)
+        assert m, f"the dispatcher no longer reads: {pat}"
+        at = m.end()
+    assert body.count("a.pack = packed =") == 3 and body.count("else if") == 3      # five branches, three that may pack
+    # the kernels' own rules
+    assert re.search(r"__host__ __device__ inline size_t lpf_buf_elems\(int N\) \{ return \(size_t\)N \+ N / 16 \+ 1; \}", k3)
+    assert re.search(r"__host__ __device__ inline size_t lpf_wave_lds_bytes\(int N\) \{ return \(size_t\)N \* 8 \+ 4 \* 2 \* lpf_buf_elems\(N\) \* 8; \}", k3)
+    assert re.search(r"constexpr int NBIN = 8;", k3)
+    assert re.search(r"const bool bins_in_regs = a\.K <= 64 \* NBIN;", k3)
+    assert re.search(r"if \(left >= 3\) \{ fft_pass<8>\(src, dst, W, N, log2n, 1 << log2ns, log2ns, lane\); log2ns \+= 3; \}\n"
+                     r"\s*else if \(left == 2\) \{ fft_pass<4>\(src, dst, W, N, log2n, 1 << log2ns, log2ns, lane\); log2ns \+= 2; \}\n"
+                     r"\s*else \{ fft_pass<2>\(src, dst, W, N, log2n, 1 << log2ns, log2ns, lane\); log2ns \+= 1; \}", k3)
+    assert re.search(r"for \(int l = wave; l < n_keep; l \+= 4\) \{\n[^\n]*\n\s*if \(l < 64\) \{", k3)
+    assert re.search(r"for \(int l0 = 0; l0 < n_keep; l0 \+= PB\) \{\n\s*const int nb = \(n_keep - l0\) < PB \? \(n_keep - l0\) : PB;", k3)
+    assert re.search(r"for \(int d = threadIdx\.x; d < a\.N; d \+= 256\) \{", k3)
+    assert re.search(r"for \(int k = threadIdx\.x; k < a\.K; k \+= 256\) \{", k3)
+    assert re.search(r"bool lpf_table_packed\(const dmx_params& prm, const WsView& ws\) \{ return fd_mfma_preferred\(prm, ws\) && ws\.P <= 32; \}",
+                     _src("k2_channel_fd.hip"))
+    assert re.search(r"if \(!fd_mfma_supported\(prm, ws\)\) return false;\n\s*if \(M >= 9\) return true;[^\n]*\n\s*return M == 8 && K >= 1024;",
+                     _src("k2_channel_fd_mfma.hip"))
+    assert R.NBIN == 8 and R.MAX_N * 16 == 64 * 1024
+
+    # the mirror at the edges of every condition
+    route = R.lpf_route
+    assert [route(512, K, 25) for K in (1, 512, 513)] == ["fft512", "fft512", "fft_wave"]
+    assert [route(512, 100, P) for P in (64, 65)] == ["fft512", "fft_wave"]
+    assert [route(N, N, 25) for N in (64, 128, 256, 1024)] == ["fft_pow2"] * 4
+    assert [route(N, N + 1, 25) for N in (64, 128, 256, 1024)] == ["fft_wave"] * 4
+    assert [route(N, 8, 65) for N in (64, 128, 256, 1024)] == ["fft_wave"] * 4
+    assert [route(2048, K, 25) for K in (1, 2048, 5000)] == ["fft_wave"] * 3
+    assert [route(N, 2, 9) for N in (2, 4, 8, 16, 32, 4096)] == ["fft"] * 6
+    assert [route(N, 2, 9) for N in (1, 3, 48, 100, 600, 4000, 4095)] == ["gains"] * 7
+    assert [route(N, 2, 9) for N in (4097, 4100, 8192)] == ["refused"] * 3
+    assert R.wave_lds_bytes(2048) == 155712 and R.wave_lds_bytes(1024) == 77888 and R.wave_lds_bytes(2048) <= 160 * 1024
+    assert R.wave_lds_bytes(512) == 512 * 8 + 4 * 2 * (512 + 512 // 16 + 1) * 8
+    assert [R.wave_radices(N) for N in (64, 128, 256, 512, 1024, 2048)] == [(8, 8), (8, 8, 2), (8, 8, 4), (8, 8, 8), (8, 8, 8, 2),
+                                                                           (8, 8, 8, 4)]
+    assert [R.wave_gather(K) for K in (1, 512, 513)] == ["regs", "regs", "buffer"]
+    assert [R.fft_pb(N, 25) for N in (2, 32, 256, 512, 4096)] == [16, 16, 16, 8, 1] and R.fft_pb(8, 9) == 9
+    assert R.fft_batches(32, 25, 25) == [16, 9] and R.fft_batches(32, 25, 16) == [16] and R.fft_batches(4096, 9, 3) == [1, 1, 1]
+    assert R.fft_lds_bytes(4096, 9) == 2048 * 8 + 4096 * 8 + 4 and R.gains_lds_bytes(4000) == 64000
+    assert R.table_packed(2048, 2048, 25, 128) and not R.table_packed(2048, 300, 25, 2)
+    assert not R.table_packed(256, 86, 70, 128) and not R.table_packed(4096, 64, 9, 128)
+
+
+def test_the_table_reaches_what_it_promises():
+    kept = {}                                                   # kept-path counts per case, from the reference's records
+    for c in R.CASES:
+        _, _, keep, _ = R.path_records(R.case_rays(c), R.case_dict(c, c.arrays[0]))
+        kept[c.id] = keep.sum(axis=1)
+    wave = [c for c in R.CASES if R.route_of(c) == "fft_wave"]
+    fft = [c for c in R.CASES if R.route_of(c) == "fft"]
+    gains = [c for c in R.CASES if R.route_of(c) == "gains"]
+    assert len(wave) + len(fft) + len(gains) == len(R.CASES)    # nothing on fft512 / fft_pow2, nothing refused
+    assert {c.id[0] for c in wave} == {"w"} and {c.id[0] for c in fft} == {"f"} and {c.id[0] for c in gains} == {"g"}
+    # k3_lpf_fft_wave
+    assert {R.wave_radices(c.N)[-1] for c in wave} == {8, 4, 2}
+    assert R.wave_radices(R.CASES_BY_ID["w2048_all"].N) == (8, 8, 8, 4) and R.wave_radices(256) == (8, 8, 4)
+    assert {R.wave_gather(len(R.selection(c))) for c in wave} == {"regs", "buffer"}
+    assert {R.wave_gather(len(R.selection(c))) for c in wave if c.N == 2048} == {"regs", "buffer"}
+    assert R.wave_gather(len(R.selection(R.CASES_BY_ID["w2048_512"]))) == "regs"
+    assert R.wave_gather(len(R.selection(R.CASES_BY_ID["w2048_513"]))) == "buffer"
+    for gather in ("regs", "buffer"):                           # the packed store of this kernel through both gathers
+        assert any(R.packed(c, a) and R.wave_gather(len(R.selection(c))) == gather for c in wave for a in c.arrays), gather
+        assert any(not R.packed(c, a) and R.wave_gather(len(R.selection(c))) == gather for c in wave for a in c.arrays), gather
+    assert any(len(R.selection(c)) % 64 for c in wave if R.wave_gather(len(R.selection(c))) == "regs")      # guarded k < K
+    sel = R.selection(R.CASES_BY_ID["w2048_neg"])
+    assert (sel < 0).sum() >= 20 and (sel >= 2048).sum() >= 10 and sel.min() >= -4096 and sel.max() < 4096
+    assert max(R.wave_lds_bytes(c.N) for c in wave) == 155712
+    over64 = [c for c in wave if kept[c.id].max() > 64]
+    assert {c.id for c in over64} == {"w256_p70", "w512_p70"} and all(c.L == 70 for c in over64)
+    for c in over64:                                            # float table whatever the arrays; both arrays at N = 256
+        assert not any(R.packed(c, a) for a in c.arrays)
+        assert kept[c.id][R.ONE] == 1 and kept[c.id][R.NONE] == 0 and kept[c.id][R.TWO] == 2
+        assert kept[c.id].max() == 70                           # slots 64 .. 69: the l >= 64 reads of two waves at least
+    assert set(R.CASES_BY_ID["w256_p70"].arrays) == {"mfma", "valu"}
+    assert R.lpf_route(512, len(R.selection(R.CASES_BY_ID["w512_p70"])), 25) == "fft512"       # what P = 70 displaces
+    # k3_lpf_fft
+    assert {R.fft_pb(c.N, c.L) for c in fft} == {16, 9, 1}
+    for cid in ("f32_all", "f32_off"):
+        c = R.CASES_BY_ID[cid]
+        batches = [tuple(R.fft_batches(c.N, c.L, int(n))) for n in kept[cid]]
+        assert any(b == (16,) or (len(b) == 2 and b[0] == 16) for b in batches)
+        assert any(len(b) == 2 and 0 < b[1] < 16 for b in batches), batches                     # a ragged second batch
+    assert R.fft_pb(4096, R.CASES_BY_ID["f4096"].L) == 1 and R.log2n(4096) == 12 and kept["f4096"].max() >= 3
+    assert {R.log2n(c.N) for c in fft} == {1, 3, 5, 12}
+    assert (R.selection(R.CASES_BY_ID["f4096"]) >= 4096).any()
+    # k3_lpf_gains
+    g600 = R.CASES_BY_ID["g600"]
+    assert g600.N > 512 and len(R.selection(g600)) > 256        # tap passes at d = tid, + 256, + 512; bin passes at k, + 256
+    g4000 = R.CASES_BY_ID["g4000"]
+    assert R.gains_lds_bytes(g4000.N) == 64000 and (R.selection(g4000) % g4000.N != np.fmod(R.selection(g4000), g4000.N)).any()
+    assert (R.selection(g4000) < 0).any() and R.CASES_BY_ID["g1"].N == 1
+    # every case: the fixture users, and a sub-range that exists
+    for c in R.CASES:
+        assert c.n_ue >= R.SUB_BEGIN + R.SUB_COUNT and 6 <= (c.oracle_users or c.n_ue) <= 14, c.id
+    c_, dn, keep, _ = R.path_records(R.case_rays(R.CASES_BY_ID["w2048_first"]), R.case_dict(R.CASES_BY_ID["w2048_first"], "valu"))
+    assert c_.dtype == np.complex64 and dn.dtype == np.float32
+    whole = dn[R.WHOLE][keep[R.WHOLE]]
+    assert (whole == 0).any() and (whole[:3] == np.round(whole[:3])).all()
+    assert dn[R.LAST, 0] == 2047.0 and keep[R.LAST, 0]
+
+
+@pytest.mark.parametrize("cid", ["w64_wrap", "f32_off", "g600"])
+def test_gain_rows_sum_to_the_oracles_channel(cid):
+    """One case per route, Doppler off and on, both array sizes (g600: the larger one only - the oracle takes a second per call
+    there).  The oracle stores its channel as complex64
+    (channel.py:257), so a float64 sum cannot meet it at 1e-10 of the peak: the storage alone rounds every element by up
+    to half a float32 ulp.  The float64 sum is therefore rounded the same way and held to 1e-10 of the user's peak plus
+    ONE float32 ulp of the element (two float64 sums that differ in their last bits may round to neighbouring floats);
+    and the rows themselves, where the oracle has float64 numbers (oracle_np.ofdm_path_gains on the kept paths), are held
+    to 1e-10 of each row's own peak."""
+    from oracle import oracle_np as onp
+    c = R.CASES_BY_ID[cid]
+    rays = R.case_rays(c)
+    for arrays in (("mfma",) if cid == "g600" else ("valu", "mfma")):
+        cd = R.case_dict(c, arrays)
+        resp = R.responses(rays, cd)
+        _, _, keep, prep = R.path_records(rays, cd)
+        ofdm = dict(subcarriers=c.N, selected_subcarriers=R.selection(c), bandwidth=R.BANDWIDTH, rx_filter=1)
+        for dop in (False, True):
+            ref = R.oracle(c, arrays, dop)["channel"]
+            rows = R.lpf_gain_rows(rays, cd, dop)
+            for u in range(c.n_ue):
+                H = R.channel_from_rows(resp[u], rows[u]).astype(np.complex64).astype(np.complex128)
+                want = ref[u].astype(np.complex128)
+                ulp = np.spacing(np.maximum(np.abs(ref[u].real), np.abs(ref[u].imag)).astype(np.float32)).astype(np.float64)
+                assert np.all(np.abs(H - want) <= 1e-10 * np.abs(want).max() + np.sqrt(2) * ulp), (cid, arrays, dop, u)
+                k = keep[u]
+                if not k.any():
+                    assert rows[u].shape == (0, len(R.selection(c))) and not want.any()
+                    continue
+                d = (rays["doppler_vel"][u, :c.L][k], rays["doppler_acc"][u, :c.L][k], R.FC) if dop else None
+                g = onp.ofdm_path_gains(prep["_power_linear_ant_gain"][u, :c.L][k], rays["delay"][u, :c.L][k],
+                                        rays["phase"][u, :c.L][k], ofdm, d)
+                assert g.dtype == np.complex128 and g.shape == rows[u].shape
+                assert np.all(np.abs(g - rows[u]).max(axis=1) <= 1e-10 * np.abs(g).max(axis=1)), (cid, arrays, dop, u)
+
+
+@pytest.mark.parametrize("cid", [c.id for c in R.CASES if c.N >= 2 and c.N & (c.N - 1) == 0])
+def test_gain_rows_are_the_fft_of_the_taps(cid):
+    c = R.CASES_BY_ID[cid]
+    rays = R.case_rays(c)
+    cd = R.case_dict(c, c.arrays[0])
+    users = [R.WHOLE, R.LAST, R.EQUAL]
+    sel = R.selection(c)
+    for dop in (False, True):
+        taps, _ = R.tap_rows(rays, cd, dop, users)
+        rows = R.lpf_gain_rows(rays, cd, dop, users)
+        for t, g in zip(taps, rows):
+            want = np.fft.fft(t, axis=1)[:, sel % c.N]
+            assert g.shape == want.shape and g.shape[0] > 0
+            assert np.all(np.abs(g - want).max(axis=1) <= 1e-12 * np.abs(want).max(axis=1))
+
+
+@pytest.mark.parametrize("cid", IDS)
+def test_equal_power_user_shows_a_lost_or_misplaced_row(cid):
+    c = R.CASES_BY_ID[cid]
+    rays = R.case_rays(c)
+    for arrays in c.arrays:
+        cd = R.case_dict(c, arrays)
+        resp = R.responses(rays, cd, [R.EQUAL])[0]
+        for dop in (False, True):
+            rows = R.lpf_gain_rows(rays, cd, dop, [R.EQUAL])[0]
+            assert rows.shape[0] >= 3
+            drop, swap, peak = R.sensitivity(resp, rows)
+            assert drop >= 2 * TOL_REL * peak and swap >= 2 * TOL_REL * peak, (cid, arrays, dop, drop / peak, swap / peak)
+    assert R.first_good_seed(c, TOL_REL) == R.SEEDS[cid]
+
+
+def test_sensitivity_formula_against_the_sum():
+    """the outer-product shortcut of `sensitivity` is what dropping and swapping do to the summed channel"""
+    c = R.CASES_BY_ID["f32_all"]
+    cd = R.case_dict(c, "mfma")
+    rays = R.case_rays(c)
+    resp = R.responses(rays, cd, [R.EQUAL])[0]
+    rows = R.lpf_gain_rows(rays, cd, True, [R.EQUAL])[0]
+    H = R.channel_from_rows(resp, rows)
+    n = rows.shape[0]
+    drops = [np.abs(H - R.channel_from_rows((np.delete(resp[0], l, 1), np.delete(resp[1], l, 1)), np.delete(rows, l, 0))).max()
+             for l in range(n)]
+    swaps = []
+    for i in range(n):
+        for j in range(i + 1, n):
+            r2 = rows.copy()
+            r2[[i, j]] = rows[[j, i]]
+            swaps.append(np.abs(H - R.channel_from_rows(resp, r2)).max())
+    drop, swap, peak = R.sensitivity(resp, rows)
+    np.testing.assert_allclose([drop, swap, peak], [min(drops), min(swaps), np.abs(H).max()], rtol=1e-12)
