@@ -21,8 +21,10 @@ EXPORTED_SYMBOLS = ("dmx_version", "dmx_last_error", "dmx_workspace_bytes", "dmx
                     "dmx_p2m_count_rx", "dmx_p2m_parse_paths", "dmx_fd_kernel_choice", "dmx_beam_power",
                     "dmx_fd_direct_supported", "dmx_channels_fd_direct", "dmx_covariance_supported",
                     "dmx_channel_covariance", "dmx_rate_supported", "dmx_channel_rate",
-                    "dmx_spectrum_supported", "dmx_channel_spectrum", "dmx_precoder_supported", "dmx_channel_precoders")
+                    "dmx_spectrum_supported", "dmx_channel_spectrum", "dmx_precoder_supported", "dmx_channel_precoders",
+                    "dmx_cell_rate_supported", "dmx_cell_rate")
 
+MAX_LINKS = 8                             # DMX_MAX_LINKS
 PATTERN_IDS = {"isotropic": 0, "halfwave-dipole": 1}
 COV_SIDES = {"tx": 0, "rx": 1}            # DMX_COV_TX / DMX_COV_RX
 
@@ -59,6 +61,11 @@ class DmxSide(C.Structure):
                 ("aoa_el_rot", C.c_void_p), ("aoa_az_rot", C.c_void_p),
                 ("power_linear", C.c_void_p), ("power_linear_ant_gain", C.c_void_p),
                 ("max_delay_key", C.c_void_p)]
+
+
+class DmxLink(C.Structure):
+    _fields_ = [("prm", C.POINTER(DmxParams)), ("workspace", C.c_void_p), ("n_paths_loaded", C.c_int32),
+                ("snr_linear", C.c_double)]
 
 
 class DmxMatInfo(C.Structure):
@@ -122,6 +129,11 @@ def load():
     lib.dmx_channel_precoders.restype = C.c_int
     lib.dmx_channel_precoders.argtypes = [C.POINTER(DmxParams), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
                                           C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dmx_cell_rate_supported.restype = C.c_int
+    lib.dmx_cell_rate_supported.argtypes = [C.POINTER(DmxLink), C.c_int32]
+    lib.dmx_cell_rate.restype = C.c_int
+    lib.dmx_cell_rate.argtypes = [C.POINTER(DmxLink), C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.dmx_decode_max_delay.restype = C.c_float
     lib.dmx_decode_max_delay.argtypes = [C.c_uint32]
     lib.dmx_path_prep.restype = C.c_int

@@ -439,6 +439,96 @@ int dmx_channel_precoders(const dmx_params* prm, const void* workspace, int64_t 
                             (float2*)out_rx_c64, (hipStream_t)stream);
 }
 
+// 1: taken; 0: not taken, with the limit in the error string; negative: bad argument.  Every link's params are checked.
+static int cell_rate_shape(const dmx_link* links, int32_t n_links) {
+    if (!links) { set_error("links is NULL"); return DMX_ERR_ARG; }
+    if (n_links < 1 || n_links > DMX_MAX_LINKS) {
+        set_error("cell rate: n_links = %d is outside the 1..%d links (DMX_MAX_LINKS) the kernel supports", n_links, DMX_MAX_LINKS);
+        return 0;
+    }
+    for (int b = 0; b < n_links; ++b) {
+        if (int rc = check_params(links[b].prm)) return rc;
+        if (links[b].n_paths_loaded < 0) { set_error("link %d: n_paths_loaded must be >= 0", b); return DMX_ERR_ARG; }
+    }
+    const dmx_params* p0 = links[0].prm;
+    const long long m_rx = (long long)p0->ue_shape[0] * p0->ue_shape[1];
+    for (int b = 0; b < n_links; ++b) {
+        const dmx_params* p = links[b].prm;
+        if (!p->freq_domain || p->rx_filter) {
+            set_error("cell rate: link %d: the rate needs freq_domain = 1 and rx_filter = 0", b); return 0;
+        }
+        const int P = used_paths(p, links[b].n_paths_loaded);
+        if (P < 1 || P > 32) {
+            set_error("cell rate: link %d: min(num_paths, loaded paths) = %d is outside the 1..32 paths the kernel supports", b, P);
+            return 0;
+        }
+        if (p->ue_shape[0] != p0->ue_shape[0] || p->ue_shape[1] != p0->ue_shape[1]) {
+            set_error("cell rate: link %d has ue_shape %d x %d, link 0 %d x %d: the links must share the UE array", b,
+                      p->ue_shape[0], p->ue_shape[1], p0->ue_shape[0], p0->ue_shape[1]);
+            return 0;
+        }
+        if (p->n_subcarriers != p0->n_subcarriers || p->n_selected != p0->n_selected) {
+            set_error("cell rate: link %d has %d of %d subcarriers selected, link 0 %d of %d: the links must share n_subcarriers "
+                      "and the selection", b, p->n_selected, p->n_subcarriers, p0->n_selected, p0->n_subcarriers);
+            return 0;
+        }
+    }
+    if (p0->n_selected < 1) { set_error("cell rate: at least one selected subcarrier is needed"); return 0; }
+    if (m_rx > 8) {
+        set_error("cell rate: M_rx = %lld exceeds the 8 elements of the UE array the kernel supports", m_rx);
+        return 0;
+    }
+    const int kc = p0->n_selected < 64 ? p0->n_selected : 64;
+    for (int b = 0; b < n_links; ++b) {
+        const dmx_params* p = links[b].prm;
+        const long long m_tx = (long long)p->bs_shape[0] * p->bs_shape[1], P = used_paths(p, links[b].n_paths_loaded);
+        if ((unsigned long long)((m_rx + m_tx + kc) * P * 8) > WAVE_LDS_MAX) {
+            set_error("cell rate: link %d: one user's tables, (%lld + %lld + %d) * %lld * 8 = %lld bytes, exceed the %zu bytes of LDS "
+                      "a wave can get", b, m_rx, m_tx, kc, P, (m_rx + m_tx + kc) * P * 8, WAVE_LDS_MAX);
+            return 0;
+        }
+    }
+    return 1;
+}
+
+int dmx_cell_rate_supported(const dmx_link* links, int32_t n_links) { return cell_rate_shape(links, n_links); }
+
+int dmx_cell_rate(const dmx_link* links, int32_t n_links, int64_t n_ue, int64_t user_begin, int64_t user_count,
+                  const int32_t* serving, float* out_rate, float* out_rate_k, int32_t* out_serving, float* out_link_snr,
+                  void* stream) {
+    if (!links) { set_error("links is NULL"); return DMX_ERR_ARG; }
+    const bool count_ok = n_links >= 1 && n_links <= DMX_MAX_LINKS;
+    int rc = DMX_OK;
+    for (int b = 0; count_ok && b < n_links; ++b) {
+        if ((rc = check_params(links[b].prm))) return rc;
+    }
+    if ((rc = check_user_range(n_ue, user_begin, user_count))) return rc;
+    if (user_count > 0 && !out_rate) { set_error("workspace/out is NULL"); return DMX_ERR_ARG; }
+    for (int b = 0; count_ok && b < n_links; ++b) {
+        if (user_count > 0 && !links[b].workspace) { set_error("workspace/out is NULL"); return DMX_ERR_ARG; }
+        if ((rc = check_workspace_aligned(links[b].workspace))) return rc;
+    }
+    if (((uintptr_t)serving & 3u) || ((uintptr_t)out_rate & 3u) || ((uintptr_t)out_rate_k & 3u) || ((uintptr_t)out_serving & 3u) ||
+        ((uintptr_t)out_link_snr & 3u)) {
+        set_error("serving / out_rate / out_rate_k / out_serving / out_link_snr must be 4-byte aligned"); return DMX_ERR_ARG;
+    }
+    for (int b = 0; count_ok && b < n_links; ++b) {
+        if (!links[b].prm->freq_domain) { set_error("dmx_cell_rate called with freq_domain = 0 on link %d", b); return DMX_ERR_ARG; }
+        if (links[b].prm->rx_filter) { set_error("dmx_cell_rate does not cover rx_filter = 1 (link %d)", b); return DMX_ERR_ARG; }
+        // finite and > 0, and so is its square root in float32 (the kernel's scale of the path coefficients)
+        if (!(links[b].snr_linear >= 1e-70) || !(links[b].snr_linear <= 1e70)) {
+            set_error("dmx_cell_rate: snr_linear of link %d must be finite and > 0 (1e-70 .. 1e70), got %g", b, links[b].snr_linear);
+            return DMX_ERR_ARG;
+        }
+    }
+    rc = cell_rate_shape(links, n_links);
+    if (rc < 0) return rc;
+    if (rc == 0) return DMX_ERR_SHAPE;
+    if (user_count == 0) return DMX_OK;
+    return launch_cell_rate(links, n_links, n_ue, user_begin, user_count, serving, out_rate, out_rate_k, out_serving,
+                            out_link_snr, (hipStream_t)stream);
+}
+
 int dmx_channels_td(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                     int64_t user_begin, int64_t user_count, void* out_c64, void* stream) {
     WsView ws;

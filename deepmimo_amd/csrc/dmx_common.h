@@ -163,6 +163,10 @@ int launch_spectrum(const dmx_params& prm, const WsView& ws, int64_t user_begin,
                     float* out_gamma, float* out_rate, float* out_rate_k, hipStream_t stream);
 int launch_precoders(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, double snr_linear,
                      int n_layers, float* out_gamma, float2* out_tx, float2* out_rx, hipStream_t stream);
+size_t cell_rate_lds_bytes(const dmx_link* links, int n_links);
+int launch_cell_rate(const dmx_link* links, int n_links, int64_t n_ue, int64_t user_begin, int64_t user_count,
+                     const int32_t* serving, float* out_rate, float* out_rate_k, int32_t* out_serving, float* out_link_snr,
+                     hipStream_t stream);
 
 // between the stage-2 files: the kernels variant 0 chooses from (k2_channel_fd.hip), their predicates and launchers
 bool fd_mfma_preferred(const dmx_params& prm, const WsView& ws);

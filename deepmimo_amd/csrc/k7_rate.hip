@@ -55,6 +55,7 @@
 // the divisions and square roots of a rotation being dependent chains with one wave per SIMD to hide them.
 #include "dmx_common.h"
 #include "k2_small_body.h"
+#include "k7_rate_body.h"
 #include <math.h>
 
 namespace dmx {
@@ -72,29 +73,7 @@ struct RateArgs {
     int ld;              // table row stride in path slots (= P)
 };
 
-// 4  pivots of I + G by elimination on the upper triangle, each clamped to >= 1: log2 det(I + G)
-template <int M>
-__device__ __forceinline__ float epilogue_logdet(float (&gr)[M * M], float (&gi)[M * M]) {
-    float lg = 0.f;
-#pragma unroll
-    for (int p = 0; p < M; ++p) {
-        const float d = fmaxf(gr[p * M + p] + (p == 0 ? 1.f : 0.f), 1.f);
-        lg += log2f(d);
-        const float inv = 1.f / d;
-#pragma unroll
-        for (int i = p + 1; i < M; ++i) {
-            const float er = gr[p * M + i] * inv, ei = -gi[p * M + i] * inv;         // conj(A_pi) / d
-#pragma unroll
-            for (int j = i; j < M; ++j) {
-                const float xr = gr[p * M + j], xi = gi[p * M + j];
-                gr[i * M + j] -= fmaf(er, xr, -(ei * xi));
-                if (j > i) gi[i * M + j] -= fmaf(er, xi, ei * xr);
-            }
-            if (p == 0) gr[i * M + i] += 1.f;                            // the identity, once per diagonal entry
-        }
-    }
-    return lg;
-}
+// 4  epilogue_logdet, and rows_pair of phase 3: k7_rate_body.h, shared with k8_cell_rate.hip
 
 // sweeps of the Jacobi iteration per m (index 0 unused)
 constexpr int SWEEPS[9] = {0, 0, 2, 5, 6, 6, 7, 8, 8};
@@ -225,28 +204,6 @@ __device__ __forceinline__ void epilogue_vectors(float (&gr)[M * M], float (&gi)
             const float re = xr[j * M + i], im = xi[j * M + i];
             xr[j * M + i] = j == jb ? ab : fmaf(re, pr, im * pi);
             xi[j * M + i] = j == jb ? 0.f : fmaf(im, pr, -(re * pi));
-        }
-    }
-}
-
-// h_i[t] of the two large-array elements whose table rows are b0 and b1, for this lane's subcarrier (wk = w + k)
-template <int M>
-__device__ __forceinline__ void rows_pair(const float2* as, const float2* b0, const float2* b1, const float2* wk, const int ld,
-                                          const int kc, const int n, float2 (&h0)[M], float2 (&h1)[M]) {
-#pragma unroll
-    for (int i = 0; i < M; ++i) h0[i] = h1[i] = make_float2(0.f, 0.f);
-#pragma unroll 2
-    for (int l = 0; l < n; ++l) {
-        const float2 x = wk[l * kc], p0 = b0[l], p1 = b1[l];
-        const float2 q0 = make_float2(fmaf(x.x, p0.x, -(x.y * p0.y)), fmaf(x.x, p0.y, x.y * p0.x));
-        const float2 q1 = make_float2(fmaf(x.x, p1.x, -(x.y * p1.y)), fmaf(x.x, p1.y, x.y * p1.x));
-#pragma unroll
-        for (int i = 0; i < M; ++i) {
-            const float2 v = as[i * ld + l];
-            h0[i].x = fmaf(v.x, q0.x, fmaf(-v.y, q0.y, h0[i].x));
-            h0[i].y = fmaf(v.x, q0.y, fmaf(v.y, q0.x, h0[i].y));
-            h1[i].x = fmaf(v.x, q1.x, fmaf(-v.y, q1.y, h1[i].x));
-            h1[i].y = fmaf(v.x, q1.y, fmaf(v.y, q1.x, h1[i].y));
         }
     }
 }

@@ -761,7 +761,8 @@ class Dataset(DotDict):
 
 class MacroDataset:
     """List of Datasets (one per TX / RX-set pair); attribute access and method calls fan out to
-    every child, a single child returns its value unwrapped (dataset.py:888-998)."""
+    every child, a single child returns its value unwrapped (dataset.py:888-998).  `compute_cell_rate` is the one method
+    of its own: it reads all children in one launch."""
 
     SINGLE_ACCESS_METHODS = {"info"}
     PROPAGATE_METHODS = {name for name, _ in inspect.getmembers(Dataset, predicate=inspect.isfunction)
@@ -790,6 +791,57 @@ class MacroDataset:
             return self._get_single(name)
         res = [getattr(d, name) for d in self.datasets]
         return res[0] if len(res) == 1 else res
+
+    def compute_cell_rate(self, params=None, *, snr_db=None, serving=None, per_subcarrier: bool = False,
+                          details: bool = False):
+        """Per-user downlink rate in bit/s/Hz under inter-cell interference, every child one base station over the same
+        users, with no channel tensor written for any of them (extension):
+
+            rho_b = 10 ** (snr_db_b / 10) / M_tx_b      # snr_db: total transmit power over noise power per subcarrier
+            N_k   = I + sum(rho_b * H_b[u, :, :, k] @ H_b[u, :, :, k].conj().T for b != s)     # s = serving[u]
+            rate_k[u, k] = log2 det(N_k + rho_s * H_s[u, :, :, k] @ H_s[u, :, :, k].conj().T) - log2 det(N_k)
+            rate[u]      = rate_k[u].mean()
+
+        ``params``: one ``ChannelGenParameters`` for all children, or a list with one per child (the BS array may differ;
+        the UE array and the subcarrier selection may not).  ``snr_db`` (required, keyword-only): a scalar, or one value per
+        child.  ``serving``: ``None`` - each user is served by the child of largest ``link_snr`` (the first on ties) - an int
+        for all users, or an int array [n_ue]; a value outside ``0 .. len(self) - 1`` means not served, rate 0.
+
+        Returns ``rate`` float32 [n_ue]; with ``per_subcarrier`` also ``rate_k`` float32 [n_ue, K]; with ``details`` also
+        ``serving`` (int32 [n_ue], -1 = not served) and ``link_snr`` (float32 [n_ue, B], linear: snr_b times the summed power
+        of the child's kept paths, an RSRP-like quantity), in that order: NumPy arrays by default, the HBM-resident torch
+        tensors when ``config('channel_output') == 'torch'``.  One child gives ``Dataset.compute_rate``.  At most 8
+        children with equal ``n_ue``, each within the limits of ``compute_rate`` with the Gram over the UE array (at most 8
+        elements; include/deepmimo_amd.h has the rule): anything else raises ValueError before any GPU work.  Not cached."""
+        from .engine import check_cell_rate_call
+        B = len(self.datasets)
+        if snr_db is None:
+            raise ValueError("compute_cell_rate: snr_db (dB, keyword) is required")
+        if not 1 <= B <= 8:
+            raise ValueError(f"compute_cell_rate: {B} children, the call takes 1..8 base stations")
+        n_ue = int(self.datasets[0].n_ue)
+        if any(int(d.n_ue) != n_ue for d in self.datasets):
+            raise ValueError("compute_cell_rate: the children must cover the same users (equal n_ue), got "
+                             f"{[int(d.n_ue) for d in self.datasets]}")
+        plist = list(params) if isinstance(params, (list, tuple)) else [params] * B
+        if len(plist) != B:
+            raise ValueError(f"compute_cell_rate: {len(plist)} parameter sets for {B} children")
+        if serving is not None and not (isinstance(serving, (int, np.integer)) and not isinstance(serving, bool)):
+            serving = np.asarray(serving)
+            if serving.dtype.kind not in "iu" or serving.shape != (n_ue,):
+                raise ValueError(f"compute_cell_rate: serving must be None, an int or an int array of shape ({n_ue},)")
+        for i, d in enumerate(self.datasets):
+            if plist[i] is None:
+                plist[i] = ChannelGenParameters() if d._data.get(c.CH_PARAMS_PARAM_NAME) is None else d.ch_params
+            d.set_channel_params(plist[i])
+        check_cell_rate_call(plist, [int(np.shape(d[c.POWER_PARAM_NAME])[1]) for d in self.datasets], snr_db)
+        np.random.seed(1001)
+        runs = [d._run_prep(want_side="light") for d in self.datasets]
+        res = runs[0][0].cell_rate([prep for _, prep in runs], snr_db, serving=serving, per_subcarrier=per_subcarrier,
+                                   details=details)
+        if config.get("channel_output", "numpy") == "torch":
+            return res
+        return tuple(t.cpu().numpy() for t in res) if isinstance(res, tuple) else res.cpu().numpy()
 
     def __getitem__(self, idx):
         if isinstance(idx, (int, slice)):

@@ -13,6 +13,7 @@ include/deepmimo_amd.h and calls the C-ABI:
     dmx_channel_rate     -> float32 [N] (and [N, K])    (per-user achievable rate, no channel tensor)
     dmx_channel_spectrum -> float32 [N, K, m], [N], [N, K]  (eigenmode SNRs and water-filling rate, no channel tensor)
     dmx_channel_precoders -> float32 [N, K, m], complex64 [N, K, L, M_tx], [N, K, L, M_rx]  (eigenbeams, no channel tensor)
+    dmx_cell_rate        -> float32 [N] (and [N, K], int32 [N], float32 [N, B])  (rate under inter-cell interference, B links)
 
 It replaces the body of Dataset.compute_channels (deepmimo/generator/dataset.py:224-268).
 No CPU path exists here: without the shared library or without a GPU every entry point raises.
@@ -281,6 +282,55 @@ def check_precoder_call(params, n_paths_loaded: int, snr_db, n_layers) -> float:
     if rc != 1:
         raise ValueError("precoders: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
     return snr
+
+
+def link_snrs_from_db(snr_db, n_links: int):
+    """Linear SNR per link from `snr_db`: a scalar for every link, or a sequence with one entry per link."""
+    if isinstance(snr_db, (list, tuple, np.ndarray)):
+        vals = list(np.asarray(snr_db, dtype=object).ravel()) if isinstance(snr_db, np.ndarray) else list(snr_db)
+        if len(vals) != n_links:
+            raise ValueError(f"cell rate: snr_db holds {len(vals)} values for {n_links} links (one per link, or a scalar)")
+        return [snr_linear_from_db(v) for v in vals]
+    return [snr_linear_from_db(snr_db)] * n_links
+
+
+def check_cell_rate_call(params_list, n_paths_loaded_list, snr_db):
+    """Everything `MacroDataset.compute_cell_rate` can refuse without a GPU, as ValueError: the link count, an snr_db that is
+    not finite (or not one per link), time domain or rx_filter on a link, and links dmx_cell_rate_supported does not take
+    together (the message is the library's and names the limit).  `params_list`: validated ChannelGenParameters, one per
+    link; `n_paths_loaded_list`: loaded paths per link.  Returns the linear SNRs, one per link."""
+    params_list, loaded = list(params_list), list(n_paths_loaded_list)
+    B = len(params_list)
+    if len(loaded) != B:
+        raise ValueError(f"cell rate: {B} parameter sets for {len(loaded)} links")
+    if not 1 <= B <= nat.MAX_LINKS:
+        raise ValueError(f"cell rate: {B} links, the call takes 1..{nat.MAX_LINKS}")
+    snrs = link_snrs_from_db(snr_db, B)
+    links = (nat.DmxLink * B)()
+    keep, first_sel = [], None
+    for b, params in enumerate(params_list):
+        ofdm = params[c.PARAMSET_OFDM]
+        if not params[c.PARAMSET_FD_CH]:
+            raise ValueError(f"cell rate: link {b} needs the frequency-domain channel (freq_domain = 1)")
+        if ofdm[c.PARAMSET_OFDM_LPF]:
+            raise ValueError(f"cell rate: link {b}: ofdm.rx_filter = 1 is not covered")
+        sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
+        if b and not np.array_equal(sel, first_sel):
+            raise ValueError(f"cell rate: link {b} selects other subcarriers than link 0; the links must share the selection")
+        first_sel = sel if b == 0 else first_sel
+        p = nat.DmxParams()
+        _fill_shape_fields(p, params, sel.size)
+        host_sel = (C.c_int32 * max(1, int(sel.size)))()      # the query reads the count, never the array
+        p.selected_subcarriers = C.addressof(host_sel)
+        keep += [p, host_sel]
+        links[b].prm = C.pointer(p)
+        links[b].n_paths_loaded = int(loaded[b])
+        links[b].snr_linear = snrs[b]
+    lib = nat.load()
+    rc = lib.dmx_cell_rate_supported(links, B)
+    if rc != 1:
+        raise ValueError("cell rate: links not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
+    return snrs
 
 
 class ChannelEngine:
@@ -864,6 +914,67 @@ class ChannelEngine:
                                                 ptr[0], ptr[1], ptr[2], self._stream_ptr())
         nat.check(rc, "dmx_channel_precoders")
         return res[0] if len(res) == 1 else tuple(res)
+
+    def _links(self, preps, snrs):
+        links = (nat.DmxLink * len(preps))()
+        for b, prep in enumerate(preps):
+            links[b].prm = C.pointer(prep.params_struct)
+            links[b].workspace = prep.workspace.data_ptr()
+            links[b].n_paths_loaded = prep.n_paths_loaded
+            links[b].snr_linear = snrs[b]
+        return links
+
+    def cell_rate_supported(self, preps) -> bool:
+        """dmx_cell_rate_supported for these preparations, one per link (host-only query; `cell_rate` raises where it says
+        no)."""
+        preps = list(preps)
+        rc = self.lib.dmx_cell_rate_supported(self._links(preps, [1.0] * len(preps)), len(preps))
+        if rc < 0:
+            nat.check(rc, "dmx_cell_rate_supported")
+        return rc == 1
+
+    def cell_rate(self, preps, snr_db, serving=None, user_begin: int = 0, user_count: Optional[int] = None,
+                  per_subcarrier: bool = False, details: bool = False):
+        """dmx_cell_rate: per-user downlink rate in bit/s/Hz under inter-cell interference.  `preps`: one preparation per
+        link (base station) over the same users; `snr_db`: total transmit power over noise power per subcarrier, a scalar or
+        one value per link.  With s the serving link of a user and rho_b = snr_b / M_tx,b,
+        rate[u] = mean over k of log2 det(N_k + rho_s H_s,k H_s,k^H) - log2 det N_k, N_k = I + sum over b != s of
+        rho_b H_b,k H_b,k^H, float32 [user_count] in HBM from the per-path records - no channel tensor is written.
+        `serving`: None (the kernel serves each user by the link of largest link_snr), an int, or an int array / tensor
+        [user_count]; a value outside 0..B-1 means not served (rate 0).  Returns rate; with `per_subcarrier` also rate_k
+        float32 [user_count, K]; with `details` also serving (int32 [user_count], -1 = not served) and link_snr (float32
+        [user_count, B], linear: snr_b times the summed power of the link's kept paths), in that order."""
+        preps = list(preps)
+        B = len(preps)
+        if not 1 <= B <= nat.MAX_LINKS:
+            raise ValueError(f"cell rate: {B} links, the call takes 1..{nat.MAX_LINKS}")
+        snrs = link_snrs_from_db(snr_db, B)
+        n_ue = preps[0].n_ue
+        if any(p.n_ue != n_ue for p in preps):
+            raise ValueError("cell rate: the links must cover the same users (equal n_ue)")
+        if user_count is None:
+            user_count = n_ue - user_begin
+        serv = None
+        if serving is not None:
+            if isinstance(serving, (int, np.integer)) and not isinstance(serving, bool):
+                serv = torch.full((user_count,), int(np.clip(serving, -1, 2 ** 31 - 1)), dtype=torch.int32, device=self.device)
+            else:
+                t = serving if isinstance(serving, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(serving))
+                if t.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or tuple(t.shape) != (user_count,):
+                    raise ValueError(f"cell rate: serving must be None, an int or an integer array of shape ({user_count},)")
+                serv = t.clamp(-1, 2 ** 31 - 1).to(device=self.device, dtype=torch.int32).contiguous()
+        K = int(preps[0].params_struct.n_selected)
+        r = torch.empty((user_count,), dtype=torch.float32, device=self.device)
+        rk = torch.empty((user_count, K), dtype=torch.float32, device=self.device) if per_subcarrier else None
+        sv = torch.empty((user_count,), dtype=torch.int32, device=self.device) if details else None
+        ls = torch.empty((user_count, B), dtype=torch.float32, device=self.device) if details else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None     # noqa: E731
+        with torch.cuda.device(self.device):
+            rc = self.lib.dmx_cell_rate(self._links(preps, snrs), B, n_ue, int(user_begin), int(user_count), ptr(serv),
+                                        ptr(r), ptr(rk), ptr(sv), ptr(ls), self._stream_ptr())
+        nat.check(rc, "dmx_cell_rate")
+        res = (r,) + ((rk,) if per_subcarrier else ()) + ((sv, ls) if details else ())
+        return res[0] if len(res) == 1 else res
 
     def pathloss(self, rays: DeviceRays, coherent: bool = True) -> torch.Tensor:
         """dmx_pathloss: float32 [n_ue] dB (dataset.py:541-566)."""

@@ -376,6 +376,63 @@ int dmx_channel_precoders(const dmx_params* prm, const void* workspace, int64_t 
                           void* out_rx_c64   /* [user_count, K, L, M_rx] or NULL */, void* stream);
 
 /*
+ * Fused consumer of SEVERAL links at once: the downlink rate of every user under inter-cell interference, no channel tensor
+ * written for any link.  Link b = 0 .. n_links-1 stands for one base station: its own dmx_path_prep workspace over the same
+ * n_ue users, its own dmx_params (the BS shape may differ from link to link) and snr_b = snr_linear, the total transmit
+ * power of that base station over the noise power per subcarrier.  With H_{b,k} = H_b[u, :, :, k] and rho_b = snr_b / M_tx,b
+ * (equal power on every antenna, no channel knowledge at the transmitters, as in dmx_channel_rate), for user u with serving
+ * link s = s[u]:
+ *   N_k            = I + sum_{b != s} rho_b H_{b,k} H_{b,k}^H                    (M_rx x M_rx: the other cells as coloured noise)
+ *   A_k            = N_k + rho_s H_{s,k} H_{s,k}^H
+ *   rate_k[u, k]   = log2 det A_k - log2 det N_k                  bit/s/Hz   out_rate_k   float32 [user_count, K], may be NULL
+ *   rate[u]        = 1 / K sum_k rate_k[u, k]                                out_rate     float32 [user_count]
+ *   link_snr[u, b] = snr_b * sum over the kept paths l of |c_{b,l}|^2        out_link_snr float32 [user_count, n_links], may be NULL
+ * c_{b,l} are the coefficients of link b's records, the frequency-domain sqrt(p / N) e^{j phase} with the antenna gains, so
+ * link_snr is the non-coherent wideband receive SNR of an antenna pair (an RSRP-like quantity), linear, clamped to FLT_MAX.
+ * serving: a device int32 [user_count] (entry i belongs to user user_begin + i), any value outside 0 .. n_links-1 meaning "not
+ * served"; or NULL, and the kernel serves every user by argmax_b link_snr[u, b], the first on ties, -1 if no link of the user
+ * has a kept path.  out_serving (int32 [user_count], may be NULL) receives the link each user was served by: the chosen one,
+ * or the given one with every value outside the range replaced by -1.
+ * A user who is not served, or whose serving link has no kept path, gets +0.0 in rate and rate_k.  No value is NaN, infinite
+ * or negative (the difference of the logarithms is clamped to 0 .. FLT_MAX).  n_links = 1 is dmx_channel_rate: where
+ * M_rx <= M_tx the same bits.  The Gram always runs over the UE array, also where M_tx < M_rx.
+ * The kernel is dmx_channel_rate's with one more loop: per chunk of 64 subcarriers the links are taken in link order, each
+ * in the wave's one LDS slice; the interferers add into one register Gram and A_k is formed by adding the serving link's
+ * Gram to those same floats, so an interferer's rounding enters both determinants alike.  fp32 arithmetic in a fixed order,
+ * no atomics: launches repeat bit for bit, a user sub-range equals the same rows of a whole launch, a launch with fewer
+ * outputs writes the same bits, and links whose users have no kept path change nothing.  Subcarrier phases are reduced in
+ * float64: any int32 index is valid.
+ *
+ * dmx_cell_rate_supported - host-only: 1 if dmx_cell_rate takes these links, 0 if not (dmx_last_error() then names the
+ * limit), negative on a bad argument; workspace may be NULL.  Taken: 1 <= n_links <= DMX_MAX_LINKS; every link with
+ * freq_domain = 1, rx_filter = 0 and P_b = min(num_paths, n_paths_loaded) in 1..32; all links with the same ue_shape,
+ * n_subcarriers and n_selected >= 1 - the selection array of link 0 is the one read, the others must hold the same values;
+ * M_rx <= 8; and one wave's tables of the largest link within the LDS:
+ *   max_b (M_rx + M_tx,b + kc) * P_b * 8 bytes <= 156 KB (159744),   kc = min(n_selected, 64)
+ * which does not depend on n_links: the headline shape (64 x 4 BS panel, 2 x 2 UE, 25 paths, 512 subcarriers) is taken for
+ * any number of cells, a 32 x 32 panel on a single link refuses the call.
+ *
+ * dmx_cell_rate - links NULL, a link without params, time domain or rx_filter = 1 on a link, an snr_linear that is not
+ * finite and > 0 (taken: 1e-70 .. 1e70), a NULL workspace or out_rate with user_count > 0: DMX_ERR_ARG; an unsupported
+ * shape or link count: DMX_ERR_SHAPE with the limit in the message; user_count = 0: DMX_OK, nothing done.  Workspaces:
+ * 256-byte aligned; serving and the four outputs: 4-byte aligned device pointers.
+ */
+#define DMX_MAX_LINKS 8
+typedef struct dmx_link {
+    const dmx_params* prm;
+    const void*       workspace;       /* of dmx_path_prep with prm, over the n_ue users of the call */
+    int32_t           n_paths_loaded;
+    double            snr_linear;      /* total transmit power of this link over the noise power per subcarrier */
+} dmx_link;
+int dmx_cell_rate_supported(const dmx_link* links, int32_t n_links);
+int dmx_cell_rate(const dmx_link* links, int32_t n_links, int64_t n_ue, int64_t user_begin, int64_t user_count,
+                  const int32_t* serving     /* device [user_count] or NULL */,
+                  float* out_rate            /* [user_count] */,
+                  float* out_rate_k          /* [user_count, K]       or NULL */,
+                  int32_t* out_serving       /* [user_count]          or NULL */,
+                  float* out_link_snr        /* [user_count, n_links] or NULL */, void* stream);
+
+/*
  * Stage 2, time domain (replaces channel.py:285-287): out[u, rx, tx, s] = a_rx a_tx sqrt(p) e^{j phase}
  * of the s-th valid path (valid paths compacted to the front, remaining slots zero),
  * complex64 [user_count, M_rx, M_tx, P], P = min(num_paths, n_paths_loaded).
