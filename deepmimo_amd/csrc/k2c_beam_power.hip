@@ -265,15 +265,19 @@ __global__ __launch_bounds__(NW * 64, 4) void k2c_beam_power(WsView ws, BeamPowA
 int launch_beam_power(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
                       const float2* codebook, int n_beams, void* beam_ws, float* out_amp, int32_t* out_best, hipStream_t stream) {
     if (user_count == 0 || n_beams == 0) return DMX_OK;
-    BeamTabs t;
-    int rc = launch_beam_project(prm, ws, user_begin, user_count, codebook, n_beams, beam_ws, stream, &t);
-    if (rc) return rc;
     BeamPowArgs a;
     a.user_begin = user_begin;
     a.m_rx = prm.ue_shape[0] * prm.ue_shape[1];
     a.ue_mh = prm.ue_shape[0];
     a.n_beams = n_beams;
     a.M = a.m_rx * n_beams;
+    // a shape this kernel refuses is refused before anything is launched, the projection included
+    const int nw = tuning_int("DMX_BEAM_WAVES", 8) == 4 ? 4 : 8;    // tuning build only
+    const size_t smem = beam_pow_lds_bytes(a.M, nw);
+    if (smem > 160 * 1024) { set_error("%d x %d (rx, beam) rows are too many for the beam-power kernel", a.m_rx, n_beams); return DMX_ERR_SHAPE; }
+    BeamTabs t;
+    int rc = launch_beam_project(prm, ws, user_begin, user_count, codebook, n_beams, beam_ws, stream, &t);
+    if (rc) return rc;
     a.K = prm.n_selected;
     a.sc = prm.selected_subcarriers;
     a.inv_n = 1.0 / (double)prm.n_subcarriers;
@@ -282,9 +286,6 @@ int launch_beam_power(const dmx_params& prm, const WsView& ws, int64_t user_begi
     a.out = out_amp;
     a.best = out_best;
     a.adaptive = (prm.flags & DMX_FLAG_ADAPTIVE_TERMS) ? 1 : 0;     // default: three product terms everywhere
-    const int nw = tuning_int("DMX_BEAM_WAVES", 8) == 4 ? 4 : 8;    // tuning build only
-    const size_t smem = beam_pow_lds_bytes(a.M, nw);
-    if (smem > 160 * 1024) { set_error("%d x %d (rx, beam) rows are too many for the beam-power kernel", a.m_rx, n_beams); return DMX_ERR_SHAPE; }
     const auto kernel = nw == 4 ? k2c_beam_power<4> : k2c_beam_power<8>;
     int64_t grid = resident_workgroups(kernel, nw * 64, smem);
     // a few users per workgroup let the dispatcher balance the tail (k2_channel_fd_mfma.hip: ITEMS_PER_WG)
