@@ -529,6 +529,70 @@ int dmx_cell_rate(const dmx_link* links, int32_t n_links, int64_t n_ue, int64_t 
                             out_link_snr, (hipStream_t)stream);
 }
 
+// 1: taken; 0: not taken, with the limit in the error string; negative: bad argument
+static int angle_delay_shape(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_rows, int32_t n_fft, int32_t n_taps) {
+    if (n_paths_loaded < 0) { set_error("n_paths_loaded must be >= 0"); return DMX_ERR_ARG; }
+    if (!prm->freq_domain || prm->rx_filter) { set_error("angle-delay: needs freq_domain = 1 and rx_filter = 0"); return 0; }
+    if (prm->sc_stride < 1) {
+        set_error("angle-delay: needs a uniformly spaced selection promised by sc_stride > 0 (sc_k = sc_first + k * sc_stride), got "
+                  "sc_stride = %d", prm->sc_stride);
+        return 0;
+    }
+    const int P = used_paths(prm, n_paths_loaded);
+    if (P < 1 || P > 32) {
+        set_error("angle-delay: min(num_paths, loaded paths) = %d is outside the 1..32 paths the kernel supports", P);
+        return 0;
+    }
+    if (prm->n_selected < 1) { set_error("angle-delay: at least one selected subcarrier is needed"); return 0; }
+    const long long m_rx = (long long)prm->ue_shape[0] * prm->ue_shape[1];
+    if (m_rx > 8) { set_error("angle-delay: M_rx = %lld exceeds the 8 UE elements the kernel supports", m_rx); return 0; }
+    if (n_fft < prm->n_selected || n_fft > (1 << 20)) {
+        set_error("angle-delay: n_fft = %d is outside n_selected = %d .. 2^20 = 1048576", n_fft, prm->n_selected);
+        return 0;
+    }
+    if (n_taps < 1 || n_taps > n_fft) { set_error("angle-delay: n_taps = %d is outside 1 .. n_fft = %d", n_taps, n_fft); return 0; }
+    if (n_rows < 1) { set_error("angle-delay: n_rows = %d, at least one row is needed", n_rows); return 0; }
+    if (angle_delay_waves_per_block(*prm, P, n_rows, n_taps) == 0) {
+        const int rc = n_rows < 32 ? n_rows : 32, tc = n_taps < 64 ? n_taps : 64;
+        set_error("angle-delay: one user's tables, (%lld + %d + %d) * %d * 8 = %lld bytes, exceed the %zu bytes of LDS a wave can get",
+                  m_rx, rc, tc, P, (m_rx + rc + tc) * P * 8, WAVE_LDS_MAX);
+        return 0;
+    }
+    return 1;
+}
+
+int dmx_angle_delay_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_rows, int32_t n_fft, int32_t n_taps) {
+    int rc = check_params(prm);
+    if (rc) return rc;
+    return angle_delay_shape(prm, n_paths_loaded, n_rows, n_fft, n_taps);
+}
+
+int dmx_channels_angle_delay(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
+                             int64_t user_begin, int64_t user_count, const void* codebook_c64, int32_t n_rows,
+                             void* beam_workspace, size_t beam_workspace_bytes_, int32_t n_fft, int32_t n_taps, void* out_c64,
+                             void* stream) {
+    WsView ws;
+    int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_c64, &ws);
+    if (rc) return rc;
+    if (!prm->freq_domain) { set_error("dmx_channels_angle_delay called with freq_domain = 0"); return DMX_ERR_ARG; }
+    if (prm->rx_filter) { set_error("dmx_channels_angle_delay does not cover rx_filter = 1"); return DMX_ERR_ARG; }
+    if (prm->sc_stride < 1) {
+        set_error("dmx_channels_angle_delay needs a uniformly spaced selection promised by sc_stride > 0"); return DMX_ERR_ARG;
+    }
+    const int m_tx = prm->bs_shape[0] * prm->bs_shape[1];
+    if (!codebook_c64 && n_rows != m_tx) {
+        set_error("dmx_channels_angle_delay: without a codebook the rows are the %d BS elements, got n_rows = %d", m_tx, n_rows);
+        return DMX_ERR_ARG;
+    }
+    rc = angle_delay_shape(prm, n_paths_loaded, n_rows, n_fft, n_taps);
+    if (rc < 0) return rc;
+    if (rc == 0) return DMX_ERR_SHAPE;
+    if (user_count == 0) return DMX_OK;
+    if (codebook_c64 && (rc = check_beam_workspace(user_count, n_rows, ws.P, beam_workspace, beam_workspace_bytes_))) return rc;
+    return launch_angle_delay(*prm, ws, user_begin, user_count, (const float2*)codebook_c64, n_rows, beam_workspace, n_fft, n_taps,
+                              (float2*)out_c64, (hipStream_t)stream);
+}
+
 int dmx_channels_td(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                     int64_t user_begin, int64_t user_count, void* out_c64, void* stream) {
     WsView ws;

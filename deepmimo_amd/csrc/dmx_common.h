@@ -168,6 +168,11 @@ int launch_cell_rate(const dmx_link* links, int n_links, int64_t n_ue, int64_t u
                      const int32_t* serving, float* out_rate, float* out_rate_k, int32_t* out_serving, float* out_link_snr,
                      hipStream_t stream);
 
+size_t angle_delay_lds_bytes(const dmx_params& prm, int P, int n_rows, int n_taps);
+int angle_delay_waves_per_block(const dmx_params& prm, int P, int n_rows, int n_taps);
+int launch_angle_delay(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, const float2* codebook,
+                       int n_rows, void* beam_ws, int n_fft, int n_taps, float2* out, hipStream_t stream);
+
 // between the stage-2 files: the kernels variant 0 chooses from (k2_channel_fd.hip), their predicates and launchers
 bool fd_mfma_preferred(const dmx_params& prm, const WsView& ws);
 bool fd_small_preferred(const dmx_params& prm, const WsView& ws);

@@ -523,6 +523,49 @@ class Dataset(DotDict):
         res = eng.precoders(prep, snr_db, n_layers=int(n_layers), rx=bool(combiners))
         return tuple(t.cpu().numpy() for t in res) if to_host else res
 
+    def compute_angle_delay(self, params: Optional[ChannelGenParameters] = None, *, n_taps=None, n_fft=None, codebook="dft"):
+        """Angle-delay representation of every user's channel, with no channel tensor written anywhere (extension) - what
+        CSI-feedback, fingerprinting and positioning models train on:
+
+            Y = codebook @ H                                         # [n_ue, M_rx, R, K], H the frequency-domain channel
+            X = np.fft.ifft(Y, n=n_fft, axis=-1)[..., :n_taps]       # the first n_taps delay taps
+
+        ``codebook``: ``"dft"`` (``dm.dft_codebook`` of the BS panel: the angular domain), a complex array [R, M_tx], or
+        ``None`` (the antenna domain: R = M_tx, the delay-domain channel of every antenna pair).  ``n_taps`` is required and
+        keyword-only; ``n_fft=None`` means the number of selected subcarriers.  Returns complex64 [n_ue, M_rx, R, n_taps]: a
+        NumPy array by default, the HBM-resident torch tensor when ``config('channel_output') == 'torch'``.  Users without
+        a path get 0.  Frequency domain without ``rx_filter``, a uniformly spaced selection, at most 32 used paths and 8 UE
+        elements, K <= n_fft <= 2**20, 1 <= n_taps <= n_fft (include/deepmimo_amd.h has the rule): anything else raises
+        ValueError before any GPU work.  Not cached."""
+        from .engine import check_angle_delay_call
+        from .geometry import dft_codebook
+        if n_taps is None:
+            raise ValueError("compute_angle_delay: n_taps (keyword) is required")
+        if params is None:
+            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
+        self.set_channel_params(params)
+        bs_shape = params[c.PARAMSET_ANT_BS][c.PARAMSET_ANT_SHAPE]
+        m_tx = int(bs_shape[0]) * int(bs_shape[1])
+        if codebook is None:
+            cb = None
+        elif isinstance(codebook, str):
+            if codebook != "dft":
+                raise ValueError(f"compute_angle_delay: codebook must be 'dft', an array [R, {m_tx}] or None, got {codebook!r}")
+            cb = dft_codebook(bs_shape)
+        else:
+            cb = codebook if hasattr(codebook, "shape") else np.asarray(codebook)
+            if len(cb.shape) != 2 or cb.shape[1] != m_tx or cb.shape[0] < 1:
+                raise ValueError(f"compute_angle_delay: codebook must be [R, {m_tx}], got {tuple(cb.shape)}")
+        n_rows = m_tx if cb is None else int(cb.shape[0])
+        n_fft = check_angle_delay_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), n_rows, n_fft, n_taps)
+        if config.get("channel_output", "numpy") != "torch":                   # before any GPU work is spent on it
+            m_rx = int(np.prod(params[c.PARAMSET_ANT_UE][c.PARAMSET_ANT_SHAPE]))
+            self._guard_host_copy(8 * int(self.n_ue) * m_rx * n_rows * int(n_taps))
+        np.random.seed(1001)
+        eng, prep = self._run_prep(want_side="light")
+        X = eng.angle_delay(prep, int(n_taps), n_fft=n_fft, tx_codebook=cb)
+        return X if config.get("channel_output", "numpy") == "torch" else X.cpu().numpy()
+
     def compute_pathloss(self, coherent: bool = True) -> np.ndarray:
         """Path loss in dB assuming 0 dBm transmitted power (dataset.py:541-566); cached as ``pathloss``."""
         eng = _engine()

@@ -14,6 +14,7 @@ include/deepmimo_amd.h and calls the C-ABI:
     dmx_channel_spectrum -> float32 [N, K, m], [N], [N, K]  (eigenmode SNRs and water-filling rate, no channel tensor)
     dmx_channel_precoders -> float32 [N, K, m], complex64 [N, K, L, M_tx], [N, K, L, M_rx]  (eigenbeams, no channel tensor)
     dmx_cell_rate        -> float32 [N] (and [N, K], int32 [N], float32 [N, B])  (rate under inter-cell interference, B links)
+    dmx_channels_angle_delay -> complex64 [N, M_rx, R, n_taps]  (codebook x inverse DFT, first delay taps, no channel tensor)
 
 It replaces the body of Dataset.compute_channels (deepmimo/generator/dataset.py:224-268).
 No CPU path exists here: without the shared library or without a GPU every entry point raises.
@@ -282,6 +283,41 @@ def check_precoder_call(params, n_paths_loaded: int, snr_db, n_layers) -> float:
     if rc != 1:
         raise ValueError("precoders: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
     return snr
+
+
+def _int_arg(name: str, v) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError(f"angle-delay: {name} must be an integer, got {v!r}")
+    return int(np.clip(v, -2 ** 31, 2 ** 31 - 1))
+
+
+def check_angle_delay_call(params, n_paths_loaded: int, n_rows, n_fft, n_taps) -> int:
+    """Everything `Dataset.compute_angle_delay` can refuse without a GPU, as ValueError: time domain, rx_filter, a selection
+    that is not uniformly spaced, `n_rows` / `n_fft` / `n_taps` that are no integers, and a shape dmx_angle_delay_supported
+    does not take (the message is the library's and names the limit).  `params`: validated ChannelGenParameters;
+    `n_fft` None = the number of selected subcarriers.  Returns n_fft."""
+    ofdm = params[c.PARAMSET_OFDM]
+    if not params[c.PARAMSET_FD_CH]:
+        raise ValueError("angle-delay: needs the frequency-domain channel (freq_domain = 1)")
+    if ofdm[c.PARAMSET_OFDM_LPF]:
+        raise ValueError("angle-delay: ofdm.rx_filter = 1 is not covered")
+    sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
+    first, stride = uniform_stride(sel)
+    if stride <= 0:
+        raise ValueError("angle-delay: ofdm.selected_subcarriers must be uniformly spaced, first + k * stride with 0 < stride < 2^20 "
+                         "and |first| < 2^30 (the delay transform is an inverse DFT over the selection)")
+    n_fft = int(sel.size) if n_fft is None else _int_arg("n_fft", n_fft)
+    p = nat.DmxParams()
+    _fill_shape_fields(p, params, sel.size)
+    p.sc_first, p.sc_stride = first, stride
+    host_sel = (C.c_int32 * max(1, int(sel.size)))()          # the query reads the count, never the array
+    p.selected_subcarriers = C.addressof(host_sel)
+    lib = nat.load()
+    rc = lib.dmx_angle_delay_supported(C.byref(p), int(n_paths_loaded), _int_arg("n_rows", n_rows), n_fft,
+                                       _int_arg("n_taps", n_taps))
+    if rc != 1:
+        raise ValueError("angle-delay: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
+    return n_fft
 
 
 def link_snrs_from_db(snr_db, n_links: int):
@@ -975,6 +1011,42 @@ class ChannelEngine:
         nat.check(rc, "dmx_cell_rate")
         res = (r,) + ((rk,) if per_subcarrier else ()) + ((sv, ls) if details else ())
         return res[0] if len(res) == 1 else res
+
+    def angle_delay_supported(self, prep: PrepResult, n_rows: int, n_fft: int, n_taps: int) -> bool:
+        """dmx_angle_delay_supported for this preparation (host-only query; `angle_delay` raises where it says no)."""
+        rc = self.lib.dmx_angle_delay_supported(C.byref(prep.params_struct), prep.n_paths_loaded, int(n_rows), int(n_fft),
+                                                int(n_taps))
+        if rc < 0:
+            nat.check(rc, "dmx_angle_delay_supported")
+        return rc == 1
+
+    def angle_delay(self, prep: PrepResult, n_taps: int, n_fft: Optional[int] = None, tx_codebook=None, user_begin: int = 0,
+                    user_count: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dmx_channels_angle_delay: the angle-delay representation ifft(F @ H, n=n_fft, axis=-1)[..., :n_taps] of the
+        frequency-domain channel, complex64 [user_count, M_rx, R, n_taps] in HBM, from the per-path records of `prep` - the
+        channel tensor is not written.  tx_codebook: complex [R, M_tx], or None for the antenna domain (R = M_tx, the
+        delay-domain channel of every antenna pair).  n_fft: None = the number of selected subcarriers.  The selection has
+        to be uniformly spaced."""
+        p = prep.params_struct
+        if user_count is None:
+            user_count = prep.n_ue - user_begin
+        m_rx, m_tx = p.ue_shape[0] * p.ue_shape[1], p.bs_shape[0] * p.bs_shape[1]
+        cb = None if tx_codebook is None else self._codebook(tx_codebook, m_tx, min_beams=1)
+        rows = m_tx if cb is None else int(cb.shape[0])
+        n_fft = int(p.n_selected) if n_fft is None else int(n_fft)
+        out = self._out(out, (user_count, m_rx, rows, max(int(n_taps), 0)))
+        with torch.cuda.device(self.device):
+            nbytes, bws = 0, None
+            if cb is not None and user_count > 0:
+                nbytes = int(self.lib.dmx_beam_workspace_bytes(C.byref(p), user_count, prep.n_paths_loaded, rows))
+                bws = self._scratch(nbytes)
+            rc = self.lib.dmx_channels_angle_delay(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
+                                                   prep.n_paths_loaded, int(user_begin), int(user_count),
+                                                   None if cb is None else C.c_void_p(cb.data_ptr()), rows,
+                                                   None if bws is None else C.c_void_p(bws.data_ptr()), nbytes, n_fft,
+                                                   int(n_taps), C.c_void_p(out.data_ptr()), self._stream_ptr())
+        nat.check(rc, "dmx_channels_angle_delay")
+        return out
 
     def pathloss(self, rays: DeviceRays, coherent: bool = True) -> torch.Tensor:
         """dmx_pathloss: float32 [n_ue] dB (dataset.py:541-566)."""

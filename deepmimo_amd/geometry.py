@@ -3,7 +3,8 @@
 The per-path geometry of the hot path (rotation, FoV, array response) runs on the GPU
 (csrc/k1_path_prep.hip, csrc/k2_channel_fd*.hip).  What stays on the host is the one-vector
 utility ``steering_vec`` (geometry.py:322-339, exported at deepmimo/__init__.py:36-38) that users
-call to build beam codebooks, and the element-index helper it needs."""
+call to build beam codebooks, the orthonormal DFT codebook ``dft_codebook`` (extension: the angular side of
+``Dataset.compute_angle_delay``), and the element-index helper they need."""
 from __future__ import annotations
 
 import numpy as np
@@ -27,3 +28,19 @@ def steering_vec(array, phi: float = 0, theta: float = 0, spacing: float = 0.5) 
     gamma = 1j * kd * np.array([np.sin(zen) * np.cos(az), np.sin(zen) * np.sin(az), np.cos(zen)])
     resp = np.exp(idx @ gamma).reshape(-1, 1)
     return resp / np.linalg.norm(resp)
+
+
+def dft_codebook(shape) -> np.ndarray:
+    """Orthonormal 2-D DFT codebook of an [Mh, Mv] panel, complex64 [M, M] with M = Mh * Mv (extension):
+
+        F[by + Mh * bz, y + Mh * z] = exp(-2j * pi * (by * y / Mh + bz * z / Mv)) / sqrt(M)
+
+    in the element order of `_ant_indices` (y fastest).  Rows are beams: ``F @ H`` is the channel in the angular domain,
+    and ``F @ F.conj().T`` is the identity."""
+    mh, mv = int(shape[0]), int(shape[1])
+    if mh < 1 or mv < 1:
+        raise ValueError(f"dft_codebook: panel shape entries must be >= 1, got {tuple(shape)}")
+    idx = _ant_indices((mh, mv))
+    y, z = idx[:, 1], idx[:, 2]
+    phase = np.outer(y, y) / mh + np.outer(z, z) / mv
+    return (np.exp(-2j * np.pi * phase) / np.sqrt(mh * mv)).astype(np.complex64)

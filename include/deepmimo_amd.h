@@ -433,6 +433,52 @@ int dmx_cell_rate(const dmx_link* links, int32_t n_links, int64_t n_ue, int64_t 
                   float* out_link_snr        /* [user_count, n_links] or NULL */, void* stream);
 
 /*
+ * Fused consumer: the angle-delay representation of the frequency-domain channel - a TX codebook over the BS array and an
+ * inverse DFT over the subcarriers, cut to the first delay taps - what CSI-feedback, fingerprinting and positioning models
+ * train on, from the workspace of dmx_path_prep; H is never written.  H[u, rx, tx, k] is the channel tensor of
+ * dmx_channels_fd (rx_filter = 0) on a uniformly spaced selection sc_k = sc_first + k * sc_stride, k = 0 .. K-1, and F a
+ * codebook [n_rows, M_tx] (complex64, row-major, device) or NULL, the antenna domain: n_rows = M_tx and F = I.
+ *   Y[u, rx, r, k] = sum_tx F[r, tx] H[u, rx, tx, k]
+ *   X[u, rx, r, t] = np.fft.ifft(Y, n=n_fft, axis=-1)[..., :n_taps]
+ *                  = (1 / n_fft) sum_{k<K} Y[u, rx, r, k] e^{+j 2 pi k t / n_fft},   t = 0 .. n_taps-1
+ * out: complex64 interleaved, C-contiguous [user_count, M_rx, n_rows, n_taps], taps fastest - the channel layout with
+ * M_tx -> n_rows and K -> n_taps.  Per path, with c_l the path coefficient (Doppler included), dn_l the clipped sample delay,
+ * a_rx / a_tx the array responses, N = n_subcarriers, d = sc_stride, s0 = sc_first:
+ *   X[u, rx, r, t] = sum_l a_rx[rx, l] f[r, l] c_l D[l, t]
+ *   f[r, l] = sum_tx F[r, tx] a_tx[tx, l]          (the projection of dmx_channels_fd_beams; a_tx itself without a codebook)
+ *   D[l, t] = (1 / n_fft) e^{-j 2 pi frac(dn_l s0 / N)} e^{j pi (K-1) r} sin(pi K r) / sin(pi r)
+ *   r = x - rint(x),   x = t / n_fft - d dn_l / N,   sin(pi K r) / sin(pi r) -> K as r -> 0
+ * D is formed in float64: numerator and denominator by angle addition from per-tap values (t / n_fft, K t / n_fft reduced
+ * in integers) and per-path values (d dn / N, K d dn / N reduced as the exact product), the limit K where |sin(pi r)| <
+ * pi 2^-30 - a path one float32 ulp off a tap keeps 7 digits of the ratio; sc_first may be any int32 (its phase is reduced in
+ * float64, DMX_SC_ABS_MAX_F32 does not apply).  The sums run in fp32 in a fixed order, no atomics: launches repeat bit for
+ * bit and a user sub-range equals the same rows of a whole launch; a user without kept paths gets +0.0 everywhere.
+ * prm->flags changes the order of a user's records and so the summation order only; the workspace of either arithmetic mode
+ * is accepted.  With a codebook the projection runs first into `beam_workspace` (dmx_beam_workspace_bytes(prm, user_count,
+ * n_paths_loaded, n_rows) bytes, 256-byte aligned, device; unused and may be NULL without a codebook); a BS panel the
+ * projection cannot take is DMX_ERR_SHAPE from the call.
+ *
+ * dmx_angle_delay_supported - host-only: 1 if dmx_channels_angle_delay takes this shape, 0 if not (dmx_last_error() then
+ * names the limit), negative on a bad argument.  No GPU involved.  Taken: freq_domain = 1, rx_filter = 0, sc_stride > 0 (a
+ * single subcarrier counts, stride 1), P = min(num_paths, n_paths_loaded) in 1..32, M_rx <= 8,
+ * 1 <= n_selected <= n_fft <= 2^20, 1 <= n_taps <= n_fft, n_rows >= 1, and one wave's tables within the LDS:
+ *   (M_rx + min(n_rows, 32) + tc) * P * 8 bytes <= 156 KB (159744),   tc = min(n_taps, 64)
+ * (the row table goes through the LDS in chunks of 32 rows, the taps in chunks of 64).  With both chunks bounded the rule
+ * refuses nothing the other limits admit: the largest tables, M_rx = 8, n_rows >= 32, n_taps >= 64 at 32 paths, are
+ * (8 + 32 + 64) * 32 * 8 = 26624 bytes, two waves per workgroup; it is what the launcher sizes the workgroup by.
+ *
+ * dmx_channels_angle_delay - time domain, rx_filter = 1, sc_stride = 0 (no spacing promise), or n_rows != M_tx with a NULL
+ * codebook: DMX_ERR_ARG; an unsupported shape: DMX_ERR_SHAPE with the limit in the message; a missing, short or misaligned
+ * beam workspace with a codebook: DMX_ERR_WORKSPACE; user_count = 0: DMX_OK, nothing done.
+ */
+int dmx_angle_delay_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_rows, int32_t n_fft, int32_t n_taps);
+int dmx_channels_angle_delay(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
+                             int64_t user_begin, int64_t user_count,
+                             const void* codebook_c64 /* [n_rows, M_tx] device, or NULL: antenna domain, n_rows = M_tx */,
+                             int32_t n_rows, void* beam_workspace, size_t beam_workspace_bytes /* dmx_beam_workspace_bytes; unused with NULL */,
+                             int32_t n_fft, int32_t n_taps, void* out_c64, void* stream);
+
+/*
  * Stage 2, time domain (replaces channel.py:285-287): out[u, rx, tx, s] = a_rx a_tx sqrt(p) e^{j phase}
  * of the s-th valid path (valid paths compacted to the front, remaining slots zero),
  * complex64 [user_count, M_rx, M_tx, P], P = min(num_paths, n_paths_loaded).
