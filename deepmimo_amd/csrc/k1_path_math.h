@@ -129,6 +129,15 @@ __device__ __forceinline__ void rotate_dir_zero(float el_deg, float az_deg, doub
     sphi = st > 0.0 ? sd : (st < 0.0 ? -sd : 0.0);
 }
 
+// np.angle(re + 1j * im) (geometry.py:308-310), zeros included.  Building the complex number is arithmetic: 1j * im has the
+// real part 0 * im - 1 * 0, which is -0 for a negative (or -0) im and +0 otherwise, and the imaginary part 0 + im, so an
+// im of -0 becomes +0 and a re of -0 becomes +0 unless im carries a sign.  Plain atan2(im, re) differs exactly there: on
+// the branch cut (im = -0, re < 0: -pi instead of +pi, e.g. zero rotation, azimuth 0, elevation 180) and at a pole (re = -0,
+// im = +0: pi instead of 0, e.g. elevation 0 with cos(azimuth) < 0), where the FoV test then sees another azimuth.
+__device__ __forceinline__ double np_angle(double re, double im) {
+    return atan2(im + 0.0, signbit(im) ? re : re + 0.0);
+}
+
 // np.mod(x, 2pi): result takes the sign of the divisor
 __device__ __forceinline__ double pymod_2pi(double x) {
     double m = fmod(x, TWO_PI);
@@ -279,8 +288,8 @@ __device__ __forceinline__ Stage1Path stage1_path(const Stage1Params& a, const d
     double th_r = (isnan(zc_r) || fabs(zc_r) > 1.0) ? nan64 : 0.0, ph_r = (isnan(re_r) || isnan(im_r)) ? nan64 : 0.0;
     if constexpr (!LEAN) {
         if (need_angles) {                               // wave-uniform
-            th_t = acos(zc_t); ph_t = atan2(im_t, re_t);
-            th_r = acos(zc_r); ph_r = atan2(im_r, re_r);
+            th_t = acos(zc_t); ph_t = np_angle(re_t, im_t);
+            th_r = acos(zc_r); ph_r = np_angle(re_r, im_r);
         }
         if (in) {
             if (side.aod_el_rot) side.aod_el_rot[srow + j] = th_t;

@@ -199,8 +199,8 @@ __global__ __launch_bounds__(64 * K1_WAVES, 8 / K1_WAVES) void k1_path_prep_full
         double th_r = (isnan(zc_r) || fabs(zc_r) > 1.0) ? nan64 : 0.0, ph_r = (isnan(re_r) || isnan(im_r)) ? nan64 : 0.0;
         if constexpr (!LEAN) {
             if (a.need_angles) {                             // wave-uniform
-                th_t = acos(zc_t); ph_t = atan2(im_t, re_t);
-                th_r = acos(zc_r); ph_r = atan2(im_r, re_r);
+                th_t = acos(zc_t); ph_t = np_angle(re_t, im_t);
+                th_r = acos(zc_r); ph_r = np_angle(re_r, im_r);
             }
             if (in) {
                 if (a.side.aod_el_rot) a.side.aod_el_rot[srow + j] = th_t;

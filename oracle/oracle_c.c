@@ -87,7 +87,9 @@ static void rotate_angles(float el_deg, float az_deg, const double rot[3], doubl
     const double sd = sin(d), cd = cos(d);
     const double sx = sin(rot[0]), cx = cos(rot[0]), sy = sin(rot[1]), cy = cos(rot[1]);
     *th_rot = acos(cy * cx * ct + st * (sy * cx * cd - sx * sd));                               /* :305-306 */
-    *ph_rot = atan2(cy * sx * ct + st * (sy * sx * cd + cx * sd), cy * st * cd - sy * ct);      /* :308-310 */
+    /* np.angle(re + 1j * im), :308-310: building the complex number adds +0 to im, and to re unless im carries a sign */
+    const double re = cy * st * cd - sy * ct, im = cy * sx * ct + st * (sy * sx * cd + cx * sd);
+    *ph_rot = atan2(im + 0.0, signbit(im) ? re : re + 0.0);
 }
 
 static double pymod_2pi(double x) { /* np.mod: sign of the divisor */
