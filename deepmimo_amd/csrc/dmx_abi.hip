@@ -593,6 +593,74 @@ int dmx_channels_angle_delay(const dmx_params* prm, const void* workspace, int64
                               (float2*)out_c64, (hipStream_t)stream);
 }
 
+// 1: taken; 0: not taken, with the limit in the error string; negative: bad argument
+static int codebook_rate_shape(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_codewords, int32_t n_layers) {
+    if (n_paths_loaded < 0) { set_error("n_paths_loaded must be >= 0"); return DMX_ERR_ARG; }
+    if (!prm->freq_domain || prm->rx_filter) { set_error("codebook rate: needs freq_domain = 1 and rx_filter = 0"); return 0; }
+    const int P = used_paths(prm, n_paths_loaded);
+    if (P < 1 || P > 32) {
+        set_error("codebook rate: min(num_paths, loaded paths) = %d is outside the 1..32 paths the kernel supports", P);
+        return 0;
+    }
+    if (prm->n_selected < 1) { set_error("codebook rate: at least one selected subcarrier is needed"); return 0; }
+    const long long m_rx = (long long)prm->ue_shape[0] * prm->ue_shape[1];
+    if (m_rx > 8) { set_error("codebook rate: M_rx = %lld exceeds the 8 UE elements the kernel supports", m_rx); return 0; }
+    const int l_max = m_rx < 4 ? (int)m_rx : 4;
+    if (n_layers < 1 || n_layers > l_max) {
+        set_error("codebook rate: n_layers = %d is outside 1..min(M_rx, 4) = 1..%d", n_layers, l_max);
+        return 0;
+    }
+    if (n_codewords < 1 || (long long)n_codewords * n_layers > 65536) {
+        set_error("codebook rate: n_codewords = %d with %d layers is outside 1 <= n_codewords, n_codewords * n_layers <= 65536",
+                  n_codewords, n_layers);
+        return 0;
+    }
+    if (codebook_rate_waves_per_block(*prm, P, n_codewords, n_layers) == 0) {
+        const long long rows = (long long)n_codewords * n_layers, rcm = (long long)n_layers * (32 / n_layers);
+        const long long rc = rows < rcm ? rows : rcm, kc = prm->n_selected < 64 ? prm->n_selected : 64;
+        set_error("codebook rate: one user's tables, (%lld + %lld + %lld) * %d * 8 = %lld bytes, exceed the %zu bytes of LDS a wave "
+                  "can get", m_rx, rc, kc, P, (m_rx + rc + kc) * P * 8, WAVE_LDS_MAX);
+        return 0;
+    }
+    return 1;
+}
+
+int dmx_codebook_rate_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_codewords, int32_t n_layers) {
+    int rc = check_params(prm);
+    if (rc) return rc;
+    return codebook_rate_shape(prm, n_paths_loaded, n_codewords, n_layers);
+}
+
+int dmx_codebook_rate(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
+                      int64_t user_begin, int64_t user_count, const void* codebook_c64, int32_t n_codewords, int32_t n_layers,
+                      void* beam_workspace, size_t beam_workspace_bytes_, double snr_linear, float* out_rate, int32_t* out_pmi,
+                      float* out_rate_c, void* stream) {
+    int rc = check_params(prm);
+    if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
+    if (user_count > 0 && (!workspace || !out_rate)) { set_error("workspace/out is NULL"); return DMX_ERR_ARG; }
+    if (user_count > 0 && !codebook_c64) { set_error("codebook missing"); return DMX_ERR_ARG; }
+    if ((rc = check_workspace_aligned(workspace))) return rc;
+    if (((uintptr_t)out_rate & 3u) || ((uintptr_t)out_pmi & 3u) || ((uintptr_t)out_rate_c & 3u)) {
+        set_error("out_rate / out_pmi / out_rate_c must be 4-byte aligned"); return DMX_ERR_ARG;
+    }
+    if ((uintptr_t)codebook_c64 & 7u) { set_error("codebook must be 8-byte aligned"); return DMX_ERR_ARG; }
+    if (!prm->freq_domain) { set_error("dmx_codebook_rate called with freq_domain = 0"); return DMX_ERR_ARG; }
+    if (prm->rx_filter) { set_error("dmx_codebook_rate does not cover rx_filter = 1"); return DMX_ERR_ARG; }
+    // finite and > 0, and so is its square root in float32 (the kernel's scale of the path coefficients)
+    if (!(snr_linear >= 1e-70) || !(snr_linear <= 1e70)) {
+        set_error("dmx_codebook_rate: snr_linear must be finite and > 0 (1e-70 .. 1e70), got %g", snr_linear); return DMX_ERR_ARG;
+    }
+    rc = codebook_rate_shape(prm, n_paths_loaded, n_codewords, n_layers);
+    if (rc < 0) return rc;
+    if (rc == 0) return DMX_ERR_SHAPE;
+    if (user_count == 0) return DMX_OK;
+    WsView ws;
+    ws_carve(const_cast<void*>(workspace), n_ue, used_paths(prm, n_paths_loaded), &ws);
+    if ((rc = check_beam_workspace(user_count, n_codewords * n_layers, ws.P, beam_workspace, beam_workspace_bytes_))) return rc;
+    return launch_codebook_rate(*prm, ws, user_begin, user_count, (const float2*)codebook_c64, n_codewords, n_layers,
+                                beam_workspace, snr_linear, out_rate, out_pmi, out_rate_c, (hipStream_t)stream);
+}
+
 int dmx_channels_td(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                     int64_t user_begin, int64_t user_count, void* out_c64, void* stream) {
     WsView ws;

@@ -173,6 +173,12 @@ int angle_delay_waves_per_block(const dmx_params& prm, int P, int n_rows, int n_
 int launch_angle_delay(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, const float2* codebook,
                        int n_rows, void* beam_ws, int n_fft, int n_taps, float2* out, hipStream_t stream);
 
+size_t codebook_rate_lds_bytes(const dmx_params& prm, int P, int n_codewords, int n_layers);
+int codebook_rate_waves_per_block(const dmx_params& prm, int P, int n_codewords, int n_layers);
+int launch_codebook_rate(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, const float2* codebook,
+                         int n_codewords, int n_layers, void* beam_ws, double snr_linear, float* out_rate, int32_t* out_pmi,
+                         float* out_rate_c, hipStream_t stream);
+
 // between the stage-2 files: the kernels variant 0 chooses from (k2_channel_fd.hip), their predicates and launchers
 bool fd_mfma_preferred(const dmx_params& prm, const WsView& ws);
 bool fd_small_preferred(const dmx_params& prm, const WsView& ws);

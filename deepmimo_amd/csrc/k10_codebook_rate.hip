@@ -1,0 +1,311 @@
+// Fused consumer of the per-path records: the rate of every codeword of a finite precoding codebook and the best codeword per
+// user (the PMI and the rate behind a CQI of a CSI report), without the channel tensor.  W [C, L, M_tx]: C codewords of L
+// layers, row W[c, i, :] multiplying the BS array as a row of F does in k2b_beam_project:
+//   E[c, rx, i, k] = sum_tx W[c, i, tx] H[rx, tx, k] = sum_l a_rx[rx, l] f[c L + i, l] c_l g[l, k],   g[l, k] = exp(-j 2pi dn_l sc_k / N)
+//   rate_c[u, c]   = 1/K sum_k log2 det(I_L + (snr / L) E_{c,k}^H E_{c,k}),   pmi[u] = argmax_c rate_c[u, c] (the first maximum)
+//   rate[u]        = rate_c[u, pmi[u]]
+// f is the row table k2b_beam_project wrote for the flattened codebook [C L, M_tx].  The Gram runs over the LAYERS (L x L,
+// L <= M_rx: the Gram of the columns of E, positive semidefinite by construction), never over the UE array: for L < M_rx the
+// M_rx x M_rx matrix I + s E E^H is rank-deficient beyond the identity and loses its last pivots to cancellation in fp32
+// (k7_rate.hip says the same of its smaller-array rule).  The registers hold conj(E^H E), whose determinant is the same.
+// One WAVE per user as k7_rate / k9_angle_delay: no workgroup barrier, the wave's tables in its own LDS slice, a flat grid.
+//   1  as[M_rx][P]: the a_rx table (k7_rate's phase 1)
+//   2  per chunk of kc = min(K, 64) subcarriers: w[l][k] = sqrt(snr / L) c_l g[l, k] PATH-MAJOR in LDS, the phase reduced in
+//      float64 as the exact product (k7_rate's phase 2: any int32 subcarrier index)
+//   3  ab[rc][P]: a chunk of WHOLE codewords of the row table, rc = L floor(32 / L) rows, copied as k9's phase 2'.  The row
+//      chunks are the outer loop and the subcarrier chunks the inner one: w is rebuilt per pair (P kc sincos against the
+//      rc M_rx P kc products it feeds), and a lane needs one accumulator instead of one per codeword.
+//   4  lane = s kcp + k, kcp the power of two >= kc, S = 64 / kcp slices; slice s takes the codewords s, s + S, ... of the
+//      chunk.  Per (codeword, subcarrier): rows_pair<M_rx> once per pair of layers (the third of three with its own row
+//      again as the dummy, whose unused products the compiler drops), E in registers, the upper triangle of the L x L Gram,
+//      epilogue_logdet<L>.  L = 1: the two rows of a call are two codewords of the slice, which share the reads of w and
+//      a_rx; every row keeps its own chain of operations, so which rows share a call changes no bit.
+//   5  the subcarriers of a chunk are added in a fixed xor tree over the log2(kcp) low lane bits (inactive lanes add +0.0),
+//      which leaves the same bits in every lane of the slice; trip `it` of the codeword loop is kept by the lane whose
+//      subcarrier index is `it` (at most 32 kcp / 64 <= kcp trips), chunk after chunk in chunk order, then times 1/K.  So
+//      the value of a codeword depends on its rows and the user alone: not on its index, the other codewords or the launch.
+//   6  the chunk's rates move to lanes 0 .. nc-1 in codeword order (one coalesced store of rate_c), a fixed xor tree picks
+//      the largest, the lower index on ties, and the chunks are compared in order with a strict >: the first maximum.
+// A user without a kept path: rate +0.0, pmi -1, rate_c +0.0.  LDS of one wave: (M_rx + min(C L, rc) + kc) * P * 8 bytes.
+// Bound: fp32 VALU issue of rows_pair, C L rows of P (1 + M_rx) complex products per subcarrier; the row table is read once,
+// C L P 8 bytes per user.
+#include "dmx_common.h"
+#include "k2_small_body.h"
+#include "k7_rate_body.h"
+#include <math.h>
+
+namespace dmx {
+
+static constexpr int CB_ROWS = 32;           // rows of the row table per LDS chunk, at most (whole codewords only)
+
+struct CbArgs {
+    int64_t user_begin, user_count;
+    int ue_mh;
+    int C;                   // codewords
+    int cpc;                 // codewords per row chunk: floor(32 / L)
+    int K, kc;               // selected subcarriers, subcarriers per chunk = w row stride
+    int kcp, log2_kcp;       // power of two >= kc
+    int S, log2_S;           // codeword slices = 64 / kcp
+    const int32_t* sc;
+    double inv_n;
+    float scale;             // sqrt(snr / L)
+    float inv_k;
+    const float2* ftab;      // [user_count, C L, P] from k2b_beam_project
+    int ld;                  // table row stride in path slots (= P)
+};
+
+template <int M, int L>
+__global__ __launch_bounds__(256) void k10_codebook_rate(WsView ws, CbArgs a, float* __restrict__ out_rate,
+                                                         int32_t* __restrict__ out_pmi, float* __restrict__ out_rate_c) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+    const int64_t ul = (int64_t)blockIdx.x * wpb + wave;
+    if (ul >= a.user_count) return;                                          // waves never talk to each other
+    const int ld = a.ld, C = a.C, K = a.K, kc = a.kc, S = a.S, cpc = a.cpc;
+    const int rows_all = C * L, rc = rows_all < cpc * L ? rows_all : cpc * L;
+    const size_t per_wave = (size_t)(M + rc + kc) * ld;
+    float2* as = reinterpret_cast<float2*>(smem_raw) + (size_t)wave * per_wave;     // [M][ld]
+    float2* ab = as + (size_t)M * ld;                                                // [rc][ld]
+    float2* w = ab + (size_t)rc * ld;                                                // [ld][kc]
+    const int64_t u = a.user_begin + ul;
+    float* oc = out_rate_c ? out_rate_c + (size_t)ul * C : nullptr;
+    int n = __builtin_amdgcn_readfirstlane(ws.n_keep[u]);
+    n = n < ld ? n : ld;
+    if (n <= 0) {                                                            // no kept path
+        if (oc) for (int i = lane; i < C; i += 64) oc[i] = 0.f;
+        if (lane == 0) {
+            out_rate[ul] = 0.f;
+            if (out_pmi) out_pmi[ul] = -1;
+        }
+        return;
+    }
+    const WsRecords rec{ws, (size_t)u * ws.P};
+
+    // 1  the a_rx table
+    for (int i = lane; i < M * n; i += 64) {
+        const int t = i / n, l = i - t * n;
+        float s, c;
+        sincos_rev(frac_rev(__builtin_fma((double)(t % a.ue_mh), rec.rx_y(l), (double)(t / a.ue_mh) * rec.rx_z(l))), s, c);
+        as[t * ld + l] = make_float2(c, s);
+    }
+
+    const int kl = lane & (a.kcp - 1), sl = lane >> a.log2_kcp;              // this lane's subcarrier of the chunk and slice
+    // where lane j finds codeword j of a chunk after phase 5: slice j mod S, trip j / S
+    const int src_lane = ((lane & (S - 1)) << a.log2_kcp) + (lane >> a.log2_S);
+    float best = -1.f;                                                       // every rate is >= 0: the first codeword wins
+    int best_c = -1;
+    for (int c0 = 0; c0 < C; c0 += cpc) {
+        const int nc = C - c0 < cpc ? C - c0 : cpc;
+        // 3  rows c0 L .. (c0 + nc) L of the row table: one contiguous block on both sides
+        wave_lds_fence();                                                    // the last chunk's reads before this chunk's writes
+        {
+            const size_t off = ((size_t)ul * rows_all + (size_t)c0 * L) * ld;
+            const float2* src = a.ftab + off;
+            const int cnt = nc * L * ld;
+            if ((off & 1) == 0) {
+                const float4* s4 = reinterpret_cast<const float4*>(src);
+                for (int i = lane; i < cnt / 2; i += 64) {
+                    const float4 v = s4[i];
+                    ab[2 * i] = make_float2(v.x, v.y); ab[2 * i + 1] = make_float2(v.z, v.w);
+                }
+                if ((cnt & 1) && lane == 0) ab[cnt - 1] = src[cnt - 1];
+            } else {
+                for (int i = lane; i < cnt; i += 64) ab[i] = src[i];
+            }
+        }
+
+        float acc = 0.f;                                                     // of codeword c0 + kl S + sl
+        for (int k0 = 0; k0 < K; k0 += kc) {
+            const int kn = K - k0 < kc ? K - k0 : kc;
+            // 2  w of the chunk
+            wave_lds_fence();
+            for (int i = lane; i < n * kn; i += 64) {
+                const int l = i / kn, k = i - l * kn;
+                float s, c;
+                // the fractional part of the EXACT product x * k (k2_small_body.h)
+                const double x = (double)rec.dn(l) * a.inv_n, kd = (double)a.sc[k0 + k];
+                sincos_rev((float)__builtin_fma(x, kd, -rint(x * kd)), s, c);
+                const float cr = rec.c_re(l) * a.scale, ci = rec.c_im(l) * a.scale;
+                w[l * kc + k] = make_float2(fmaf(cr, c, ci * s), fmaf(ci, c, -(cr * s)));     // c_l (cos - j sin)
+            }
+            wave_lds_fence();
+
+            // 4, 5  one codeword per slice and trip
+            const float2* wk = w + (kl < kn ? kl : 0);
+            int it = 0;
+            if constexpr (L == 1) {
+                // one layer: the two rows of a call are the codewords of trips `it` and `it + 1`
+                for (int cb = 0; cb < nc; cb += 2 * S, it += 2) {
+                    const int ca = cb + sl, cc = cb + S + sl;
+                    float lg0 = 0.f, lg1 = 0.f;
+                    if (kl < kn && ca < nc) {
+                        const bool two = cc < nc;
+                        float2 e0[M], e1[M];
+                        rows_pair<M>(as, ab + (size_t)ca * ld, ab + (size_t)(two ? cc : ca) * ld, wk, ld, kc, n, e0, e1);
+                        float g0[1] = {0.f}, g1[1] = {0.f}, z0[1] = {0.f}, z1[1] = {0.f};
+#pragma unroll
+                        for (int i = 0; i < M; ++i) {                        // rx in index order
+                            g0[0] = fmaf(e0[i].x, e0[i].x, fmaf(e0[i].y, e0[i].y, g0[0]));
+                            g1[0] = fmaf(e1[i].x, e1[i].x, fmaf(e1[i].y, e1[i].y, g1[0]));
+                        }
+                        lg0 = epilogue_logdet<1>(g0, z0);
+                        lg1 = two ? epilogue_logdet<1>(g1, z1) : 0.f;
+                    }
+                    for (int d = 1; d < a.kcp; d <<= 1) {
+                        lg0 += __shfl_xor(lg0, d, 64);
+                        lg1 += __shfl_xor(lg1, d, 64);
+                    }
+                    acc += kl == it ? lg0 : (kl == it + 1 ? lg1 : 0.f);
+                }
+            } else {
+                for (int cb = 0; cb < nc; cb += S, ++it) {
+                    const int ci = cb + sl;
+                    float lg = 0.f;
+                    if (kl < kn && ci < nc) {
+                        const float2* rows = ab + (size_t)ci * L * ld;
+                        float2 e[L + (L & 1)][M];                            // an odd L: the last row is the dummy's
+                        rows_pair<M>(as, rows, rows + ld, wk, ld, kc, n, e[0], e[1]);
+                        if constexpr (L > 2) {
+                            rows_pair<M>(as, rows + (size_t)2 * ld, rows + (size_t)(L > 3 ? 3 : 2) * ld, wk, ld, kc, n, e[2], e[3]);
+                        }
+                        float gr[L * L], gi[L * L];
+#pragma unroll
+                        for (int p = 0; p < L; ++p) {
+#pragma unroll
+                            for (int q = p; q < L; ++q) {                    // G_pq = sum_rx e_p conj(e_q), rx in index order
+                                float r = 0.f, im = 0.f;
+#pragma unroll
+                                for (int i = 0; i < M; ++i) {
+                                    r = fmaf(e[p][i].x, e[q][i].x, fmaf(e[p][i].y, e[q][i].y, r));
+                                    if (q > p) im = fmaf(e[p][i].y, e[q][i].x, fmaf(-e[p][i].x, e[q][i].y, im));
+                                }
+                                gr[p * L + q] = r; gi[p * L + q] = im;
+                                if (q > p) { gr[q * L + p] = 0.f; gi[q * L + p] = 0.f; }
+                            }
+                        }
+                        lg = epilogue_logdet<L>(gr, gi);
+                    }
+                    for (int d = 1; d < a.kcp; d <<= 1) lg += __shfl_xor(lg, d, 64);
+                    acc += kl == it ? lg : 0.f;
+                }
+            }
+        }
+
+        // 6  codeword c0 + j in lane j, stored, and the chunk's first maximum
+        float v = __shfl(acc, src_lane, 64) * a.inv_k;
+        int vi = lane;
+        const bool mine = lane < nc;
+        if (mine && oc) oc[c0 + lane] = v;
+        v = mine ? v : -1.f;
+        for (int d = 1; d < CB_ROWS; d <<= 1) {
+            const float ov = __shfl_xor(v, d, 64);
+            const int oi = __shfl_xor(vi, d, 64);
+            const bool take = ov > v || (ov == v && oi < vi);
+            v = take ? ov : v; vi = take ? oi : vi;
+        }
+        v = __shfl(v, 0, 64); vi = __shfl(vi, 0, 64);
+        if (v > best) { best = v; best_c = c0 + vi; }
+    }
+    if (lane == 0) {
+        out_rate[ul] = best;
+        if (out_pmi) out_pmi[ul] = best_c;
+    }
+}
+
+// LDS bytes of one wave for P path slots (0: the shape is not taken): the a_rx table, one chunk of whole codewords of the
+// row table and one chunk of w,
+//   (M_rx + min(C * L, rc) + kc) * P * 8,   M_rx <= 8,  rc = L * floor(32 / L),  kc = min(n_selected, 64)
+// lds_waves_per_block turns that into 4 / 2 waves per workgroup (at most 26,624 bytes per wave).
+size_t codebook_rate_lds_bytes(const dmx_params& prm, int P, int n_codewords, int n_layers) {
+    if (P < 1 || P > 32 || n_codewords < 1 || n_layers < 1 || n_layers > 4 || prm.n_selected < 1) return 0;
+    const size_t m_rx = (size_t)prm.ue_shape[0] * prm.ue_shape[1];
+    if (m_rx > 8 || (size_t)n_layers > m_rx) return 0;
+    const size_t rows = (size_t)n_codewords * n_layers, rcm = (size_t)n_layers * (CB_ROWS / n_layers);
+    const size_t rc = rows < rcm ? rows : rcm, kc = prm.n_selected < 64 ? prm.n_selected : 64;
+    return (m_rx + rc + kc) * (size_t)P * sizeof(float2);
+}
+
+int codebook_rate_waves_per_block(const dmx_params& prm, int P, int n_codewords, int n_layers) {
+    return lds_waves_per_block(codebook_rate_lds_bytes(prm, P, n_codewords, n_layers));
+}
+
+namespace {
+
+struct CbLaunch {
+    dim3 g, b;
+    size_t smem;
+    hipStream_t stream;
+    const WsView* ws;
+    const CbArgs* a;
+    float* out_rate;
+    int32_t* out_pmi;
+    float* out_rate_c;
+};
+
+template <int M, int L>
+int launch_cb_ml(const CbLaunch& l) {
+    if constexpr (L <= M) {
+        return launch_dyn_lds(k10_codebook_rate<M, L>, "k10_codebook_rate", l.g, l.b, l.smem, WAVE_LDS_MAX, l.stream, *l.ws, *l.a,
+                              l.out_rate, l.out_pmi, l.out_rate_c);
+    } else {
+        set_error("codebook rate: n_layers = %d exceeds M_rx = %d", L, M);
+        return DMX_ERR_SHAPE;
+    }
+}
+
+template <int M>
+int launch_cb_m(const CbLaunch& l, int n_layers) {
+    switch (n_layers) {
+        case 1: return launch_cb_ml<M, 1>(l);
+        case 2: return launch_cb_ml<M, 2>(l);
+        case 3: return launch_cb_ml<M, 3>(l);
+        default: return launch_cb_ml<M, 4>(l);
+    }
+}
+
+}  // namespace
+
+// the projection of the flattened codebook [C L, M_tx] into beam_ws (beam_workspace_bytes), then the kernel
+int launch_codebook_rate(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, const float2* codebook,
+                         int n_codewords, int n_layers, void* beam_ws, double snr_linear, float* out_rate, int32_t* out_pmi,
+                         float* out_rate_c, hipStream_t stream) {
+    if (user_count == 0) return DMX_OK;
+    const int wpb = codebook_rate_waves_per_block(prm, ws.P, n_codewords, n_layers);
+    if (!wpb) { set_error("codebook rate kernel: tables of one user do not fit the LDS"); return DMX_ERR_SHAPE; }
+    BeamTabs t;
+    int rc = launch_beam_project(prm, ws, user_begin, user_count, codebook, n_codewords * n_layers, beam_ws, stream, &t);
+    if (rc) return rc;
+    CbArgs a;
+    a.user_begin = user_begin; a.user_count = user_count;
+    a.ue_mh = prm.ue_shape[0];
+    a.C = n_codewords; a.cpc = CB_ROWS / n_layers;
+    a.K = prm.n_selected; a.kc = a.K < 64 ? a.K : 64;
+    a.log2_kcp = 0;
+    while ((1 << a.log2_kcp) < a.kc) ++a.log2_kcp;
+    a.kcp = 1 << a.log2_kcp;
+    a.log2_S = 6 - a.log2_kcp; a.S = 1 << a.log2_S;
+    a.sc = prm.selected_subcarriers;
+    a.inv_n = 1.0 / (double)prm.n_subcarriers;
+    a.scale = (float)sqrt(snr_linear / (double)n_layers);
+    a.inv_k = (float)(1.0 / (double)a.K);
+    a.ftab = t.ftab;
+    a.ld = ws.P;
+    const int m_rx = prm.ue_shape[0] * prm.ue_shape[1];
+    CbLaunch l;
+    l.smem = (size_t)wpb * codebook_rate_lds_bytes(prm, ws.P, n_codewords, n_layers);
+    l.g = dim3((unsigned)((user_count + wpb - 1) / wpb)); l.b = dim3(64 * wpb);      // flat: one wave per user
+    l.stream = stream; l.ws = &ws; l.a = &a;
+    l.out_rate = out_rate; l.out_pmi = out_pmi; l.out_rate_c = out_rate_c;
+    switch (m_rx) {
+        case 1: return launch_cb_m<1>(l, n_layers);
+        case 2: return launch_cb_m<2>(l, n_layers);
+        case 3: return launch_cb_m<3>(l, n_layers);
+        case 4: return launch_cb_m<4>(l, n_layers);
+        case 5: return launch_cb_m<5>(l, n_layers);
+        case 6: return launch_cb_m<6>(l, n_layers);
+        case 7: return launch_cb_m<7>(l, n_layers);
+        default: return launch_cb_m<8>(l, n_layers);
+    }
+}
+
+}  // namespace dmx

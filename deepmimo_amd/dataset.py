@@ -566,6 +566,56 @@ class Dataset(DotDict):
         X = eng.angle_delay(prep, int(n_taps), n_fft=n_fft, tx_codebook=cb)
         return X if config.get("channel_output", "numpy") == "torch" else X.cpu().numpy()
 
+    def compute_codebook_rate(self, params: Optional[ChannelGenParameters] = None, *, codebook="dft", snr_db=None,
+                              per_codeword: bool = False):
+        """Rate of every codeword of a finite precoding codebook and the best codeword per user - the precoder-matrix
+        indicator (PMI) of a CSI report and the rate behind its CQI - with no channel tensor written anywhere (extension):
+
+            s = 10 ** (snr_db / 10) / L               # snr_db: total transmit power over noise power per subcarrier
+            E = H[u, :, :, k] @ W[c].T                # [M_rx, L]: codeword c, its L layers (rows of W[c]) on the BS array
+            rate_c[u, c] = mean over k of log2 det(I + s * E.conj().T @ E)
+            pmi[u]  = rate_c[u].argmax()              # the first maximum; -1 for a user without a path
+            rate[u] = rate_c[u, pmi[u]]               # 0 for a user without a path
+
+        ``codebook``: ``"dft"`` (``dm.dft_codebook`` of the BS panel as M_tx single-layer codewords), a complex array
+        [C, M_tx] (L = 1) or [C, L, M_tx] with 1 <= L <= min(M_rx, 4).  Codewords are used as given: rows of unit norm keep the
+        transmit power at ``snr_db``.  Returns ``(rate, pmi)`` - float32 [n_ue], int32 [n_ue] - and with ``per_codeword``
+        ``(rate, pmi, rate_c)``, rate_c float32 [n_ue, C]: NumPy arrays by default, the HBM-resident torch tensors when
+        ``config('channel_output') == 'torch'``.  ``snr_db`` is required and keyword-only.  One PMI over the whole selection
+        (no subbands); for rank adaptation call once per L.  Frequency domain without ``rx_filter``, at most 32 used paths
+        and 8 UE elements (include/deepmimo_amd.h has the rule): anything else raises ValueError before any GPU work.  Not
+        cached."""
+        from .engine import check_codebook_rate_call, snr_linear_from_db
+        from .geometry import dft_codebook
+        if snr_db is None:
+            raise ValueError("compute_codebook_rate: snr_db (dB, keyword) is required")
+        snr_linear_from_db(snr_db)
+        if params is None:
+            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
+        self.set_channel_params(params)
+        bs_shape = params[c.PARAMSET_ANT_BS][c.PARAMSET_ANT_SHAPE]
+        m_tx = int(bs_shape[0]) * int(bs_shape[1])
+        what = f"compute_codebook_rate: codebook must be 'dft', an array [C, {m_tx}] or an array [C, L, {m_tx}]"
+        if isinstance(codebook, str):
+            if codebook != "dft":
+                raise ValueError(f"{what}, got {codebook!r}")
+            cb = dft_codebook(bs_shape)
+        elif codebook is None or isinstance(codebook, (bool, int, float, complex)):
+            raise ValueError(f"{what}, got {codebook!r}")
+        else:
+            cb = codebook if hasattr(codebook, "shape") else np.asarray(codebook)
+        if len(cb.shape) == 2:
+            cb = cb[:, None, :]
+        if len(cb.shape) != 3 or cb.shape[2] != m_tx or cb.shape[0] < 1:
+            raise ValueError(f"{what}, got shape {tuple(codebook.shape) if hasattr(codebook, 'shape') else tuple(cb.shape)}")
+        check_codebook_rate_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), int(cb.shape[0]), int(cb.shape[1]), snr_db)
+        np.random.seed(1001)
+        eng, prep = self._run_prep(want_side="light")
+        res = eng.codebook_rate(prep, cb, snr_db, per_codeword=bool(per_codeword))
+        if config.get("channel_output", "numpy") == "torch":
+            return res
+        return tuple(t.cpu().numpy() for t in res)
+
     def compute_pathloss(self, coherent: bool = True) -> np.ndarray:
         """Path loss in dB assuming 0 dBm transmitted power (dataset.py:541-566); cached as ``pathloss``."""
         eng = _engine()

@@ -15,6 +15,7 @@ include/deepmimo_amd.h and calls the C-ABI:
     dmx_channel_precoders -> float32 [N, K, m], complex64 [N, K, L, M_tx], [N, K, L, M_rx]  (eigenbeams, no channel tensor)
     dmx_cell_rate        -> float32 [N] (and [N, K], int32 [N], float32 [N, B])  (rate under inter-cell interference, B links)
     dmx_channels_angle_delay -> complex64 [N, M_rx, R, n_taps]  (codebook x inverse DFT, first delay taps, no channel tensor)
+    dmx_codebook_rate   -> float32 [N], int32 [N], float32 [N, C]  (rate and PMI over a precoding codebook, no channel tensor)
 
 It replaces the body of Dataset.compute_channels (deepmimo/generator/dataset.py:224-268).
 No CPU path exists here: without the shared library or without a GPU every entry point raises.
@@ -318,6 +319,33 @@ def check_angle_delay_call(params, n_paths_loaded: int, n_rows, n_fft, n_taps) -
     if rc != 1:
         raise ValueError("angle-delay: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
     return n_fft
+
+
+def check_codebook_rate_call(params, n_paths_loaded: int, n_codewords, n_layers, snr_db) -> float:
+    """Everything `Dataset.compute_codebook_rate` can refuse without a GPU, as ValueError: an snr_db that is not finite, time
+    domain, rx_filter, `n_codewords` / `n_layers` that are no integers, and a shape dmx_codebook_rate_supported does not take
+    (the message is the library's and names the limit).  `params`: validated ChannelGenParameters.  Returns the linear
+    SNR."""
+    snr = snr_linear_from_db(snr_db)
+    for name, v in (("n_codewords", n_codewords), ("n_layers", n_layers)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"codebook rate: {name} must be an integer, got {v!r}")
+    ofdm = params[c.PARAMSET_OFDM]
+    if not params[c.PARAMSET_FD_CH]:
+        raise ValueError("codebook rate: needs the frequency-domain channel (freq_domain = 1)")
+    if ofdm[c.PARAMSET_OFDM_LPF]:
+        raise ValueError("codebook rate: ofdm.rx_filter = 1 is not covered")
+    sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
+    p = nat.DmxParams()
+    _fill_shape_fields(p, params, sel.size)
+    host_sel = (C.c_int32 * max(1, int(sel.size)))()          # the query reads the count, never the array
+    p.selected_subcarriers = C.addressof(host_sel)
+    lib = nat.load()
+    clip = lambda v: int(np.clip(v, -2 ** 31, 2 ** 31 - 1))   # noqa: E731
+    rc = lib.dmx_codebook_rate_supported(C.byref(p), int(n_paths_loaded), clip(n_codewords), clip(n_layers))
+    if rc != 1:
+        raise ValueError("codebook rate: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
+    return snr
 
 
 def link_snrs_from_db(snr_db, n_links: int):
@@ -1047,6 +1075,59 @@ class ChannelEngine:
                                                    int(n_taps), C.c_void_p(out.data_ptr()), self._stream_ptr())
         nat.check(rc, "dmx_channels_angle_delay")
         return out
+
+    CODEBOOK_WS_BYTES = 1 << 30          # beam workspace of one dmx_codebook_rate call; more users go in blocks
+
+    def codebook_rate_supported(self, prep: PrepResult, n_codewords: int, n_layers: int = 1) -> bool:
+        """dmx_codebook_rate_supported for this preparation (host-only query; `codebook_rate` raises where it says no)."""
+        rc = self.lib.dmx_codebook_rate_supported(C.byref(prep.params_struct), prep.n_paths_loaded, int(n_codewords),
+                                                  int(n_layers))
+        if rc < 0:
+            nat.check(rc, "dmx_codebook_rate_supported")
+        return rc == 1
+
+    def codebook_rate(self, prep: PrepResult, codebook, snr_db, per_codeword: bool = False, user_begin: int = 0,
+                      user_count: Optional[int] = None):
+        """dmx_codebook_rate: the rate of every codeword of a precoding codebook and the best one per user at `snr_db` (total
+        transmit power over noise power per subcarrier, split equally over the layers), from the per-path records of `prep` -
+        neither the channel tensor nor the beam-space tensor is written.  `codebook`: complex [C, L, M_tx], C codewords of
+        L layers (a 2-D [C, M_tx] is L = 1).  With E = W[c] @ H[u, :, :, k] transposed to M_rx x L,
+        rate_c[u, c] = mean over k of log2 det(I + snr / L E^H E).  Returns (rate float32 [user_count], pmi int32
+        [user_count]) - pmi the first codeword of the largest rate, -1 and rate 0 for a user without a path - and with
+        `per_codeword` also rate_c float32 [user_count, C], all in HBM.  Users go in blocks whose beam workspace stays within
+        CODEBOOK_WS_BYTES; a block equals the same rows of one launch bit for bit."""
+        snr = snr_linear_from_db(snr_db)
+        p = prep.params_struct
+        if user_count is None:
+            user_count = prep.n_ue - user_begin
+        m_tx = p.bs_shape[0] * p.bs_shape[1]
+        cb = codebook if isinstance(codebook, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(codebook))
+        if cb.dim() == 2:
+            cb = cb[:, None, :]
+        if cb.dim() != 3 or cb.shape[2] != m_tx or cb.shape[0] < 1 or cb.shape[1] < 1:
+            raise ValueError(f"codebook must be [C, L, {m_tx}] or [C, {m_tx}], got {tuple(cb.shape)}")
+        cb = cb.to(device=self.device, dtype=torch.complex64).contiguous()
+        n_cw, n_layers = int(cb.shape[0]), int(cb.shape[1])
+        if not self.codebook_rate_supported(prep, n_cw, n_layers):   # DMX_ERR_SHAPE, before anything is allocated
+            nat.check(-2, "dmx_codebook_rate")
+        rate = torch.empty((user_count,), dtype=torch.float32, device=self.device)
+        pmi = torch.empty((user_count,), dtype=torch.int32, device=self.device)
+        rate_c = torch.empty((user_count, n_cw), dtype=torch.float32, device=self.device) if per_codeword else None
+        per_user = n_cw * n_layers * max(1, min(int(p.num_paths), prep.n_paths_loaded)) * 8 + 4
+        block = max(1, (int(self.CODEBOOK_WS_BYTES) - 512) // per_user)
+        with torch.cuda.device(self.device):
+            for b in range(0, user_count, block):
+                cnt = min(block, user_count - b)
+                nbytes = int(self.lib.dmx_beam_workspace_bytes(C.byref(p), cnt, prep.n_paths_loaded, n_cw * n_layers))
+                bws = self._scratch(nbytes)
+                rc = self.lib.dmx_codebook_rate(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
+                                                prep.n_paths_loaded, int(user_begin) + b, cnt, C.c_void_p(cb.data_ptr()),
+                                                n_cw, n_layers, C.c_void_p(bws.data_ptr()), nbytes, snr,
+                                                C.c_void_p(rate[b:].data_ptr()), C.c_void_p(pmi[b:].data_ptr()),
+                                                C.c_void_p(rate_c[b:].data_ptr()) if per_codeword else None,
+                                                self._stream_ptr())
+                nat.check(rc, "dmx_codebook_rate")
+        return (rate, pmi, rate_c) if per_codeword else (rate, pmi)
 
     def pathloss(self, rays: DeviceRays, coherent: bool = True) -> torch.Tensor:
         """dmx_pathloss: float32 [n_ue] dB (dataset.py:541-566)."""

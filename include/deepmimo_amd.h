@@ -479,6 +479,55 @@ int dmx_channels_angle_delay(const dmx_params* prm, const void* workspace, int64
                              int32_t n_fft, int32_t n_taps, void* out_c64, void* stream);
 
 /*
+ * Fused consumer: the rate of every codeword of a finite precoding codebook and the best codeword per user - the precoder-
+ * matrix indicator (PMI) of a CSI report and the rate behind its channel-quality indicator - from the workspace of
+ * dmx_path_prep; H is never written.  W is a codebook [n_codewords, n_layers, M_tx] (complex64, row-major, device) of C
+ * codewords with L layers each; row W[c, i, :] multiplies the BS array as a row of F does in dmx_channels_fd_beams, and
+ * H[u, rx, tx, k] is the channel tensor of dmx_channels_fd (rx_filter = 0):
+ *   E[u, c, rx, i, k] = sum_tx W[c, i, tx] H[u, rx, tx, k]                          (M_rx x L per codeword and subcarrier)
+ *   rate_c[u, c]      = 1 / K sum_k log2 det(I_L + (snr_linear / L) E_{c,k}^H E_{c,k})   out_rate_c float32 [user_count, C], may be NULL
+ *   pmi[u]            = argmax_c rate_c[u, c], the first maximum                    out_pmi    int32   [user_count], may be NULL
+ *   rate[u]           = rate_c[u, pmi[u]]                                           out_rate   float32 [user_count]
+ * snr_linear, the total transmit power over the noise power per subcarrier, is split equally over the L layers.  Codewords are
+ * used as given: rows of unit norm keep the transmit power at snr_linear, and that is the caller's business.  The Gram is
+ * formed over the layers (L x L, L <= M_rx, positive semidefinite by construction), never over the UE array, whose
+ * I + s E E^H is rank-deficient beyond the identity for L < M_rx; the pivots of the elimination are clamped to >= 1 as in
+ * dmx_channel_rate.  A user without kept paths gets rate +0.0, pmi -1 and +0.0 in every rate_c.  No output is NaN, infinite
+ * or negative.  The projection of the flattened codebook [C * L, M_tx] runs first into `beam_workspace`
+ * (dmx_beam_workspace_bytes(prm, user_count, n_paths_loaded, C * L) bytes, 256-byte aligned, device); the kernel then streams
+ * that table through the LDS in chunks of whole codewords, L * floor(32 / L) rows.  fp32 arithmetic in a fixed order, no
+ * atomics: launches repeat bit for bit, a user sub-range equals the same rows of a whole launch, a launch with fewer outputs
+ * writes the same bits, and the rate of a codeword depends on neither its index nor the other codewords (a repeated codeword
+ * repeats its bits; the PMI is then the first).  Subcarrier phases are reduced in float64: any int32 index is valid,
+ * DMX_SC_ABS_MAX_F32 does not apply.  prm->flags changes the order of a user's records and so the summation order only; the
+ * workspace of either arithmetic mode is accepted.
+ * Not covered: a PMI per subband, rank adaptation (call once per L and compare), L > 4 or L > M_rx, the time domain and
+ * rx_filter = 1.
+ *
+ * dmx_codebook_rate_supported - host-only: 1 if dmx_codebook_rate takes this shape, 0 if not (dmx_last_error() then names the
+ * limit), negative on a bad argument.  No GPU involved.  Taken: freq_domain = 1, rx_filter = 0,
+ * P = min(num_paths, n_paths_loaded) in 1..32, n_selected >= 1, M_rx <= 8, 1 <= n_layers <= min(M_rx, 4), n_codewords >= 1,
+ * n_codewords * n_layers <= 65536, and one wave's tables within the LDS:
+ *   (M_rx + min(C * L, rc) + kc) * P * 8 bytes <= 156 KB (159744),   rc = L * floor(32 / L),  kc = min(n_selected, 64)
+ * With both chunks bounded the rule refuses nothing the other limits admit: the largest tables, M_rx = 8, 32 rows and 64
+ * subcarriers at 32 paths, are (8 + 32 + 64) * 32 * 8 = 26624 bytes, two waves per workgroup; it is what the launcher sizes
+ * the workgroup by.
+ *
+ * dmx_codebook_rate - time domain, rx_filter = 1, a NULL codebook or out_rate with user_count > 0, an snr_linear that is not
+ * finite and > 0 (taken: 1e-70 .. 1e70): DMX_ERR_ARG; an unsupported shape, or a BS panel the projection cannot take:
+ * DMX_ERR_SHAPE with the limit in the message; a missing, short or misaligned beam workspace: DMX_ERR_WORKSPACE;
+ * user_count = 0: DMX_OK, nothing done.  workspace: 256-byte aligned; codebook: 8-byte, the outputs: 4-byte aligned device
+ * pointers.
+ */
+int dmx_codebook_rate_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_codewords, int32_t n_layers);
+int dmx_codebook_rate(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
+                      int64_t user_begin, int64_t user_count,
+                      const void* codebook_c64 /* [n_codewords, n_layers, M_tx] device */, int32_t n_codewords, int32_t n_layers,
+                      void* beam_workspace, size_t beam_workspace_bytes /* dmx_beam_workspace_bytes(prm, user_count, n_paths_loaded, C * L) */,
+                      double snr_linear, float* out_rate /* [user_count] */, int32_t* out_pmi /* [user_count] or NULL */,
+                      float* out_rate_c /* [user_count, C] or NULL */, void* stream);
+
+/*
  * Stage 2, time domain (replaces channel.py:285-287): out[u, rx, tx, s] = a_rx a_tx sqrt(p) e^{j phase}
  * of the s-th valid path (valid paths compacted to the front, remaining slots zero),
  * complex64 [user_count, M_rx, M_tx, P], P = min(num_paths, n_paths_loaded).
