@@ -23,7 +23,8 @@ EXPORTED_SYMBOLS = ("dmx_version", "dmx_last_error", "dmx_workspace_bytes", "dmx
                     "dmx_channel_covariance", "dmx_rate_supported", "dmx_channel_rate",
                     "dmx_spectrum_supported", "dmx_channel_spectrum", "dmx_precoder_supported", "dmx_channel_precoders",
                     "dmx_cell_rate_supported", "dmx_cell_rate", "dmx_angle_delay_supported", "dmx_channels_angle_delay",
-                    "dmx_codebook_rate_supported", "dmx_codebook_rate")
+                    "dmx_codebook_rate_supported", "dmx_codebook_rate", "dmx_codebook_rate_subbands_supported",
+                    "dmx_codebook_rate_subbands")
 
 MAX_LINKS = 8                             # DMX_MAX_LINKS
 PATTERN_IDS = {"isotropic": 0, "halfwave-dipole": 1}
@@ -147,6 +148,13 @@ def load():
     lib.dmx_codebook_rate.argtypes = [C.POINTER(DmxParams), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
                                       C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dmx_codebook_rate_subbands_supported.restype = C.c_int
+    lib.dmx_codebook_rate_subbands_supported.argtypes = [C.POINTER(DmxParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.dmx_codebook_rate_subbands.restype = C.c_int
+    lib.dmx_codebook_rate_subbands.argtypes = [C.POINTER(DmxParams), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
+                                               C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_double, C.c_int32,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
     lib.dmx_decode_max_delay.restype = C.c_float
     lib.dmx_decode_max_delay.argtypes = [C.c_uint32]
     lib.dmx_path_prep.restype = C.c_int

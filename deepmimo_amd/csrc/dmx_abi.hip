@@ -631,25 +631,34 @@ int dmx_codebook_rate_supported(const dmx_params* prm, int32_t n_paths_loaded, i
     return codebook_rate_shape(prm, n_paths_loaded, n_codewords, n_layers);
 }
 
+// the checks dmx_codebook_rate and dmx_codebook_rate_subbands share, up to the shape; `out` is the output that must not be NULL,
+// `out_bits` the addresses of all outputs or'ed together and `out_names` their names for the message
+static int codebook_rate_args(const char* fn, const dmx_params* prm, const void* workspace, int64_t n_ue, int64_t user_begin,
+                              int64_t user_count, const void* codebook_c64, double snr_linear, const void* out, uintptr_t out_bits,
+                              const char* out_names) {
+    int rc = check_params(prm);
+    if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
+    if (user_count > 0 && (!workspace || !out)) { set_error("workspace/out is NULL"); return DMX_ERR_ARG; }
+    if (user_count > 0 && !codebook_c64) { set_error("codebook missing"); return DMX_ERR_ARG; }
+    if ((rc = check_workspace_aligned(workspace))) return rc;
+    if (out_bits & 3u) { set_error("%s must be 4-byte aligned", out_names); return DMX_ERR_ARG; }
+    if ((uintptr_t)codebook_c64 & 7u) { set_error("codebook must be 8-byte aligned"); return DMX_ERR_ARG; }
+    if (!prm->freq_domain) { set_error("%s called with freq_domain = 0", fn); return DMX_ERR_ARG; }
+    if (prm->rx_filter) { set_error("%s does not cover rx_filter = 1", fn); return DMX_ERR_ARG; }
+    // finite and > 0, and so is its square root in float32 (the kernel's scale of the path coefficients)
+    if (!(snr_linear >= 1e-70) || !(snr_linear <= 1e70)) {
+        set_error("%s: snr_linear must be finite and > 0 (1e-70 .. 1e70), got %g", fn, snr_linear); return DMX_ERR_ARG;
+    }
+    return DMX_OK;
+}
+
 int dmx_codebook_rate(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                       int64_t user_begin, int64_t user_count, const void* codebook_c64, int32_t n_codewords, int32_t n_layers,
                       void* beam_workspace, size_t beam_workspace_bytes_, double snr_linear, float* out_rate, int32_t* out_pmi,
                       float* out_rate_c, void* stream) {
-    int rc = check_params(prm);
-    if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
-    if (user_count > 0 && (!workspace || !out_rate)) { set_error("workspace/out is NULL"); return DMX_ERR_ARG; }
-    if (user_count > 0 && !codebook_c64) { set_error("codebook missing"); return DMX_ERR_ARG; }
-    if ((rc = check_workspace_aligned(workspace))) return rc;
-    if (((uintptr_t)out_rate & 3u) || ((uintptr_t)out_pmi & 3u) || ((uintptr_t)out_rate_c & 3u)) {
-        set_error("out_rate / out_pmi / out_rate_c must be 4-byte aligned"); return DMX_ERR_ARG;
-    }
-    if ((uintptr_t)codebook_c64 & 7u) { set_error("codebook must be 8-byte aligned"); return DMX_ERR_ARG; }
-    if (!prm->freq_domain) { set_error("dmx_codebook_rate called with freq_domain = 0"); return DMX_ERR_ARG; }
-    if (prm->rx_filter) { set_error("dmx_codebook_rate does not cover rx_filter = 1"); return DMX_ERR_ARG; }
-    // finite and > 0, and so is its square root in float32 (the kernel's scale of the path coefficients)
-    if (!(snr_linear >= 1e-70) || !(snr_linear <= 1e70)) {
-        set_error("dmx_codebook_rate: snr_linear must be finite and > 0 (1e-70 .. 1e70), got %g", snr_linear); return DMX_ERR_ARG;
-    }
+    int rc = codebook_rate_args("dmx_codebook_rate", prm, workspace, n_ue, user_begin, user_count, codebook_c64, snr_linear, out_rate,
+                                (uintptr_t)out_rate | (uintptr_t)out_pmi | (uintptr_t)out_rate_c, "out_rate / out_pmi / out_rate_c");
+    if (rc) return rc;
     rc = codebook_rate_shape(prm, n_paths_loaded, n_codewords, n_layers);
     if (rc < 0) return rc;
     if (rc == 0) return DMX_ERR_SHAPE;
@@ -659,6 +668,48 @@ int dmx_codebook_rate(const dmx_params* prm, const void* workspace, int64_t n_ue
     if ((rc = check_beam_workspace(user_count, n_codewords * n_layers, ws.P, beam_workspace, beam_workspace_bytes_))) return rc;
     return launch_codebook_rate(*prm, ws, user_begin, user_count, (const float2*)codebook_c64, n_codewords, n_layers,
                                 beam_workspace, snr_linear, out_rate, out_pmi, out_rate_c, (hipStream_t)stream);
+}
+
+// the shape of dmx_codebook_rate and a subband size >= 1; the subband form keeps min(subband_size, n_selected, 64) subcarriers
+// of w in the LDS where the wideband one keeps min(n_selected, 64), so the LDS rule refuses nothing more
+static int codebook_rate_subbands_shape(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_codewords, int32_t n_layers,
+                                        int32_t subband_size) {
+    if (subband_size < 1) { set_error("codebook rate: subband_size = %d must be >= 1", subband_size); return DMX_ERR_ARG; }
+    const int rc = codebook_rate_shape(prm, n_paths_loaded, n_codewords, n_layers);
+    if (rc != 1) return rc;
+    if (codebook_rate_subbands_waves_per_block(*prm, used_paths(prm, n_paths_loaded), n_codewords, n_layers, subband_size) == 0) {
+        set_error("codebook rate: one user's tables of the subband form exceed the %zu bytes of LDS a wave can get", WAVE_LDS_MAX);
+        return 0;
+    }
+    return 1;
+}
+
+int dmx_codebook_rate_subbands_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_codewords, int32_t n_layers,
+                                         int32_t subband_size) {
+    int rc = check_params(prm);
+    if (rc) return rc;
+    return codebook_rate_subbands_shape(prm, n_paths_loaded, n_codewords, n_layers, subband_size);
+}
+
+int dmx_codebook_rate_subbands(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
+                               int64_t user_begin, int64_t user_count, const void* codebook_c64, int32_t n_codewords,
+                               int32_t n_layers, void* beam_workspace, size_t beam_workspace_bytes_, double snr_linear,
+                               int32_t subband_size, float* out_rate_sb, int32_t* out_pmi_sb, float* out_rate_sb_c, float* out_rate,
+                               int32_t* out_pmi, float* out_rate_c, void* stream) {
+    int rc = codebook_rate_args("dmx_codebook_rate_subbands", prm, workspace, n_ue, user_begin, user_count, codebook_c64, snr_linear,
+                                out_rate_sb, (uintptr_t)out_rate_sb | (uintptr_t)out_pmi_sb | (uintptr_t)out_rate_sb_c |
+                                (uintptr_t)out_rate | (uintptr_t)out_pmi | (uintptr_t)out_rate_c, "the outputs");
+    if (rc) return rc;
+    rc = codebook_rate_subbands_shape(prm, n_paths_loaded, n_codewords, n_layers, subband_size);
+    if (rc < 0) return rc;
+    if (rc == 0) return DMX_ERR_SHAPE;
+    if (user_count == 0) return DMX_OK;
+    WsView ws;
+    ws_carve(const_cast<void*>(workspace), n_ue, used_paths(prm, n_paths_loaded), &ws);
+    if ((rc = check_beam_workspace(user_count, n_codewords * n_layers, ws.P, beam_workspace, beam_workspace_bytes_))) return rc;
+    return launch_codebook_rate_subbands(*prm, ws, user_begin, user_count, (const float2*)codebook_c64, n_codewords, n_layers,
+                                         beam_workspace, snr_linear, subband_size, out_rate_sb, out_pmi_sb, out_rate_sb_c, out_rate,
+                                         out_pmi, out_rate_c, (hipStream_t)stream);
 }
 
 int dmx_channels_td(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,

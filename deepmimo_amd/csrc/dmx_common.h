@@ -178,6 +178,12 @@ int codebook_rate_waves_per_block(const dmx_params& prm, int P, int n_codewords,
 int launch_codebook_rate(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, const float2* codebook,
                          int n_codewords, int n_layers, void* beam_ws, double snr_linear, float* out_rate, int32_t* out_pmi,
                          float* out_rate_c, hipStream_t stream);
+size_t codebook_rate_subbands_lds_bytes(const dmx_params& prm, int P, int n_codewords, int n_layers, int subband_size);
+int codebook_rate_subbands_waves_per_block(const dmx_params& prm, int P, int n_codewords, int n_layers, int subband_size);
+int launch_codebook_rate_subbands(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
+                                  const float2* codebook, int n_codewords, int n_layers, void* beam_ws, double snr_linear,
+                                  int subband_size, float* out_rate_sb, int32_t* out_pmi_sb, float* out_rate_sb_c, float* out_rate,
+                                  int32_t* out_pmi, float* out_rate_c, hipStream_t stream);
 
 // between the stage-2 files: the kernels variant 0 chooses from (k2_channel_fd.hip), their predicates and launchers
 bool fd_mfma_preferred(const dmx_params& prm, const WsView& ws);

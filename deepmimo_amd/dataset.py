@@ -63,6 +63,28 @@ def _engine():
     return _engines[dev]
 
 
+def _precoding_codebook(who: str, params, codebook):
+    """The `codebook` argument of the codebook-rate methods as an array [C, L, M_tx]: "dft", [C, M_tx] or [C, L, M_tx]; anything
+    else is a ValueError that starts with `who`."""
+    from .geometry import dft_codebook
+    bs_shape = params[c.PARAMSET_ANT_BS][c.PARAMSET_ANT_SHAPE]
+    m_tx = int(bs_shape[0]) * int(bs_shape[1])
+    what = f"{who}: codebook must be 'dft', an array [C, {m_tx}] or an array [C, L, {m_tx}]"
+    if isinstance(codebook, str):
+        if codebook != "dft":
+            raise ValueError(f"{what}, got {codebook!r}")
+        cb = dft_codebook(bs_shape)
+    elif codebook is None or isinstance(codebook, (bool, int, float, complex)):
+        raise ValueError(f"{what}, got {codebook!r}")
+    else:
+        cb = codebook if hasattr(codebook, "shape") else np.asarray(codebook)
+    if len(cb.shape) == 2:
+        cb = cb[:, None, :]
+    if len(cb.shape) != 3 or cb.shape[2] != m_tx or cb.shape[0] < 1:
+        raise ValueError(f"{what}, got shape {tuple(codebook.shape) if hasattr(codebook, 'shape') else tuple(cb.shape)}")
+    return cb
+
+
 class Dataset(DotDict):
     """One (TX, RX-set) pair of ray-tracing results plus everything computed from it."""
 
@@ -581,33 +603,18 @@ class Dataset(DotDict):
         [C, M_tx] (L = 1) or [C, L, M_tx] with 1 <= L <= min(M_rx, 4).  Codewords are used as given: rows of unit norm keep the
         transmit power at ``snr_db``.  Returns ``(rate, pmi)`` - float32 [n_ue], int32 [n_ue] - and with ``per_codeword``
         ``(rate, pmi, rate_c)``, rate_c float32 [n_ue, C]: NumPy arrays by default, the HBM-resident torch tensors when
-        ``config('channel_output') == 'torch'``.  ``snr_db`` is required and keyword-only.  One PMI over the whole selection
-        (no subbands); for rank adaptation call once per L.  Frequency domain without ``rx_filter``, at most 32 used paths
-        and 8 UE elements (include/deepmimo_amd.h has the rule): anything else raises ValueError before any GPU work.  Not
-        cached."""
+        ``config('channel_output') == 'torch'``.  ``snr_db`` is required and keyword-only.  One PMI over the whole selection;
+        ``compute_subband_pmi`` adds a PMI per subband and ``compute_csi_report`` the rank.  Frequency domain without
+        ``rx_filter``, at most 32 used paths and 8 UE elements (include/deepmimo_amd.h has the rule): anything else raises
+        ValueError before any GPU work.  Not cached."""
         from .engine import check_codebook_rate_call, snr_linear_from_db
-        from .geometry import dft_codebook
         if snr_db is None:
             raise ValueError("compute_codebook_rate: snr_db (dB, keyword) is required")
         snr_linear_from_db(snr_db)
         if params is None:
             params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
         self.set_channel_params(params)
-        bs_shape = params[c.PARAMSET_ANT_BS][c.PARAMSET_ANT_SHAPE]
-        m_tx = int(bs_shape[0]) * int(bs_shape[1])
-        what = f"compute_codebook_rate: codebook must be 'dft', an array [C, {m_tx}] or an array [C, L, {m_tx}]"
-        if isinstance(codebook, str):
-            if codebook != "dft":
-                raise ValueError(f"{what}, got {codebook!r}")
-            cb = dft_codebook(bs_shape)
-        elif codebook is None or isinstance(codebook, (bool, int, float, complex)):
-            raise ValueError(f"{what}, got {codebook!r}")
-        else:
-            cb = codebook if hasattr(codebook, "shape") else np.asarray(codebook)
-        if len(cb.shape) == 2:
-            cb = cb[:, None, :]
-        if len(cb.shape) != 3 or cb.shape[2] != m_tx or cb.shape[0] < 1:
-            raise ValueError(f"{what}, got shape {tuple(codebook.shape) if hasattr(codebook, 'shape') else tuple(cb.shape)}")
+        cb = _precoding_codebook("compute_codebook_rate", params, codebook)
         check_codebook_rate_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), int(cb.shape[0]), int(cb.shape[1]), snr_db)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
@@ -615,6 +622,89 @@ class Dataset(DotDict):
         if config.get("channel_output", "numpy") == "torch":
             return res
         return tuple(t.cpu().numpy() for t in res)
+
+    def compute_subband_pmi(self, params: Optional[ChannelGenParameters] = None, *, codebook="dft", snr_db=None,
+                            subband_size=None, per_codeword: bool = False):
+        """``compute_codebook_rate`` with a PMI per subband from the same launch - the wideband and the subband part of a CSI
+        report for the layer count of ``codebook`` (extension).  Subbands partition the selected subcarriers in their own
+        order: subband s covers the positions s B .. min((s + 1) B, K) - 1 with B = ``subband_size`` (an integer >= 1; None:
+        one subband), n_sb = ceil(K / B), the last one possibly short:
+
+            rate_sb_c[u, s, c] = mean over k in subband s of log2 det(I + s * E.conj().T @ E)     # E, s as compute_codebook_rate
+            pmi_sb[u, s]  = rate_sb_c[u, s].argmax()      # the first maximum; -1 for a user without a path
+            rate_sb[u, s] = rate_sb_c[u, s, pmi_sb[u, s]]
+            rate_c, pmi, rate: as compute_codebook_rate, the subbands added in subband order
+
+        Returns ``(rate, pmi, rate_sb, pmi_sb)`` - float32 [n_ue], int32 [n_ue], float32 / int32 [n_ue, n_sb] - and with
+        ``per_codeword`` also ``rate_c`` [n_ue, C] and ``rate_sb_c`` [n_ue, n_sb, C].  Column s equals what
+        ``compute_codebook_rate`` returns for the selection ``sc[s B : (s + 1) B]`` bit for bit; with one subband all of it
+        equals ``compute_codebook_rate``.  ``codebook``, ``snr_db``, the shapes taken and the return convention are those of
+        ``compute_codebook_rate``; anything else raises ValueError before any GPU work.  Not cached."""
+        from .engine import check_codebook_rate_call, check_subband_size, snr_linear_from_db
+        if snr_db is None:
+            raise ValueError("compute_subband_pmi: snr_db (dB, keyword) is required")
+        snr_linear_from_db(snr_db)
+        subband_size = check_subband_size(subband_size)
+        if params is None:
+            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
+        self.set_channel_params(params)
+        cb = _precoding_codebook("compute_subband_pmi", params, codebook)
+        check_codebook_rate_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), int(cb.shape[0]), int(cb.shape[1]), snr_db)
+        np.random.seed(1001)
+        eng, prep = self._run_prep(want_side="light")
+        res = eng.codebook_rate_subbands(prep, cb, snr_db, subband_size, per_codeword=bool(per_codeword))
+        if config.get("channel_output", "numpy") == "torch":
+            return res
+        return tuple(t.cpu().numpy() for t in res)
+
+    def compute_csi_report(self, params: Optional[ChannelGenParameters] = None, *, codebooks=None, snr_db=None,
+                           subband_size=None):
+        """Rank indicator, wideband PMI and a PMI per subband of every user - the three parts of a CSI report - from one
+        subband launch per candidate rank on the same preparation, no channel tensor written (extension).  ``codebooks``: a
+        sequence of complex arrays [C_L, L, M_tx] (2-D: L = 1) with distinct layer counts L, one per candidate rank.
+
+            rank[u] = the L of the largest wideband rate (``compute_subband_pmi`` per codebook); on ties the smallest L;
+                      0 for a user without a path
+
+        Returns a DotDict: ``rank`` int32 [n_ue]; ``rate`` float32 [n_ue], ``pmi`` int32 [n_ue], ``rate_sb`` float32 and
+        ``pmi_sb`` int32 [n_ue, n_sb], all of the chosen rank's codebook (0 / -1 without a path); ``rate_by_rank`` float32
+        [n_ue, n_ranks], the wideband rate of every candidate in ascending L.  ``subband_size``, ``snr_db`` (the total
+        transmit power, split over the layers of each candidate) and the return convention as ``compute_subband_pmi``; a
+        duplicate L, an empty ``codebooks`` or a shape not taken raises ValueError before any GPU work.  Mapping a rate to a
+        CQI index is a table lookup left to the caller.  Not cached."""
+        import torch
+        from .engine import check_codebook_rate_call, check_subband_size, snr_linear_from_db
+        if snr_db is None:
+            raise ValueError("compute_csi_report: snr_db (dB, keyword) is required")
+        snr_linear_from_db(snr_db)
+        subband_size = check_subband_size(subband_size)
+        if params is None:
+            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
+        self.set_channel_params(params)
+        if codebooks is None or isinstance(codebooks, (str, bool, int, float, complex)) or hasattr(codebooks, "shape") or \
+                len(codebooks) == 0:
+            raise ValueError("compute_csi_report: codebooks must be a non-empty sequence of arrays [C, L, M_tx], one per rank")
+        cbs = sorted((_precoding_codebook("compute_csi_report", params, cb) for cb in codebooks), key=lambda cb: int(cb.shape[1]))
+        ranks = [int(cb.shape[1]) for cb in cbs]
+        if len(set(ranks)) != len(ranks):
+            raise ValueError(f"compute_csi_report: the codebooks must have distinct layer counts, got L = {ranks}")
+        for cb in cbs:
+            check_codebook_rate_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), int(cb.shape[0]), int(cb.shape[1]), snr_db)
+        np.random.seed(1001)
+        eng, prep = self._run_prep(want_side="light")
+        per_rank = [eng.codebook_rate_subbands(prep, cb, snr_db, subband_size) for cb in cbs]
+        rate, pmi, rate_sb, pmi_sb = (t.clone() for t in per_rank[0])
+        rank = torch.where(pmi >= 0, ranks[0], 0).to(torch.int32)
+        for L, (r, p, rs, ps) in zip(ranks[1:], per_rank[1:]):                 # a strict >: the smallest L on ties
+            take = r > rate
+            rank = torch.where(take, L, rank).to(torch.int32)
+            rate, pmi = torch.where(take, r, rate), torch.where(take, p, pmi)
+            rate_sb, pmi_sb = torch.where(take[:, None], rs, rate_sb), torch.where(take[:, None], ps, pmi_sb)
+        out = dict(rank=rank, rate=rate, pmi=pmi, rate_sb=rate_sb, pmi_sb=pmi_sb,
+                   rate_by_rank=torch.stack([t[0] for t in per_rank], dim=1))
+        if config.get("channel_output", "numpy") != "torch":
+            out = {k: t.cpu().numpy() for k, t in out.items()}
+        return DotDict(out)
 
     def compute_pathloss(self, coherent: bool = True) -> np.ndarray:
         """Path loss in dB assuming 0 dBm transmitted power (dataset.py:541-566); cached as ``pathloss``."""

@@ -16,6 +16,7 @@ include/deepmimo_amd.h and calls the C-ABI:
     dmx_cell_rate        -> float32 [N] (and [N, K], int32 [N], float32 [N, B])  (rate under inter-cell interference, B links)
     dmx_channels_angle_delay -> complex64 [N, M_rx, R, n_taps]  (codebook x inverse DFT, first delay taps, no channel tensor)
     dmx_codebook_rate   -> float32 [N], int32 [N], float32 [N, C]  (rate and PMI over a precoding codebook, no channel tensor)
+    dmx_codebook_rate_subbands -> the same and float32 [N, n_sb], int32 [N, n_sb], float32 [N, n_sb, C]  (a PMI per subband)
 
 It replaces the body of Dataset.compute_channels (deepmimo/generator/dataset.py:224-268).
 No CPU path exists here: without the shared library or without a GPU every entry point raises.
@@ -346,6 +347,16 @@ def check_codebook_rate_call(params, n_paths_loaded: int, n_codewords, n_layers,
     if rc != 1:
         raise ValueError("codebook rate: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
     return snr
+
+
+def check_subband_size(subband_size) -> Optional[int]:
+    """`subband_size` of the subband calls as an int, None (one subband over the whole selection) passed through; anything
+    that is not an integer >= 1 is a ValueError."""
+    if subband_size is None:
+        return None
+    if isinstance(subband_size, bool) or not isinstance(subband_size, (int, np.integer)) or subband_size < 1:
+        raise ValueError(f"codebook rate: subband_size must be an integer >= 1 or None, got {subband_size!r}")
+    return int(subband_size)
 
 
 def link_snrs_from_db(snr_db, n_links: int):
@@ -1078,6 +1089,29 @@ class ChannelEngine:
 
     CODEBOOK_WS_BYTES = 1 << 30          # beam workspace of one dmx_codebook_rate call; more users go in blocks
 
+    def _codebook_on_device(self, prep: PrepResult, codebook):
+        """(complex64 [C, L, M_tx] on the device, C, L) of the `codebook` argument of the codebook-rate calls"""
+        p = prep.params_struct
+        m_tx = p.bs_shape[0] * p.bs_shape[1]
+        cb = codebook if isinstance(codebook, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(codebook))
+        if cb.dim() == 2:
+            cb = cb[:, None, :]
+        if cb.dim() != 3 or cb.shape[2] != m_tx or cb.shape[0] < 1 or cb.shape[1] < 1:
+            raise ValueError(f"codebook must be [C, L, {m_tx}] or [C, {m_tx}], got {tuple(cb.shape)}")
+        cb = cb.to(device=self.device, dtype=torch.complex64).contiguous()
+        return cb, int(cb.shape[0]), int(cb.shape[1])
+
+    def _codebook_user_blocks(self, prep: PrepResult, user_count: int, n_rows: int):
+        """(first user of the block, users, beam workspace, its bytes) of the user blocks of a codebook-rate call: the beam
+        workspace of a block stays within CODEBOOK_WS_BYTES"""
+        p = prep.params_struct
+        per_user = n_rows * max(1, min(int(p.num_paths), prep.n_paths_loaded)) * 8 + 4
+        block = max(1, (int(self.CODEBOOK_WS_BYTES) - 512) // per_user)
+        for b in range(0, user_count, block):
+            cnt = min(block, user_count - b)
+            nbytes = int(self.lib.dmx_beam_workspace_bytes(C.byref(p), cnt, prep.n_paths_loaded, n_rows))
+            yield b, cnt, self._scratch(nbytes), nbytes
+
     def codebook_rate_supported(self, prep: PrepResult, n_codewords: int, n_layers: int = 1) -> bool:
         """dmx_codebook_rate_supported for this preparation (host-only query; `codebook_rate` raises where it says no)."""
         rc = self.lib.dmx_codebook_rate_supported(C.byref(prep.params_struct), prep.n_paths_loaded, int(n_codewords),
@@ -1100,26 +1134,14 @@ class ChannelEngine:
         p = prep.params_struct
         if user_count is None:
             user_count = prep.n_ue - user_begin
-        m_tx = p.bs_shape[0] * p.bs_shape[1]
-        cb = codebook if isinstance(codebook, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(codebook))
-        if cb.dim() == 2:
-            cb = cb[:, None, :]
-        if cb.dim() != 3 or cb.shape[2] != m_tx or cb.shape[0] < 1 or cb.shape[1] < 1:
-            raise ValueError(f"codebook must be [C, L, {m_tx}] or [C, {m_tx}], got {tuple(cb.shape)}")
-        cb = cb.to(device=self.device, dtype=torch.complex64).contiguous()
-        n_cw, n_layers = int(cb.shape[0]), int(cb.shape[1])
+        cb, n_cw, n_layers = self._codebook_on_device(prep, codebook)
         if not self.codebook_rate_supported(prep, n_cw, n_layers):   # DMX_ERR_SHAPE, before anything is allocated
             nat.check(-2, "dmx_codebook_rate")
         rate = torch.empty((user_count,), dtype=torch.float32, device=self.device)
         pmi = torch.empty((user_count,), dtype=torch.int32, device=self.device)
         rate_c = torch.empty((user_count, n_cw), dtype=torch.float32, device=self.device) if per_codeword else None
-        per_user = n_cw * n_layers * max(1, min(int(p.num_paths), prep.n_paths_loaded)) * 8 + 4
-        block = max(1, (int(self.CODEBOOK_WS_BYTES) - 512) // per_user)
         with torch.cuda.device(self.device):
-            for b in range(0, user_count, block):
-                cnt = min(block, user_count - b)
-                nbytes = int(self.lib.dmx_beam_workspace_bytes(C.byref(p), cnt, prep.n_paths_loaded, n_cw * n_layers))
-                bws = self._scratch(nbytes)
+            for b, cnt, bws, nbytes in self._codebook_user_blocks(prep, user_count, n_cw * n_layers):
                 rc = self.lib.dmx_codebook_rate(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
                                                 prep.n_paths_loaded, int(user_begin) + b, cnt, C.c_void_p(cb.data_ptr()),
                                                 n_cw, n_layers, C.c_void_p(bws.data_ptr()), nbytes, snr,
@@ -1128,6 +1150,51 @@ class ChannelEngine:
                                                 self._stream_ptr())
                 nat.check(rc, "dmx_codebook_rate")
         return (rate, pmi, rate_c) if per_codeword else (rate, pmi)
+
+    def codebook_rate_subbands_supported(self, prep: PrepResult, n_codewords: int, n_layers: int = 1, subband_size: int = 1) -> bool:
+        """dmx_codebook_rate_subbands_supported for this preparation (host-only query)."""
+        rc = self.lib.dmx_codebook_rate_subbands_supported(C.byref(prep.params_struct), prep.n_paths_loaded, int(n_codewords),
+                                                           int(n_layers), int(subband_size))
+        if rc < 0:
+            nat.check(rc, "dmx_codebook_rate_subbands_supported")
+        return rc == 1
+
+    def codebook_rate_subbands(self, prep: PrepResult, codebook, snr_db, subband_size, per_codeword: bool = False,
+                               user_begin: int = 0, user_count: Optional[int] = None):
+        """dmx_codebook_rate_subbands: `codebook_rate` with a PMI per subband in the same launch.  Subband s covers the
+        selection positions s B .. min((s + 1) B, K) - 1, B = `subband_size` (an integer >= 1; None: one subband over the
+        whole selection), n_sb = ceil(K / B).  Returns (rate [user_count], pmi [user_count], rate_sb [user_count, n_sb],
+        pmi_sb [user_count, n_sb]) - float32 / int32 - and with `per_codeword` also rate_c [user_count, C] and rate_sb_c
+        [user_count, n_sb, C], all in HBM.  Column s of the subband outputs equals `codebook_rate` on the selection
+        sc[s B : (s + 1) B] bit for bit, and with one subband everything equals `codebook_rate`; with more the wideband
+        outputs add the subbands in order (another summation order than `codebook_rate`).  User blocks as `codebook_rate`."""
+        snr = snr_linear_from_db(snr_db)
+        B = check_subband_size(subband_size)
+        p = prep.params_struct
+        K = int(p.n_selected)
+        B = max(1, K) if B is None else min(B, max(1, K))
+        if user_count is None:
+            user_count = prep.n_ue - user_begin
+        cb, n_cw, n_layers = self._codebook_on_device(prep, codebook)
+        if not self.codebook_rate_subbands_supported(prep, n_cw, n_layers, B):   # DMX_ERR_SHAPE, before anything is allocated
+            nat.check(-2, "dmx_codebook_rate_subbands")
+        n_sb = (K + B - 1) // B
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)   # noqa: E731
+        rate, pmi = new((user_count,), torch.float32), new((user_count,), torch.int32)
+        rate_sb, pmi_sb = new((user_count, n_sb), torch.float32), new((user_count, n_sb), torch.int32)
+        rate_c = new((user_count, n_cw), torch.float32) if per_codeword else None
+        rate_sb_c = new((user_count, n_sb, n_cw), torch.float32) if per_codeword else None
+        ptr = lambda t, b: C.c_void_p(t[b:].data_ptr()) if t is not None else None   # noqa: E731
+        with torch.cuda.device(self.device):
+            for b, cnt, bws, nbytes in self._codebook_user_blocks(prep, user_count, n_cw * n_layers):
+                rc = self.lib.dmx_codebook_rate_subbands(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
+                                                         prep.n_paths_loaded, int(user_begin) + b, cnt, C.c_void_p(cb.data_ptr()),
+                                                         n_cw, n_layers, C.c_void_p(bws.data_ptr()), nbytes, snr, B,
+                                                         ptr(rate_sb, b), ptr(pmi_sb, b), ptr(rate_sb_c, b), ptr(rate, b),
+                                                         ptr(pmi, b), ptr(rate_c, b), self._stream_ptr())
+                nat.check(rc, "dmx_codebook_rate_subbands")
+        res = (rate, pmi, rate_sb, pmi_sb)
+        return res + (rate_c, rate_sb_c) if per_codeword else res
 
     def pathloss(self, rays: DeviceRays, coherent: bool = True) -> torch.Tensor:
         """dmx_pathloss: float32 [n_ue] dB (dataset.py:541-566)."""

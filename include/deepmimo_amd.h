@@ -501,8 +501,8 @@ int dmx_channels_angle_delay(const dmx_params* prm, const void* workspace, int64
  * repeats its bits; the PMI is then the first).  Subcarrier phases are reduced in float64: any int32 index is valid,
  * DMX_SC_ABS_MAX_F32 does not apply.  prm->flags changes the order of a user's records and so the summation order only; the
  * workspace of either arithmetic mode is accepted.
- * Not covered: a PMI per subband, rank adaptation (call once per L and compare), L > 4 or L > M_rx, the time domain and
- * rx_filter = 1.
+ * A PMI per subband, and with it one call per L for rank adaptation: dmx_codebook_rate_subbands below.  Not covered: L > 4 or
+ * L > M_rx, the time domain and rx_filter = 1.
  *
  * dmx_codebook_rate_supported - host-only: 1 if dmx_codebook_rate takes this shape, 0 if not (dmx_last_error() then names the
  * limit), negative on a bad argument.  No GPU involved.  Taken: freq_domain = 1, rx_filter = 0,
@@ -526,6 +526,48 @@ int dmx_codebook_rate(const dmx_params* prm, const void* workspace, int64_t n_ue
                       void* beam_workspace, size_t beam_workspace_bytes /* dmx_beam_workspace_bytes(prm, user_count, n_paths_loaded, C * L) */,
                       double snr_linear, float* out_rate /* [user_count] */, int32_t* out_pmi /* [user_count] or NULL */,
                       float* out_rate_c /* [user_count, C] or NULL */, void* stream);
+
+/*
+ * The subband form of dmx_codebook_rate: the three parts of a CSI report for one layer count - a PMI and its rate per subband
+ * and the wideband pair - in one launch; the projection of the codebook, which does not depend on the subcarriers, runs once.
+ * Subbands partition the selection in its own order: with B = subband_size >= 1 and K = n_selected, subband s covers the
+ * selection positions s B .. min((s + 1) B, K) - 1, n_sb = ceil(K / B) subbands, the last possibly short; B >= K is one
+ * subband.  With E, snr_linear and L as above:
+ *   rate_sb_c[u, s, c] = mean over k in subband s of log2 det(I_L + (snr_linear / L) E_{c,k}^H E_{c,k})
+ *                                                                    out_rate_sb_c float32 [user_count, n_sb, C], may be NULL
+ *   pmi_sb[u, s]       = argmax_c rate_sb_c[u, s, c], the first maximum            out_pmi_sb int32 [user_count, n_sb], may be NULL
+ *   rate_sb[u, s]      = rate_sb_c[u, s, pmi_sb[u, s]]                             out_rate_sb float32 [user_count, n_sb]
+ *   rate_c[u, c]       = 1 / K sum_s (sum over the subband s), the subbands added in subband order
+ *   pmi[u], rate[u]    as in dmx_codebook_rate, from this rate_c; out_rate_c, out_pmi, out_rate as there, each may be NULL
+ * A subband is processed exactly as dmx_codebook_rate processes a selection that consists of that subband alone (chunks of
+ * min(B, K, 64) subcarriers from the subband's first one, the same summation tree, the chunks in order, times
+ * (float)(1.0 / length)).  So rate_sb_c[:, s, :], rate_sb[:, s] and pmi_sb[:, s] equal bit for bit what dmx_codebook_rate returns
+ * for the selection selected_subcarriers[s B : (s + 1) B], and with one subband all six outputs equal dmx_codebook_rate bit for
+ * bit.  With more than one subband the wideband outputs add the same terms in another order: they agree with dmx_codebook_rate
+ * within rounding, not bit for bit.  A user without kept paths gets +0.0 in every rate and -1 in every PMI.  No output is NaN,
+ * infinite or negative.  As above: launches repeat bit for bit, a user sub-range equals the same rows of a whole launch, and
+ * leaving out optional outputs changes no bit of the others.  n_sb is bounded by K alone: where the codebook spans several
+ * chunks of rows a subband's running best lives in out_rate_sb / out_pmi_sb themselves, not in the LDS.
+ *
+ * dmx_codebook_rate_subbands_supported - host-only, as dmx_codebook_rate_supported with subband_size: a subband_size < 1 is a bad
+ * argument (DMX_ERR_ARG); else the limits of dmx_codebook_rate_supported with the LDS rule
+ *   (M_rx + min(C * L, rc) + kc_sb) * P * 8 bytes <= 156 KB (159744),   kc_sb = min(subband_size, n_selected, 64)
+ * which is never more than the wideband call needs (26624 bytes at most).
+ *
+ * dmx_codebook_rate_subbands - the argument checks, error codes and alignments of dmx_codebook_rate, with out_rate_sb the output
+ * that must not be NULL when user_count > 0; subband_size < 1: DMX_ERR_ARG.  The beam workspace is that of dmx_codebook_rate.
+ */
+int dmx_codebook_rate_subbands_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_codewords, int32_t n_layers,
+                                         int32_t subband_size);
+int dmx_codebook_rate_subbands(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
+                               int64_t user_begin, int64_t user_count,
+                               const void* codebook_c64 /* [n_codewords, n_layers, M_tx] device */, int32_t n_codewords, int32_t n_layers,
+                               void* beam_workspace, size_t beam_workspace_bytes /* as dmx_codebook_rate */,
+                               double snr_linear, int32_t subband_size,
+                               float* out_rate_sb /* [user_count, n_sb] */, int32_t* out_pmi_sb /* [user_count, n_sb] or NULL */,
+                               float* out_rate_sb_c /* [user_count, n_sb, C] or NULL */, float* out_rate /* [user_count] or NULL */,
+                               int32_t* out_pmi /* [user_count] or NULL */, float* out_rate_c /* [user_count, C] or NULL */,
+                               void* stream);
 
 /*
  * Stage 2, time domain (replaces channel.py:285-287): out[u, rx, tx, s] = a_rx a_tx sqrt(p) e^{j phase}

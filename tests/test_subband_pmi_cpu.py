@@ -1,0 +1,304 @@
+"""Host side of the subband PMI and the CSI report (dmx_codebook_rate_subbands_supported / dmx_codebook_rate_subbands, the
+subband form of k10_codebook_rate.hip, Dataset.compute_subband_pmi / compute_csi_report) - no GPU: the symbols, the shape
+query, the errors that must come before any GPU call, the reference of the GPU tests against hand cases, and the conditions on
+the GPU tests' inputs (the tolerance share of every case; the rank cases pick more than one rank)."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from tests._codebook_rate_ref import case_codebook, case_snr, codebook_rate_from_channel, codebook_rate_tolerance
+from tests._subband_pmi_cases import RANK_CASES, RANK_CODEWORDS, RANK_LAYERS, SUBBAND_CASES, case_label
+from tests._subband_pmi_ref import reference_ranks, subband_edges, subband_means, subband_reference, subband_tolerance_share
+from tests.test_codebook_rate_cpu import _dataset, _params, lds_rule
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "deepmimo_amd", "lib", "libdeepmimo_amd.so")
+needs_lib = pytest.mark.skipif(not os.path.exists(LIB), reason="needs the built library")
+
+SYMBOLS = ("dmx_codebook_rate_subbands_supported", "dmx_codebook_rate_subbands")
+
+
+def test_header_and_binding_name_the_new_entry_points():
+    from deepmimo_amd import _native as n
+    hdr = open(os.path.join(ROOT, "include", "deepmimo_amd.h")).read()
+    for sym in SYMBOLS:
+        assert re.search(r"\b%s\(" % sym, hdr) and sym in n.EXPORTED_SYMBOLS
+    flat = re.sub(r"[ \t]+", " ", hdr)
+    assert n.ABI_VERSION == 3 and "#define DMX_ABI_VERSION 3" in flat
+    text = re.sub(r"\s*\n \*\s*", " ", hdr)
+    assert "Not covered: a PMI per subband" not in text and "dmx_codebook_rate_subbands below" in text
+    assert "kc_sb = min(subband_size, n_selected, 64)" in text
+    for promise in ("equal bit for bit what dmx_codebook_rate returns", "with one subband all six outputs equal dmx_codebook_rate",
+                    "not bit for bit", "n_sb is bounded by K alone"):
+        assert promise in text, promise
+
+
+@needs_lib
+def test_library_exports_the_symbols_with_abi_3():
+    from deepmimo_amd import _native as n
+    lib = n.load()
+    assert lib.dmx_version() == 3
+    for sym in SYMBOLS:
+        assert getattr(lib, sym) is not None
+
+
+@needs_lib
+def test_supported_shapes_without_a_gpu():
+    from deepmimo_amd import _native as n
+    lib = n.load()
+    err = lambda: lib.dmx_last_error().decode()                               # noqa: E731
+    q = lambda p, B, C_=8, L_=1, loaded=25: lib.dmx_codebook_rate_subbands_supported(C.byref(p), loaded, C_, L_, B)   # noqa: E731
+    assert q(_params(), 1) == 1                                               # DeepMIMO's defaults, K = 1
+    assert q(_params(K=512), 32) == 1 and q(_params(K=512), 4) == 1 and q(_params(K=512), 1) == 1
+    assert q(_params(K=512), 512) == 1 and q(_params(K=512), 2 ** 31 - 1) == 1          # B >= K: one subband
+    assert q(_params((64, 4), (2, 2), 512), 4, 64, 1) == 1                    # the headline panel, 128 subbands
+    assert q(_params((8, 4), (4, 2), 3), 2, 9, 4) == 1                        # M_rx = 8, L = 4
+    for bad in (0, -1, -(2 ** 31)):
+        assert q(_params(K=512), bad) == -1 and "subband_size" in err() and ">= 1" in err()
+    assert q(_params(freq_domain=0), 4) == 0 and "freq_domain" in err()       # the time domain
+    assert q(_params(rx_filter=1), 4) == 0 and "rx_filter" in err()
+    assert q(_params((8, 4), (2, 1), 3), 1, 8, 3) == 0 and "n_layers = 3" in err() and "1..2" in err()      # L > M_rx
+    assert q(_params((8, 4), (3, 3), 3), 1) == 0 and "8 UE elements" in err()
+    assert q(_params(num_paths=33), 1, loaded=40) == 0 and "1..32 paths" in err()
+    assert q(_params(K=0), 1) == 0 and q(_params(), 1, 0) == 0 and q(_params(), 1, 65537) == 0
+    assert q(_params(), 1, loaded=-1) == -1
+    assert lib.dmx_codebook_rate_subbands_supported(None, 25, 8, 1, 4) == -1 and "params is NULL" in err()
+    assert q(_params(flags=n.FLAG_ADAPTIVE_TERMS), 1) == 1
+
+
+@needs_lib
+def test_supported_equals_the_wideband_query_for_every_subband_size():
+    """kc of the subband form, min(B, K, 64), never exceeds the wideband min(K, 64): the two queries agree for every B >= 1"""
+    from deepmimo_amd import _native as n
+    lib = n.load()
+    rng = np.random.default_rng(14)
+    seen = {0: 0, 1: 0}
+    for _ in range(3000):
+        ue = (int(rng.integers(1, 6)), int(rng.integers(1, 3)))
+        L, num_paths, K = int(rng.integers(0, 40)), int(rng.integers(0, 40)), int(rng.integers(1, 100))
+        n_cw, n_layers, B = int(rng.integers(0, 70)), int(rng.integers(0, 6)), int(rng.integers(1, 130))
+        p = _params((8, 4), ue, K, num_paths)
+        wide = lib.dmx_codebook_rate_supported(C.byref(p), L, n_cw, n_layers)
+        got = lib.dmx_codebook_rate_subbands_supported(C.byref(p), L, n_cw, n_layers, B)
+        assert got == wide == (1 if lds_rule(ue, K, min(L, num_paths), n_cw, n_layers) else 0), (ue, K, num_paths, L, n_cw, n_layers, B)
+        seen[got] += 1
+    assert all(v > 50 for v in seen.values()), seen
+
+
+@needs_lib
+def test_argument_errors_without_gpu():
+    from deepmimo_amd import _native as n
+    lib = n.load()
+    err = lambda: lib.dmx_last_error().decode()                               # noqa: E731
+    buf = (C.c_char * (1 << 20))()
+    base = (C.addressof(buf) + 255) // 256 * 256
+    at = lambda off: C.c_void_p(base + off)                                   # noqa: E731
+    ws, cbp, bws = at(0), at(8192), at(65536)
+    outs = dict(rsb=at(4096), psb=at(12288), rsbc=at(16384), r=at(20480), pm=at(24576), rc_=at(28672))
+
+    def call(p, b=0, cnt=4, snr=10.0, cb=cbp, n_cw=8, n_layers=1, bw=bws, bw_bytes=1 << 19, L=25, B=1, **o):
+        v = dict(outs, **o)
+        return lib.dmx_codebook_rate_subbands(C.byref(p), ws, 4, L, b, cnt, cb, n_cw, n_layers, bw, bw_bytes, snr, B,
+                                              v["rsb"], v["psb"], v["rsbc"], v["r"], v["pm"], v["rc_"], None)
+    assert call(_params(freq_domain=0)) == -1 and "freq_domain" in err()
+    assert call(_params(rx_filter=1)) == -1 and "rx_filter" in err()
+    for bad in (0.0, -1.0, float("nan"), float("inf"), 1e71, 1e-71):
+        assert call(_params(), snr=bad) == -1 and "snr_linear" in err()
+    for bad in (0, -1):
+        assert call(_params(), B=bad) == -1 and "subband_size" in err()
+    assert call(_params(), b=2, cnt=4) == -1 and "user range" in err()
+    assert call(_params(), rsb=None) == -1 and "NULL" in err()                # the one output that is not optional
+    assert call(_params(), cb=None) == -1 and "codebook" in err()
+    for name in outs:
+        assert call(_params(), **{name: C.c_void_p(outs[name].value + 2)}) == -1 and "4-byte aligned" in err(), name
+    assert call(_params((8, 4), (3, 3), 2)) == -2 and "8 UE elements" in err()
+    assert call(_params((8, 4), (2, 1), 2), n_layers=3) == -2 and "n_layers" in err()
+    assert call(_params(), n_layers=0) == -2 and call(_params(), n_layers=5) == -2 and call(_params(), n_cw=0) == -2
+    assert call(_params(num_paths=33), L=40) == -2 and "32" in err()
+    assert call(_params(K=0)) == -2
+    need = lib.dmx_beam_workspace_bytes(C.byref(_params()), 4, 25, 8)
+    assert call(_params(), bw=None) == -4 and "beam workspace" in err()
+    assert call(_params(), bw_bytes=need - 1) == -4 and str(need) in err()
+    assert call(_params(), cnt=0) == 0                                        # nothing to do: success before any GPU call
+    assert call(_params(), cnt=0, cb=None, bw=None, bw_bytes=0, rsb=None, psb=None, rsbc=None, r=None, pm=None, rc_=None) == 0
+
+
+@needs_lib
+def test_dataset_errors_come_before_any_gpu_call(monkeypatch):
+    from deepmimo_amd import dataset as dsm
+    from deepmimo_amd.engine import check_subband_size
+    dm, ds = _dataset()
+
+    def no_engine():
+        raise AssertionError("the GPU engine was asked for before the argument checks")
+    monkeypatch.setattr(dsm, "_engine", no_engine)
+    assert check_subband_size(None) is None and check_subband_size(np.int64(7)) == 7 and check_subband_size(1) == 1
+    P = dm.ChannelGenParameters
+    one = [np.ones((4, 8), np.complex64)]
+    for bad in (0, -1, 2.0, "4", True, [4]):
+        with pytest.raises(ValueError, match="subband_size"):
+            check_subband_size(bad)
+        with pytest.raises(ValueError, match="subband_size"):
+            ds.compute_subband_pmi(P(), snr_db=20.0, subband_size=bad)
+        with pytest.raises(ValueError, match="subband_size"):
+            ds.compute_csi_report(P(), codebooks=one, snr_db=20.0, subband_size=bad)
+    with pytest.raises(ValueError, match="snr_db"):                           # missing
+        ds.compute_subband_pmi(P(), subband_size=4)
+    with pytest.raises(ValueError, match="snr_db"):
+        ds.compute_csi_report(P(), codebooks=one)
+    for bad in (float("nan"), float("inf"), "20", True):
+        with pytest.raises(ValueError, match="snr_db"):
+            ds.compute_subband_pmi(P(), snr_db=bad)
+        with pytest.raises(ValueError, match="snr_db"):
+            ds.compute_csi_report(P(), codebooks=one, snr_db=bad)
+    with pytest.raises(TypeError):                                            # keyword-only
+        ds.compute_subband_pmi(P(), "dft", 20.0)
+    with pytest.raises(TypeError):
+        ds.compute_csi_report(P(), one, 20.0)
+    for bad in ("hadamard", True, None, 3):
+        with pytest.raises(ValueError, match="'dft'"):
+            ds.compute_subband_pmi(P(), snr_db=20.0, codebook=bad)
+    with pytest.raises(ValueError, match=r"\[C, L, 8\]"):
+        ds.compute_subband_pmi(P(), snr_db=20.0, codebook=np.ones((4, 7), np.complex64))
+    with pytest.raises(ValueError, match="n_layers = 2"):                     # two layers on the default 1 x 1 UE
+        ds.compute_subband_pmi(P(), snr_db=20.0, codebook=np.ones((4, 2, 8), np.complex64))
+    # the codebooks of a report: empty, no sequence, duplicate ranks (a 2-D array is L = 1), a wrong width, too many layers
+    for bad in ([], (), None, "dft", np.ones((4, 1, 8), np.complex64), 3):
+        with pytest.raises(ValueError, match="non-empty sequence"):
+            ds.compute_csi_report(P(), codebooks=bad, snr_db=20.0)
+    p22 = P()
+    p22.ue_antenna.shape = np.array([2, 1])
+    two = np.ones((3, 2, 8), np.complex64)
+    for dup in ([one[0], np.ones((5, 1, 8), np.complex64)], [two, one[0], two]):
+        with pytest.raises(ValueError, match="distinct layer counts"):
+            ds.compute_csi_report(p22, codebooks=dup, snr_db=20.0)
+    with pytest.raises(ValueError, match=r"\[C, L, 8\]"):
+        ds.compute_csi_report(P(), codebooks=[np.ones((4, 7), np.complex64)], snr_db=20.0)
+    with pytest.raises(ValueError, match="n_layers = 2"):
+        ds.compute_csi_report(P(), codebooks=[one[0], two], snr_db=20.0)
+    p = P()
+    p.freq_domain = 0
+    with pytest.raises(ValueError, match="freq_domain"):
+        ds.compute_subband_pmi(p, snr_db=20.0, subband_size=2)
+    with pytest.raises(ValueError, match="freq_domain"):
+        ds.compute_csi_report(p, codebooks=one, snr_db=20.0)
+    p = P()
+    p.ofdm.rx_filter = 1
+    with pytest.raises(ValueError, match="rx_filter"):
+        ds.compute_subband_pmi(p, snr_db=20.0)
+    with pytest.raises(ValueError, match="rx_filter"):
+        ds.compute_csi_report(p, codebooks=one, snr_db=20.0)
+
+
+@needs_lib
+def test_valid_call_without_a_gpu_raises_the_usual_error(monkeypatch):
+    """After the host checks the call asks for the engine, which raises where no GPU is visible (no CPU fallback)."""
+    import torch
+    from deepmimo_amd import dataset as dsm
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    monkeypatch.setattr(dsm, "_engines", {})
+    dm, ds = _dataset()
+    with pytest.raises(RuntimeError, match="no GPU"):
+        ds.compute_subband_pmi(dm.ChannelGenParameters(), snr_db=20.0, subband_size=4, per_codeword=True)
+    with pytest.raises(RuntimeError, match="no GPU"):
+        ds.compute_csi_report(dm.ChannelGenParameters(), codebooks=[np.ones((3, 8))], snr_db=20.0)
+    assert {"compute_subband_pmi", "compute_csi_report"} <= dm.MacroDataset.PROPAGATE_METHODS
+
+
+# ---- the reference, by hand -----------------------------------------------------------------------------------------------
+def _random_channel(seed, K, n=5, m_rx=2, m_tx=8):
+    rng = np.random.default_rng(seed)
+    H = rng.normal(size=(n, m_rx, m_tx, K)) + 1j * rng.normal(size=(n, m_rx, m_tx, K))
+    H[1] = 0
+    return H
+
+
+def test_reference_subband_edges():
+    assert subband_edges(7, 3) == [(0, 3), (3, 6), (6, 7)] and subband_edges(6, 3) == [(0, 3), (3, 6)]
+    assert subband_edges(7, None) == [(0, 7)] and subband_edges(7, 7) == [(0, 7)] and subband_edges(7, 1000) == [(0, 7)]
+    assert subband_edges(3, 1) == [(0, 1), (1, 2), (2, 3)] and subband_edges(1, 1) == [(0, 1)]
+    assert subband_edges(65, 64) == [(0, 64), (64, 65)] and len(subband_edges(512, 4)) == 128
+
+
+def test_reference_one_subband_is_the_wideband_reference():
+    H, W = _random_channel(3, 7), case_codebook([4, 2], 6, 2)
+    for B in (None, 7, 50):
+        ref = subband_reference(H, W, 3.0, B)
+        assert ref["rate_sb_c"].shape == (5, 1, 6) and ref["tol_sb_c"].shape == (5, 1, 6)
+        assert np.array_equal(ref["rate_sb_c"][:, 0], ref["rate_c"]) and np.array_equal(ref["tol_sb_c"][:, 0], ref["tol_c"])
+        assert np.array_equal(ref["rate_c"], codebook_rate_from_channel(H, W, 3.0)[0])
+        assert np.array_equal(ref["tol_c"], codebook_rate_tolerance(H, W, 3.0)[0])
+
+
+def test_reference_subbands_of_one_are_the_per_subcarrier_rates():
+    H, W = _random_channel(4, 5), case_codebook([4, 2], 3, 1)
+    ref = subband_reference(H, W, 2.0, 1)
+    _, rate_ck = codebook_rate_from_channel(H, W, 2.0)
+    _, tol_ck = codebook_rate_tolerance(H, W, 2.0)
+    assert np.array_equal(ref["rate_sb_c"], rate_ck.transpose(0, 2, 1)) and np.array_equal(ref["tol_sb_c"], tol_ck.transpose(0, 2, 1))
+    assert (ref["rate_sb_c"][1] == 0).all() and (ref["tol_sb_c"] > 0).all()
+
+
+def test_reference_short_last_subband_takes_its_own_length():
+    x = np.arange(2 * 3 * 7, dtype=np.float64).reshape(2, 3, 7) ** 2
+    m = subband_means(x, 3)
+    assert m.shape == (2, 3, 3)
+    np.testing.assert_array_equal(m[:, 0], x[:, :, 0:3].sum(axis=2) / 3)
+    np.testing.assert_array_equal(m[:, 1], x[:, :, 3:6].sum(axis=2) / 3)
+    np.testing.assert_array_equal(m[:, 2], x[:, :, 6])                         # one subcarrier: its own value, not a third of it
+    # the wideband mean is the length-weighted mean of the subband means
+    np.testing.assert_allclose((m * np.array([3, 3, 1])[None, :, None]).sum(axis=1) / 7, x.mean(axis=2), rtol=1e-14)
+    H, W = _random_channel(5, 7), case_codebook([4, 2], 4, 2)
+    ref = subband_reference(H, W, 5.0, 3)
+    _, rate_ck = codebook_rate_from_channel(H, W, 5.0)
+    np.testing.assert_array_equal(ref["rate_sb_c"][:, 2], rate_ck[:, :, 6])
+    np.testing.assert_array_equal(ref["rate_sb_c"][:, 1], rate_ck[:, :, 3:6].mean(axis=2))
+
+
+def test_the_case_table_names_cases_of_the_codebook_rate_tests():
+    from tests import test_gpu_codebook_rate as g
+    by = {c["id"]: c for c in g.CASES}
+    assert len(set(SUBBAND_CASES)) == len(SUBBAND_CASES) and all(cid in by and B >= 1 for cid, B in SUBBAND_CASES)
+    n_sb = {case_label(cid, B): len(subband_edges(len(by[cid]["selected"]), B)) for cid, B in SUBBAND_CASES}
+    assert n_sb["K65-B65"] == n_sb["K65-B1000"] == 1 and n_sb["K65-B64"] == 2 and n_sb["K65-B16"] == 5
+    assert n_sb["K512-B4"] == 128 and n_sb["K512-B100"] == 6 and n_sb["slices_K33-B4"] == 9 and n_sb["slices_K33-B32"] == 2
+    assert by["L1_C33"]["C"] > 32 and by["panel_C64"]["C"] > 32 and by["L4_C9"]["C"] * 4 > 32 and by["L3_C11"]["C"] * 3 > 30
+    assert all(cid in by and by[cid]["ue_shape"][0] * by[cid]["ue_shape"][1] >= max(RANK_LAYERS) for cid in RANK_CASES)
+
+
+@needs_lib
+def test_tolerance_share_condition_of_every_gpu_case():
+    """The tolerance may exceed 1 % of max(1, rate_sb_ref) on at most 5 % of a case's live (user, subband, codeword) entries,
+    otherwise the GPU test would hide failures.  Inputs: those of tests/test_gpu_codebook_rate.py, SNR = case_snr(H)."""
+    from tests import test_gpu_codebook_rate as g
+    by = {c["id"]: c for c in g.CASES}
+    worst = 0.0
+    for cid, B in SUBBAND_CASES:
+        _, _, H, W, snr, _ = g.case_inputs(by[cid])
+        assert snr == case_snr(H)
+        share = subband_tolerance_share(H, subband_reference(H, W, snr, B))
+        print(f"{case_label(cid, B)}: share of entries with tol > 1 % = {share:.4f}")
+        worst = max(worst, share)
+        assert share <= 0.05, (cid, B, share)
+    print(f"largest share {worst:.4f}")
+
+
+@needs_lib
+def test_the_rank_cases_pick_more_than_one_rank():
+    """The reference alone picks at least two different ranks, each for at least 10 % of the live users: otherwise the rank
+    selection of compute_csi_report would be tested on one rank only"""
+    from tests import test_gpu_codebook_rate as g
+    by = {c["id"]: c for c in g.CASES}
+    for cid in RANK_CASES:
+        c = by[cid]
+        _, _, H, _, snr, _ = g.case_inputs(c)
+        refs = [subband_reference(H, case_codebook(c["bs_shape"], RANK_CODEWORDS, L), snr, None) for L in RANK_LAYERS]
+        rank, best, tol = reference_ranks(refs, RANK_LAYERS)
+        live = np.abs(H).reshape(len(H), -1).max(axis=1) > 0
+        counts = {L: int((rank[live] == L).sum()) for L in RANK_LAYERS}
+        print(f"{cid}: ranks picked by the reference {counts} of {int(live.sum())} live users")
+        assert sum(v >= 0.1 * live.sum() for v in counts.values()) >= 2, (cid, counts)
+        assert (best[live] > 0).all() and (tol > 0).all()
