@@ -128,6 +128,9 @@ def _load_group(items, device, rx_idxs=None, max_paths: Optional[int] = None) ->
         for m in metas:
             if idx.size and (idx.min() < 0 or idx.max() >= m["rows"]):
                 raise IndexError(f"{m['path']}: receiver index out of range for {m['rows']} stored receivers")
+        if idx.size == 0:       # as m[rx_idxs][:, :max_paths] on the host; to the library a NULL index list means every row
+            return {m["key"]: torch.empty((0, m["cols"] if max_paths is None else min(int(max_paths), m["cols"])),
+                                          dtype=torch.float32, device=dev) for m in metas}
         d_idx, n_idx = torch.from_numpy(idx).to(dev), int(idx.size)
     stage = _staging(total)
     stage_np = stage.numpy()
