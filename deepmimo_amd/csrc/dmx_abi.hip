@@ -113,6 +113,75 @@ static dmx_side side_or_none(const dmx_side* side) {
     return s;
 }
 
+// ---- the consumers of the per-path records (covariance, rate, spectrum, precoders, cell rate, angle-delay, codebook rate) ----
+// An entry point is: consumer_args, its own argument checks, check_snr where it takes one, shape_status of its shape rule, the
+// early return without users, carve, launch.  A dmx_*_supported query is `supported` over the same shape rule.
+
+// Before the shape rule: the parameter block, the user range, what the entry point found `missing` (counted only with users
+// to run) or `misaligned` among its pointers - the message, or nullptr - around the workspace alignment, and plain frequency
+// domain under the entry point's name `fn`.
+static int consumer_args(const char* fn, const dmx_params* prm, const void* workspace, int64_t n_ue, int64_t user_begin,
+                         int64_t user_count, const char* missing, const char* misaligned) {
+    int rc = check_params(prm);
+    if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
+    if (user_count > 0 && missing) { set_error("%s", missing); return DMX_ERR_ARG; }
+    if ((rc = check_workspace_aligned(workspace))) return rc;
+    if (misaligned) { set_error("%s", misaligned); return DMX_ERR_ARG; }
+    if (!prm->freq_domain) { set_error("%s called with freq_domain = 0", fn); return DMX_ERR_ARG; }
+    if (prm->rx_filter) { set_error("%s does not cover rx_filter = 1", fn); return DMX_ERR_ARG; }
+    return DMX_OK;
+}
+static const char* const WS_OUT_NULL = "workspace/out is NULL";
+
+// finite and > 0, and so is its square root in float32 (the kernel's scale of the path coefficients); `what` names the value
+static int check_snr(const char* what, double snr_linear) {
+    if (snr_linear >= 1e-70 && snr_linear <= 1e70) return DMX_OK;
+    set_error("%s must be finite and > 0 (1e-70 .. 1e70), got %g", what, snr_linear);
+    return DMX_ERR_ARG;
+}
+
+// A shape rule answers 1: taken; 0: not taken, with the limit in the error string; negative: bad argument.
+// What a launching entry point returns for that answer:
+static int shape_status(int shape) { return shape < 0 ? shape : shape == 0 ? DMX_ERR_SHAPE : DMX_OK; }
+
+// a dmx_*_supported query: the parameter block, then the shape rule
+template <class Shape>
+static int supported(const dmx_params* prm, Shape shape) {
+    const int rc = check_params(prm);
+    return rc ? rc : shape();
+}
+
+// Steps the shape rules share, each with the words of its feature; 1: passed, 0: not taken.  `who` + " needs ...":
+static int shape_plain_fd(const char* who, const dmx_params* p) {
+    if (p->freq_domain && !p->rx_filter) return 1;
+    set_error("%s needs freq_domain = 1 and rx_filter = 0", who);
+    return 0;
+}
+// *P = min(num_paths, loaded paths), which has to be in 1..32
+static int shape_used_paths(const char* feature, const dmx_params* p, int32_t n_paths_loaded, int* P) {
+    *P = used_paths(p, n_paths_loaded);
+    if (*P >= 1 && *P <= 32) return 1;
+    set_error("%s: min(num_paths, loaded paths) = %d is outside the 1..32 paths the kernel supports", feature, *P);
+    return 0;
+}
+static int shape_selected(const char* feature, const dmx_params* p) {
+    if (p->n_selected >= 1) return 1;
+    set_error("%s: at least one selected subcarrier is needed", feature);
+    return 0;
+}
+// the head of a one-link shape rule: a loaded-path count, plain frequency domain, 1..32 used paths, a subcarrier
+static int shape_head(const char* feature, const char* who_fd, const dmx_params* p, int32_t n_paths_loaded, int* P) {
+    if (n_paths_loaded < 0) { set_error("n_paths_loaded must be >= 0"); return DMX_ERR_ARG; }
+    return shape_plain_fd(who_fd, p) && shape_used_paths(feature, p, n_paths_loaded, P) && shape_selected(feature, p);
+}
+
+// the view of the records, carved once the checks have passed
+static WsView carve(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded) {
+    WsView ws;
+    ws_carve(const_cast<void*>(workspace), n_ue, used_paths(prm, n_paths_loaded), &ws);
+    return ws;
+}
+
 }  // namespace dmx
 
 using namespace dmx;
@@ -265,17 +334,11 @@ int dmx_beam_power(const dmx_params* prm, const void* workspace, int64_t n_ue, i
                              out_mean_amp, out_best_beam, (hipStream_t)stream);
 }
 
-// 1: taken; 0: not taken, with the limit in the error string; negative: bad argument
 static int covariance_shape(const dmx_params* prm, int32_t n_paths_loaded, int32_t side) {
     if (side != DMX_COV_TX && side != DMX_COV_RX) { set_error("side must be DMX_COV_TX (0) or DMX_COV_RX (1), got %d", side); return DMX_ERR_ARG; }
-    if (n_paths_loaded < 0) { set_error("n_paths_loaded must be >= 0"); return DMX_ERR_ARG; }
-    if (!prm->freq_domain || prm->rx_filter) { set_error("the covariance needs freq_domain = 1 and rx_filter = 0"); return 0; }
-    const int P = used_paths(prm, n_paths_loaded);
-    if (P < 1 || P > 32) {
-        set_error("covariance: min(num_paths, loaded paths) = %d is outside the 1..32 paths the kernel supports", P);
-        return 0;
-    }
-    if (prm->n_selected < 1) { set_error("covariance: at least one selected subcarrier is needed"); return 0; }
+    int P;
+    const int rc = shape_head("covariance", "the covariance", prm, n_paths_loaded, &P);
+    if (rc != 1) return rc;
     if (cov_waves_per_block(*prm, P, side, nullptr) == 0) {
         const long long m_tx = (long long)prm->bs_shape[0] * prm->bs_shape[1], m_rx = (long long)prm->ue_shape[0] * prm->ue_shape[1];
         set_error("covariance: one user's tables, (%lld + %lld + %lld + %d + 8) * %d * 8 = %lld bytes, exceed the %zu bytes of LDS "
@@ -287,35 +350,23 @@ static int covariance_shape(const dmx_params* prm, int32_t n_paths_loaded, int32
 }
 
 int dmx_covariance_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t side) {
-    int rc = check_params(prm);
-    if (rc) return rc;
-    return covariance_shape(prm, n_paths_loaded, side);
+    return supported(prm, [&] { return covariance_shape(prm, n_paths_loaded, side); });
 }
 
 int dmx_channel_covariance(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                            int64_t user_begin, int64_t user_count, int32_t side, void* out_c64, void* stream) {
-    WsView ws;
-    int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_c64, &ws);
-    if (rc) return rc;
-    if (!prm->freq_domain) { set_error("dmx_channel_covariance called with freq_domain = 0"); return DMX_ERR_ARG; }
-    if (prm->rx_filter) { set_error("dmx_channel_covariance does not cover rx_filter = 1"); return DMX_ERR_ARG; }
-    rc = covariance_shape(prm, n_paths_loaded, side);
-    if (rc < 0) return rc;
-    if (rc == 0) return DMX_ERR_SHAPE;
+    int rc = consumer_args("dmx_channel_covariance", prm, workspace, n_ue, user_begin, user_count,
+                           !workspace || !out_c64 ? WS_OUT_NULL : nullptr, (uintptr_t)out_c64 & 7u ? "out must be 8-byte aligned" : nullptr);
+    if (rc || (rc = shape_status(covariance_shape(prm, n_paths_loaded, side)))) return rc;
     if (user_count == 0) return DMX_OK;
-    return launch_covariance(*prm, ws, user_begin, user_count, side, (float2*)out_c64, (hipStream_t)stream);
+    return launch_covariance(*prm, carve(prm, workspace, n_ue, n_paths_loaded), user_begin, user_count, side, (float2*)out_c64,
+                             (hipStream_t)stream);
 }
 
-// 1: taken; 0: not taken, with the limit in the error string; negative: bad argument
 static int rate_shape(const dmx_params* prm, int32_t n_paths_loaded) {
-    if (n_paths_loaded < 0) { set_error("n_paths_loaded must be >= 0"); return DMX_ERR_ARG; }
-    if (!prm->freq_domain || prm->rx_filter) { set_error("the rate needs freq_domain = 1 and rx_filter = 0"); return 0; }
-    const int P = used_paths(prm, n_paths_loaded);
-    if (P < 1 || P > 32) {
-        set_error("rate: min(num_paths, loaded paths) = %d is outside the 1..32 paths the kernel supports", P);
-        return 0;
-    }
-    if (prm->n_selected < 1) { set_error("rate: at least one selected subcarrier is needed"); return 0; }
+    int P;
+    const int rc = shape_head("rate", "the rate", prm, n_paths_loaded, &P);
+    if (rc != 1) return rc;
     const long long m_tx = (long long)prm->bs_shape[0] * prm->bs_shape[1], m_rx = (long long)prm->ue_shape[0] * prm->ue_shape[1];
     const long long m = m_rx <= m_tx ? m_rx : m_tx, big = m_rx <= m_tx ? m_tx : m_rx;
     if (m > 8) {
@@ -332,33 +383,20 @@ static int rate_shape(const dmx_params* prm, int32_t n_paths_loaded) {
 }
 
 int dmx_rate_supported(const dmx_params* prm, int32_t n_paths_loaded) {
-    int rc = check_params(prm);
-    if (rc) return rc;
-    return rate_shape(prm, n_paths_loaded);
+    return supported(prm, [&] { return rate_shape(prm, n_paths_loaded); });
 }
 
 int dmx_channel_rate(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                      int64_t user_begin, int64_t user_count, double snr_linear, float* out_rate, float* out_rate_k,
                      void* stream) {
-    // the checks of stage2_common, with float outputs: rows of a float32 tensor are 4-byte aligned
-    int rc = check_params(prm);
-    if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
-    if (user_count > 0 && (!workspace || !out_rate)) { set_error("workspace/out is NULL"); return DMX_ERR_ARG; }
-    if ((rc = check_workspace_aligned(workspace))) return rc;
-    if (((uintptr_t)out_rate & 3u) || ((uintptr_t)out_rate_k & 3u)) { set_error("out_rate / out_rate_k must be 4-byte aligned"); return DMX_ERR_ARG; }
-    if (!prm->freq_domain) { set_error("dmx_channel_rate called with freq_domain = 0"); return DMX_ERR_ARG; }
-    if (prm->rx_filter) { set_error("dmx_channel_rate does not cover rx_filter = 1"); return DMX_ERR_ARG; }
-    // finite and > 0, and so is its square root in float32 (the kernel's scale of the path coefficients)
-    if (!(snr_linear >= 1e-70) || !(snr_linear <= 1e70)) {
-        set_error("dmx_channel_rate: snr_linear must be finite and > 0 (1e-70 .. 1e70), got %g", snr_linear); return DMX_ERR_ARG;
-    }
-    rc = rate_shape(prm, n_paths_loaded);
-    if (rc < 0) return rc;
-    if (rc == 0) return DMX_ERR_SHAPE;
+    // float outputs: rows of a float32 tensor are 4-byte aligned
+    int rc = consumer_args("dmx_channel_rate", prm, workspace, n_ue, user_begin, user_count,
+                           !workspace || !out_rate ? WS_OUT_NULL : nullptr,
+                           ((uintptr_t)out_rate | (uintptr_t)out_rate_k) & 3u ? "out_rate / out_rate_k must be 4-byte aligned" : nullptr);
+    if (rc || (rc = check_snr("dmx_channel_rate: snr_linear", snr_linear)) || (rc = shape_status(rate_shape(prm, n_paths_loaded)))) return rc;
     if (user_count == 0) return DMX_OK;
-    WsView ws;
-    ws_carve(const_cast<void*>(workspace), n_ue, used_paths(prm, n_paths_loaded), &ws);
-    return launch_rate(*prm, ws, user_begin, user_count, snr_linear, out_rate, out_rate_k, (hipStream_t)stream);
+    return launch_rate(*prm, carve(prm, workspace, n_ue, n_paths_loaded), user_begin, user_count, snr_linear, out_rate, out_rate_k,
+                       (hipStream_t)stream);
 }
 
 int dmx_spectrum_supported(const dmx_params* prm, int32_t n_paths_loaded) {
@@ -368,28 +406,15 @@ int dmx_spectrum_supported(const dmx_params* prm, int32_t n_paths_loaded) {
 int dmx_channel_spectrum(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                          int64_t user_begin, int64_t user_count, double snr_linear, float* out_gamma, float* out_rate,
                          float* out_rate_k, void* stream) {
-    int rc = check_params(prm);
-    if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
-    if (user_count > 0 && !workspace) { set_error("workspace is NULL"); return DMX_ERR_ARG; }
-    if (user_count > 0 && !out_gamma && !out_rate && !out_rate_k) {
-        set_error("dmx_channel_spectrum: out_gamma, out_rate and out_rate_k are all NULL"); return DMX_ERR_ARG;
-    }
-    if ((rc = check_workspace_aligned(workspace))) return rc;
-    if (((uintptr_t)out_gamma & 3u) || ((uintptr_t)out_rate & 3u) || ((uintptr_t)out_rate_k & 3u)) {
-        set_error("out_gamma / out_rate / out_rate_k must be 4-byte aligned"); return DMX_ERR_ARG;
-    }
-    if (!prm->freq_domain) { set_error("dmx_channel_spectrum called with freq_domain = 0"); return DMX_ERR_ARG; }
-    if (prm->rx_filter) { set_error("dmx_channel_spectrum does not cover rx_filter = 1"); return DMX_ERR_ARG; }
-    if (!(snr_linear >= 1e-70) || !(snr_linear <= 1e70)) {
-        set_error("dmx_channel_spectrum: snr_linear must be finite and > 0 (1e-70 .. 1e70), got %g", snr_linear); return DMX_ERR_ARG;
-    }
-    rc = rate_shape(prm, n_paths_loaded);
-    if (rc < 0) return rc;
-    if (rc == 0) return DMX_ERR_SHAPE;
+    int rc = consumer_args("dmx_channel_spectrum", prm, workspace, n_ue, user_begin, user_count,
+                           !workspace ? "workspace is NULL" :
+                           !out_gamma && !out_rate && !out_rate_k ? "dmx_channel_spectrum: out_gamma, out_rate and out_rate_k are all NULL" : nullptr,
+                           ((uintptr_t)out_gamma | (uintptr_t)out_rate | (uintptr_t)out_rate_k) & 3u ?
+                               "out_gamma / out_rate / out_rate_k must be 4-byte aligned" : nullptr);
+    if (rc || (rc = check_snr("dmx_channel_spectrum: snr_linear", snr_linear)) || (rc = shape_status(rate_shape(prm, n_paths_loaded)))) return rc;
     if (user_count == 0) return DMX_OK;
-    WsView ws;
-    ws_carve(const_cast<void*>(workspace), n_ue, used_paths(prm, n_paths_loaded), &ws);
-    return launch_spectrum(*prm, ws, user_begin, user_count, snr_linear, out_gamma, out_rate, out_rate_k, (hipStream_t)stream);
+    return launch_spectrum(*prm, carve(prm, workspace, n_ue, n_paths_loaded), user_begin, user_count, snr_linear, out_gamma, out_rate,
+                           out_rate_k, (hipStream_t)stream);
 }
 
 // rate_shape and 1 <= n_layers <= min(M_rx, M_tx)
@@ -406,43 +431,40 @@ static int precoder_shape(const dmx_params* prm, int32_t n_paths_loaded, int32_t
 }
 
 int dmx_precoder_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_layers) {
-    int rc = check_params(prm);
-    if (rc) return rc;
-    return precoder_shape(prm, n_paths_loaded, n_layers);
+    return supported(prm, [&] { return precoder_shape(prm, n_paths_loaded, n_layers); });
 }
 
 int dmx_channel_precoders(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                           int64_t user_begin, int64_t user_count, double snr_linear, int32_t n_layers, float* out_gamma,
                           void* out_tx_c64, void* out_rx_c64, void* stream) {
-    int rc = check_params(prm);
-    if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
-    if (user_count > 0 && !workspace) { set_error("workspace is NULL"); return DMX_ERR_ARG; }
-    if (user_count > 0 && !out_gamma && !out_tx_c64 && !out_rx_c64) {
-        set_error("dmx_channel_precoders: out_gamma, out_tx_c64 and out_rx_c64 are all NULL"); return DMX_ERR_ARG;
-    }
-    if ((rc = check_workspace_aligned(workspace))) return rc;
-    if (((uintptr_t)out_gamma & 3u) || ((uintptr_t)out_tx_c64 & 7u) || ((uintptr_t)out_rx_c64 & 7u)) {
-        set_error("out_gamma must be 4-byte aligned, out_tx_c64 / out_rx_c64 8-byte aligned"); return DMX_ERR_ARG;
-    }
-    if (!prm->freq_domain) { set_error("dmx_channel_precoders called with freq_domain = 0"); return DMX_ERR_ARG; }
-    if (prm->rx_filter) { set_error("dmx_channel_precoders does not cover rx_filter = 1"); return DMX_ERR_ARG; }
-    if (!(snr_linear >= 1e-70) || !(snr_linear <= 1e70)) {
-        set_error("dmx_channel_precoders: snr_linear must be finite and > 0 (1e-70 .. 1e70), got %g", snr_linear); return DMX_ERR_ARG;
-    }
-    rc = precoder_shape(prm, n_paths_loaded, n_layers);
-    if (rc < 0) return rc;
-    if (rc == 0) return DMX_ERR_SHAPE;
+    int rc = consumer_args("dmx_channel_precoders", prm, workspace, n_ue, user_begin, user_count,
+                           !workspace ? "workspace is NULL" :
+                           !out_gamma && !out_tx_c64 && !out_rx_c64 ? "dmx_channel_precoders: out_gamma, out_tx_c64 and out_rx_c64 are all NULL" : nullptr,
+                           ((uintptr_t)out_gamma & 3u) || (((uintptr_t)out_tx_c64 | (uintptr_t)out_rx_c64) & 7u) ?
+                               "out_gamma must be 4-byte aligned, out_tx_c64 / out_rx_c64 8-byte aligned" : nullptr);
+    if (rc || (rc = check_snr("dmx_channel_precoders: snr_linear", snr_linear)) ||
+        (rc = shape_status(precoder_shape(prm, n_paths_loaded, n_layers)))) return rc;
     if (user_count == 0) return DMX_OK;
-    WsView ws;
-    ws_carve(const_cast<void*>(workspace), n_ue, used_paths(prm, n_paths_loaded), &ws);
-    return launch_precoders(*prm, ws, user_begin, user_count, snr_linear, n_layers, out_gamma, (float2*)out_tx_c64,
-                            (float2*)out_rx_c64, (hipStream_t)stream);
+    return launch_precoders(*prm, carve(prm, workspace, n_ue, n_paths_loaded), user_begin, user_count, snr_linear, n_layers, out_gamma,
+                            (float2*)out_tx_c64, (float2*)out_rx_c64, (hipStream_t)stream);
 }
 
-// 1: taken; 0: not taken, with the limit in the error string; negative: bad argument.  Every link's params are checked.
+// the links in range of `n_links` (none when the count is not one the kernel takes: the shape rule refuses it)
+static int links_in_range(int32_t n_links) { return n_links >= 1 && n_links <= DMX_MAX_LINKS ? n_links : 0; }
+
+// every link's parameter block
+static int check_link_params(const dmx_link* links, int32_t n_links) {
+    if (!links) { set_error("links is NULL"); return DMX_ERR_ARG; }
+    for (int b = 0; b < links_in_range(n_links); ++b) {
+        if (int rc = check_params(links[b].prm)) return rc;
+    }
+    return DMX_OK;
+}
+
+// Every link's params are checked.
 static int cell_rate_shape(const dmx_link* links, int32_t n_links) {
     if (!links) { set_error("links is NULL"); return DMX_ERR_ARG; }
-    if (n_links < 1 || n_links > DMX_MAX_LINKS) {
+    if (!links_in_range(n_links)) {
         set_error("cell rate: n_links = %d is outside the 1..%d links (DMX_MAX_LINKS) the kernel supports", n_links, DMX_MAX_LINKS);
         return 0;
     }
@@ -454,14 +476,11 @@ static int cell_rate_shape(const dmx_link* links, int32_t n_links) {
     const long long m_rx = (long long)p0->ue_shape[0] * p0->ue_shape[1];
     for (int b = 0; b < n_links; ++b) {
         const dmx_params* p = links[b].prm;
-        if (!p->freq_domain || p->rx_filter) {
-            set_error("cell rate: link %d: the rate needs freq_domain = 1 and rx_filter = 0", b); return 0;
-        }
-        const int P = used_paths(p, links[b].n_paths_loaded);
-        if (P < 1 || P > 32) {
-            set_error("cell rate: link %d: min(num_paths, loaded paths) = %d is outside the 1..32 paths the kernel supports", b, P);
-            return 0;
-        }
+        char link[48], who[64];
+        snprintf(link, sizeof(link), "cell rate: link %d", b);
+        snprintf(who, sizeof(who), "%s: the rate", link);
+        int P;
+        if (!shape_plain_fd(who, p) || !shape_used_paths(link, p, links[b].n_paths_loaded, &P)) return 0;
         if (p->ue_shape[0] != p0->ue_shape[0] || p->ue_shape[1] != p0->ue_shape[1]) {
             set_error("cell rate: link %d has ue_shape %d x %d, link 0 %d x %d: the links must share the UE array", b,
                       p->ue_shape[0], p->ue_shape[1], p0->ue_shape[0], p0->ue_shape[1]);
@@ -473,7 +492,7 @@ static int cell_rate_shape(const dmx_link* links, int32_t n_links) {
             return 0;
         }
     }
-    if (p0->n_selected < 1) { set_error("cell rate: at least one selected subcarrier is needed"); return 0; }
+    if (!shape_selected("cell rate", p0)) return 0;
     if (m_rx > 8) {
         set_error("cell rate: M_rx = %lld exceeds the 8 elements of the UE array the kernel supports", m_rx);
         return 0;
@@ -496,54 +515,41 @@ int dmx_cell_rate_supported(const dmx_link* links, int32_t n_links) { return cel
 int dmx_cell_rate(const dmx_link* links, int32_t n_links, int64_t n_ue, int64_t user_begin, int64_t user_count,
                   const int32_t* serving, float* out_rate, float* out_rate_k, int32_t* out_serving, float* out_link_snr,
                   void* stream) {
-    if (!links) { set_error("links is NULL"); return DMX_ERR_ARG; }
-    const bool count_ok = n_links >= 1 && n_links <= DMX_MAX_LINKS;
-    int rc = DMX_OK;
-    for (int b = 0; count_ok && b < n_links; ++b) {
-        if ((rc = check_params(links[b].prm))) return rc;
-    }
-    if ((rc = check_user_range(n_ue, user_begin, user_count))) return rc;
-    if (user_count > 0 && !out_rate) { set_error("workspace/out is NULL"); return DMX_ERR_ARG; }
-    for (int b = 0; count_ok && b < n_links; ++b) {
-        if (user_count > 0 && !links[b].workspace) { set_error("workspace/out is NULL"); return DMX_ERR_ARG; }
+    // consumer_args per link: the steps of one kind for every link before the next kind
+    int rc = check_link_params(links, n_links);
+    if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
+    if (user_count > 0 && !out_rate) { set_error("%s", WS_OUT_NULL); return DMX_ERR_ARG; }
+    const int nb = links_in_range(n_links);
+    for (int b = 0; b < nb; ++b) {
+        if (user_count > 0 && !links[b].workspace) { set_error("%s", WS_OUT_NULL); return DMX_ERR_ARG; }
         if ((rc = check_workspace_aligned(links[b].workspace))) return rc;
     }
-    if (((uintptr_t)serving & 3u) || ((uintptr_t)out_rate & 3u) || ((uintptr_t)out_rate_k & 3u) || ((uintptr_t)out_serving & 3u) ||
-        ((uintptr_t)out_link_snr & 3u)) {
+    if (((uintptr_t)serving | (uintptr_t)out_rate | (uintptr_t)out_rate_k | (uintptr_t)out_serving | (uintptr_t)out_link_snr) & 3u) {
         set_error("serving / out_rate / out_rate_k / out_serving / out_link_snr must be 4-byte aligned"); return DMX_ERR_ARG;
     }
-    for (int b = 0; count_ok && b < n_links; ++b) {
+    for (int b = 0; b < nb; ++b) {
         if (!links[b].prm->freq_domain) { set_error("dmx_cell_rate called with freq_domain = 0 on link %d", b); return DMX_ERR_ARG; }
         if (links[b].prm->rx_filter) { set_error("dmx_cell_rate does not cover rx_filter = 1 (link %d)", b); return DMX_ERR_ARG; }
-        // finite and > 0, and so is its square root in float32 (the kernel's scale of the path coefficients)
-        if (!(links[b].snr_linear >= 1e-70) || !(links[b].snr_linear <= 1e70)) {
-            set_error("dmx_cell_rate: snr_linear of link %d must be finite and > 0 (1e-70 .. 1e70), got %g", b, links[b].snr_linear);
-            return DMX_ERR_ARG;
-        }
+        char what[64];
+        snprintf(what, sizeof(what), "dmx_cell_rate: snr_linear of link %d", b);
+        if ((rc = check_snr(what, links[b].snr_linear))) return rc;
     }
-    rc = cell_rate_shape(links, n_links);
-    if (rc < 0) return rc;
-    if (rc == 0) return DMX_ERR_SHAPE;
+    if ((rc = shape_status(cell_rate_shape(links, n_links)))) return rc;
     if (user_count == 0) return DMX_OK;
     return launch_cell_rate(links, n_links, n_ue, user_begin, user_count, serving, out_rate, out_rate_k, out_serving,
                             out_link_snr, (hipStream_t)stream);
 }
 
-// 1: taken; 0: not taken, with the limit in the error string; negative: bad argument
 static int angle_delay_shape(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_rows, int32_t n_fft, int32_t n_taps) {
     if (n_paths_loaded < 0) { set_error("n_paths_loaded must be >= 0"); return DMX_ERR_ARG; }
-    if (!prm->freq_domain || prm->rx_filter) { set_error("angle-delay: needs freq_domain = 1 and rx_filter = 0"); return 0; }
-    if (prm->sc_stride < 1) {
+    if (!shape_plain_fd("angle-delay:", prm)) return 0;
+    if (prm->sc_stride < 1) {                                                // between the steps of shape_head
         set_error("angle-delay: needs a uniformly spaced selection promised by sc_stride > 0 (sc_k = sc_first + k * sc_stride), got "
                   "sc_stride = %d", prm->sc_stride);
         return 0;
     }
-    const int P = used_paths(prm, n_paths_loaded);
-    if (P < 1 || P > 32) {
-        set_error("angle-delay: min(num_paths, loaded paths) = %d is outside the 1..32 paths the kernel supports", P);
-        return 0;
-    }
-    if (prm->n_selected < 1) { set_error("angle-delay: at least one selected subcarrier is needed"); return 0; }
+    int P;
+    if (!shape_used_paths("angle-delay", prm, n_paths_loaded, &P) || !shape_selected("angle-delay", prm)) return 0;
     const long long m_rx = (long long)prm->ue_shape[0] * prm->ue_shape[1];
     if (m_rx > 8) { set_error("angle-delay: M_rx = %lld exceeds the 8 UE elements the kernel supports", m_rx); return 0; }
     if (n_fft < prm->n_selected || n_fft > (1 << 20)) {
@@ -562,20 +568,16 @@ static int angle_delay_shape(const dmx_params* prm, int32_t n_paths_loaded, int3
 }
 
 int dmx_angle_delay_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_rows, int32_t n_fft, int32_t n_taps) {
-    int rc = check_params(prm);
-    if (rc) return rc;
-    return angle_delay_shape(prm, n_paths_loaded, n_rows, n_fft, n_taps);
+    return supported(prm, [&] { return angle_delay_shape(prm, n_paths_loaded, n_rows, n_fft, n_taps); });
 }
 
 int dmx_channels_angle_delay(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                              int64_t user_begin, int64_t user_count, const void* codebook_c64, int32_t n_rows,
                              void* beam_workspace, size_t beam_workspace_bytes_, int32_t n_fft, int32_t n_taps, void* out_c64,
                              void* stream) {
-    WsView ws;
-    int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_c64, &ws);
+    int rc = consumer_args("dmx_channels_angle_delay", prm, workspace, n_ue, user_begin, user_count,
+                           !workspace || !out_c64 ? WS_OUT_NULL : nullptr, (uintptr_t)out_c64 & 7u ? "out must be 8-byte aligned" : nullptr);
     if (rc) return rc;
-    if (!prm->freq_domain) { set_error("dmx_channels_angle_delay called with freq_domain = 0"); return DMX_ERR_ARG; }
-    if (prm->rx_filter) { set_error("dmx_channels_angle_delay does not cover rx_filter = 1"); return DMX_ERR_ARG; }
     if (prm->sc_stride < 1) {
         set_error("dmx_channels_angle_delay needs a uniformly spaced selection promised by sc_stride > 0"); return DMX_ERR_ARG;
     }
@@ -584,25 +586,18 @@ int dmx_channels_angle_delay(const dmx_params* prm, const void* workspace, int64
         set_error("dmx_channels_angle_delay: without a codebook the rows are the %d BS elements, got n_rows = %d", m_tx, n_rows);
         return DMX_ERR_ARG;
     }
-    rc = angle_delay_shape(prm, n_paths_loaded, n_rows, n_fft, n_taps);
-    if (rc < 0) return rc;
-    if (rc == 0) return DMX_ERR_SHAPE;
+    if ((rc = shape_status(angle_delay_shape(prm, n_paths_loaded, n_rows, n_fft, n_taps)))) return rc;
     if (user_count == 0) return DMX_OK;
+    const WsView ws = carve(prm, workspace, n_ue, n_paths_loaded);
     if (codebook_c64 && (rc = check_beam_workspace(user_count, n_rows, ws.P, beam_workspace, beam_workspace_bytes_))) return rc;
     return launch_angle_delay(*prm, ws, user_begin, user_count, (const float2*)codebook_c64, n_rows, beam_workspace, n_fft, n_taps,
                               (float2*)out_c64, (hipStream_t)stream);
 }
 
-// 1: taken; 0: not taken, with the limit in the error string; negative: bad argument
 static int codebook_rate_shape(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_codewords, int32_t n_layers) {
-    if (n_paths_loaded < 0) { set_error("n_paths_loaded must be >= 0"); return DMX_ERR_ARG; }
-    if (!prm->freq_domain || prm->rx_filter) { set_error("codebook rate: needs freq_domain = 1 and rx_filter = 0"); return 0; }
-    const int P = used_paths(prm, n_paths_loaded);
-    if (P < 1 || P > 32) {
-        set_error("codebook rate: min(num_paths, loaded paths) = %d is outside the 1..32 paths the kernel supports", P);
-        return 0;
-    }
-    if (prm->n_selected < 1) { set_error("codebook rate: at least one selected subcarrier is needed"); return 0; }
+    int P;
+    const int head = shape_head("codebook rate", "codebook rate:", prm, n_paths_loaded, &P);
+    if (head != 1) return head;
     const long long m_rx = (long long)prm->ue_shape[0] * prm->ue_shape[1];
     if (m_rx > 8) { set_error("codebook rate: M_rx = %lld exceeds the 8 UE elements the kernel supports", m_rx); return 0; }
     const int l_max = m_rx < 4 ? (int)m_rx : 4;
@@ -626,45 +621,33 @@ static int codebook_rate_shape(const dmx_params* prm, int32_t n_paths_loaded, in
 }
 
 int dmx_codebook_rate_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_codewords, int32_t n_layers) {
-    int rc = check_params(prm);
-    if (rc) return rc;
-    return codebook_rate_shape(prm, n_paths_loaded, n_codewords, n_layers);
+    return supported(prm, [&] { return codebook_rate_shape(prm, n_paths_loaded, n_codewords, n_layers); });
 }
 
 // the checks dmx_codebook_rate and dmx_codebook_rate_subbands share, up to the shape; `out` is the output that must not be NULL,
-// `out_bits` the addresses of all outputs or'ed together and `out_names` their names for the message
+// `out_misaligned` the message when one of the outputs is not 4-byte aligned
 static int codebook_rate_args(const char* fn, const dmx_params* prm, const void* workspace, int64_t n_ue, int64_t user_begin,
-                              int64_t user_count, const void* codebook_c64, double snr_linear, const void* out, uintptr_t out_bits,
-                              const char* out_names) {
-    int rc = check_params(prm);
-    if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
-    if (user_count > 0 && (!workspace || !out)) { set_error("workspace/out is NULL"); return DMX_ERR_ARG; }
-    if (user_count > 0 && !codebook_c64) { set_error("codebook missing"); return DMX_ERR_ARG; }
-    if ((rc = check_workspace_aligned(workspace))) return rc;
-    if (out_bits & 3u) { set_error("%s must be 4-byte aligned", out_names); return DMX_ERR_ARG; }
-    if ((uintptr_t)codebook_c64 & 7u) { set_error("codebook must be 8-byte aligned"); return DMX_ERR_ARG; }
-    if (!prm->freq_domain) { set_error("%s called with freq_domain = 0", fn); return DMX_ERR_ARG; }
-    if (prm->rx_filter) { set_error("%s does not cover rx_filter = 1", fn); return DMX_ERR_ARG; }
-    // finite and > 0, and so is its square root in float32 (the kernel's scale of the path coefficients)
-    if (!(snr_linear >= 1e-70) || !(snr_linear <= 1e70)) {
-        set_error("%s: snr_linear must be finite and > 0 (1e-70 .. 1e70), got %g", fn, snr_linear); return DMX_ERR_ARG;
-    }
-    return DMX_OK;
+                              int64_t user_count, const void* codebook_c64, double snr_linear, const void* out,
+                              const char* out_misaligned) {
+    char snr_name[64];
+    snprintf(snr_name, sizeof(snr_name), "%s: snr_linear", fn);
+    const int rc = consumer_args(fn, prm, workspace, n_ue, user_begin, user_count,
+                                 !workspace || !out ? WS_OUT_NULL : !codebook_c64 ? "codebook missing" : nullptr,
+                                 out_misaligned ? out_misaligned : (uintptr_t)codebook_c64 & 7u ? "codebook must be 8-byte aligned" : nullptr);
+    return rc ? rc : check_snr(snr_name, snr_linear);
 }
 
 int dmx_codebook_rate(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                       int64_t user_begin, int64_t user_count, const void* codebook_c64, int32_t n_codewords, int32_t n_layers,
                       void* beam_workspace, size_t beam_workspace_bytes_, double snr_linear, float* out_rate, int32_t* out_pmi,
                       float* out_rate_c, void* stream) {
-    int rc = codebook_rate_args("dmx_codebook_rate", prm, workspace, n_ue, user_begin, user_count, codebook_c64, snr_linear, out_rate,
-                                (uintptr_t)out_rate | (uintptr_t)out_pmi | (uintptr_t)out_rate_c, "out_rate / out_pmi / out_rate_c");
-    if (rc) return rc;
-    rc = codebook_rate_shape(prm, n_paths_loaded, n_codewords, n_layers);
-    if (rc < 0) return rc;
-    if (rc == 0) return DMX_ERR_SHAPE;
+    int rc = codebook_rate_args("dmx_codebook_rate", prm, workspace, n_ue, user_begin, user_count,
+                                codebook_c64, snr_linear, out_rate,
+                                ((uintptr_t)out_rate | (uintptr_t)out_pmi | (uintptr_t)out_rate_c) & 3u ?
+                                    "out_rate / out_pmi / out_rate_c must be 4-byte aligned" : nullptr);
+    if (rc || (rc = shape_status(codebook_rate_shape(prm, n_paths_loaded, n_codewords, n_layers)))) return rc;
     if (user_count == 0) return DMX_OK;
-    WsView ws;
-    ws_carve(const_cast<void*>(workspace), n_ue, used_paths(prm, n_paths_loaded), &ws);
+    const WsView ws = carve(prm, workspace, n_ue, n_paths_loaded);
     if ((rc = check_beam_workspace(user_count, n_codewords * n_layers, ws.P, beam_workspace, beam_workspace_bytes_))) return rc;
     return launch_codebook_rate(*prm, ws, user_begin, user_count, (const float2*)codebook_c64, n_codewords, n_layers,
                                 beam_workspace, snr_linear, out_rate, out_pmi, out_rate_c, (hipStream_t)stream);
@@ -686,9 +669,7 @@ static int codebook_rate_subbands_shape(const dmx_params* prm, int32_t n_paths_l
 
 int dmx_codebook_rate_subbands_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_codewords, int32_t n_layers,
                                          int32_t subband_size) {
-    int rc = check_params(prm);
-    if (rc) return rc;
-    return codebook_rate_subbands_shape(prm, n_paths_loaded, n_codewords, n_layers, subband_size);
+    return supported(prm, [&] { return codebook_rate_subbands_shape(prm, n_paths_loaded, n_codewords, n_layers, subband_size); });
 }
 
 int dmx_codebook_rate_subbands(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
@@ -696,16 +677,13 @@ int dmx_codebook_rate_subbands(const dmx_params* prm, const void* workspace, int
                                int32_t n_layers, void* beam_workspace, size_t beam_workspace_bytes_, double snr_linear,
                                int32_t subband_size, float* out_rate_sb, int32_t* out_pmi_sb, float* out_rate_sb_c, float* out_rate,
                                int32_t* out_pmi, float* out_rate_c, void* stream) {
-    int rc = codebook_rate_args("dmx_codebook_rate_subbands", prm, workspace, n_ue, user_begin, user_count, codebook_c64, snr_linear,
-                                out_rate_sb, (uintptr_t)out_rate_sb | (uintptr_t)out_pmi_sb | (uintptr_t)out_rate_sb_c |
-                                (uintptr_t)out_rate | (uintptr_t)out_pmi | (uintptr_t)out_rate_c, "the outputs");
-    if (rc) return rc;
-    rc = codebook_rate_subbands_shape(prm, n_paths_loaded, n_codewords, n_layers, subband_size);
-    if (rc < 0) return rc;
-    if (rc == 0) return DMX_ERR_SHAPE;
+    int rc = codebook_rate_args("dmx_codebook_rate_subbands", prm, workspace, n_ue, user_begin,
+                                user_count, codebook_c64, snr_linear, out_rate_sb,
+                                ((uintptr_t)out_rate_sb | (uintptr_t)out_pmi_sb | (uintptr_t)out_rate_sb_c | (uintptr_t)out_rate |
+                                 (uintptr_t)out_pmi | (uintptr_t)out_rate_c) & 3u ? "the outputs must be 4-byte aligned" : nullptr);
+    if (rc || (rc = shape_status(codebook_rate_subbands_shape(prm, n_paths_loaded, n_codewords, n_layers, subband_size)))) return rc;
     if (user_count == 0) return DMX_OK;
-    WsView ws;
-    ws_carve(const_cast<void*>(workspace), n_ue, used_paths(prm, n_paths_loaded), &ws);
+    const WsView ws = carve(prm, workspace, n_ue, n_paths_loaded);
     if ((rc = check_beam_workspace(user_count, n_codewords * n_layers, ws.P, beam_workspace, beam_workspace_bytes_))) return rc;
     return launch_codebook_rate_subbands(*prm, ws, user_begin, user_count, (const float2*)codebook_c64, n_codewords, n_layers,
                                          beam_workspace, snr_linear, subband_size, out_rate_sb, out_pmi_sb, out_rate_sb_c, out_rate,

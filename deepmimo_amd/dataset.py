@@ -176,6 +176,38 @@ class Dataset(DotDict):
                 self._clear_cache_rotated_angles()
         return params
 
+    # -------------------------------------------------------------- steps every compute_* shares
+    def _call_params(self, params: Optional[ChannelGenParameters]) -> ChannelGenParameters:
+        """The parameters of a compute_* call, validated and stored: `params`, or the stored ones (the defaults when none
+        were ever set)."""
+        if params is None:
+            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
+        return self.set_channel_params(params)
+
+    @staticmethod
+    def _required_snr(who: str, snr_db, scalar: bool = True) -> None:
+        """`snr_db` is a keyword without a default that means anything: None is refused under the method's name, and a
+        `scalar` one has to be a finite number."""
+        if snr_db is None:
+            raise ValueError(f"{who}: snr_db (dB, keyword) is required")
+        if scalar:
+            from .engine import snr_linear_from_db
+            snr_linear_from_db(snr_db)
+
+    def _loaded_paths(self) -> int:
+        """Columns of the ray matrices: the paths every user was loaded with."""
+        return int(np.shape(self[c.POWER_PARAM_NAME])[1])
+
+    @staticmethod
+    def _deliver(res):
+        """What a compute_* returns for the HBM-resident result `res` - a tensor, a tuple or a dict of tensors: NumPy
+        unless ``config('channel_output') == 'torch'``."""
+        if config.get("channel_output", "numpy") == "torch":
+            return res
+        if isinstance(res, dict):
+            return {k: t.cpu().numpy() for k, t in res.items()}
+        return tuple(t.cpu().numpy() for t in res) if isinstance(res, tuple) else res.cpu().numpy()
+
     # -------------------------------------------------------------- GPU passes
     def _resolved_ue_rotation(self):
         """Per-user UE rotation in degrees or None for a constant one (dataset.py:327-338).  A (3, 2)
@@ -334,9 +366,7 @@ class Dataset(DotDict):
         """dataset.py:224-268.  Returns complex64 [n_ue, M_rx, M_tx, K] (freq_domain) or
         [n_ue, M_rx, M_tx, num_paths]: a NumPy array by default, the HBM-resident torch tensor when
         ``config('channel_output') == 'torch'``.  Cached as ``dataset.channel``."""
-        if params is None:
-            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
-        self.set_channel_params(params)
+        params = self._call_params(params)
         np.random.seed(1001)                                                   # dataset.py:250
         to_host = config.get("channel_output", "numpy") != "torch"
         if to_host:                                                            # before any GPU work is spent on it
@@ -363,9 +393,7 @@ class Dataset(DotDict):
         NumPy complex64 array [<= chunk_users, M_rx, M_tx, K].  For scenarios whose full tensor (1 MB per user at
         64x4 antennas x 512 subcarriers) fits neither host memory nor one NumPy array; stage 1 runs once, stage 2
         per chunk through the C-ABI's user_begin / user_count range.  Nothing is cached as ``channel``."""
-        if params is None:
-            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
-        self.set_channel_params(params)
+        params = self._call_params(params)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
         n = prep.n_ue
@@ -378,9 +406,7 @@ class Dataset(DotDict):
         """Beam-space channels ``codebook @ H`` for a TX codebook [n_beams, M_tx] (rows e.g. from
         ``dm.steering_vec``), complex64 [n_ue, M_rx, n_beams, K] - what docs/manual.ipynb cell 105 computes
         as ``F1 @ dataset.channel`` - without materialising H (extension).  Not cached."""
-        if params is None:
-            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
-        self.set_channel_params(params)
+        self._call_params(params)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
         if config.get("channel_output", "numpy") == "torch":
@@ -398,9 +424,7 @@ class Dataset(DotDict):
 
         Returns ``recv_bf_pwr_dbm`` float64 [n_ue, n_beams] (and ``best_beams`` with ``return_best``).  The raw means stay
         available as ``dataset['beam_mean_amplitude']`` (float32 [n_ue, n_beams])."""
-        if params is None:
-            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
-        self.set_channel_params(params)
+        self._call_params(params)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
         amp, _ = eng.beam_power(prep, codebook, want_best=False)
@@ -428,14 +452,11 @@ class Dataset(DotDict):
         ``rx_filter``, at most 32 used paths, tables within the LDS (include/deepmimo_amd.h has the rule): anything else
         raises ValueError before any GPU work.  Not cached."""
         from .engine import check_covariance_call
-        if params is None:
-            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
-        self.set_channel_params(params)
-        check_covariance_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), side)
+        params = self._call_params(params)
+        check_covariance_call(params, self._loaded_paths(), side)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
-        R = eng.covariance(prep, side=side)
-        return R if config.get("channel_output", "numpy") == "torch" else R.cpu().numpy()
+        return self._deliver(eng.covariance(prep, side=side))
 
     def compute_rate(self, params: Optional[ChannelGenParameters] = None, *, snr_db=None, per_subcarrier: bool = False,
                      power_allocation: str = "equal"):
@@ -458,29 +479,18 @@ class Dataset(DotDict):
         and keyword-only.  Users without a path get 0.  Frequency domain without ``rx_filter``, at most 32 used paths, the smaller array of at most 8 elements, tables
         within the LDS (include/deepmimo_amd.h has the rule): anything else raises ValueError before any GPU work.  Not
         cached."""
-        from .engine import check_rate_call, check_spectrum_call, snr_linear_from_db
+        from .engine import check_rate_call, check_spectrum_call
         if power_allocation not in ("equal", "waterfilling"):
             raise ValueError(f"compute_rate: power_allocation must be 'equal' or 'waterfilling', got {power_allocation!r}")
-        if snr_db is None:
-            raise ValueError("compute_rate: snr_db (dB, keyword) is required")
-        snr_linear_from_db(snr_db)
-        if params is None:
-            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
-        self.set_channel_params(params)
-        n_loaded = int(np.shape(self[c.POWER_PARAM_NAME])[1])
-        if power_allocation == "equal":
-            check_rate_call(params, n_loaded, snr_db)
-        else:
-            check_spectrum_call(params, n_loaded, snr_db)
+        equal = power_allocation == "equal"
+        self._required_snr("compute_rate", snr_db)
+        params = self._call_params(params)
+        (check_rate_call if equal else check_spectrum_call)(params, self._loaded_paths(), snr_db)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
-        if power_allocation == "equal":
-            res = eng.rate(prep, snr_db, per_subcarrier=per_subcarrier)
-        else:
-            res = eng.spectrum(prep, snr_db, gamma=False, rate=True, per_subcarrier=per_subcarrier)
-        if config.get("channel_output", "numpy") == "torch":
-            return res
-        return tuple(t.cpu().numpy() for t in res) if per_subcarrier else res.cpu().numpy()
+        if equal:
+            return self._deliver(eng.rate(prep, snr_db, per_subcarrier=per_subcarrier))
+        return self._deliver(eng.spectrum(prep, snr_db, gamma=False, rate=True, per_subcarrier=per_subcarrier))
 
     def compute_eigenmodes(self, params: Optional[ChannelGenParameters] = None, *, snr_db=None):
         """Eigenmodes of every user's channel per subcarrier, with no channel tensor written anywhere (extension;
@@ -494,18 +504,13 @@ class Dataset(DotDict):
         ``snr_db`` (total transmit power over noise power per subcarrier) is required and keyword-only.  Users without a
         path get 0.  The shapes taken are those of ``compute_rate``; anything else raises ValueError before any GPU work.
         Not cached."""
-        from .engine import check_spectrum_call, snr_linear_from_db
-        if snr_db is None:
-            raise ValueError("compute_eigenmodes: snr_db (dB, keyword) is required")
-        snr_linear_from_db(snr_db)
-        if params is None:
-            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
-        self.set_channel_params(params)
-        check_spectrum_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), snr_db)
+        from .engine import check_spectrum_call
+        self._required_snr("compute_eigenmodes", snr_db)
+        params = self._call_params(params)
+        check_spectrum_call(params, self._loaded_paths(), snr_db)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
-        g = eng.spectrum(prep, snr_db)
-        return g if config.get("channel_output", "numpy") == "torch" else g.cpu().numpy()
+        return self._deliver(eng.spectrum(prep, snr_db))
 
     def compute_precoders(self, params: Optional[ChannelGenParameters] = None, *, snr_db=None, n_layers: int = 1,
                           combiners: bool = False):
@@ -526,24 +531,18 @@ class Dataset(DotDict):
         noise power per subcarrier) is required and keyword-only: it puts the Gram matrix into float32 range and is the
         unit of ``gamma``; the vectors do not depend on it otherwise.  The shapes taken are those of ``compute_rate``;
         anything else raises ValueError before any GPU work.  Not cached."""
-        from .engine import check_precoder_call, snr_linear_from_db
-        if snr_db is None:
-            raise ValueError("compute_precoders: snr_db (dB, keyword) is required")
-        snr_linear_from_db(snr_db)
-        if params is None:
-            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
-        self.set_channel_params(params)
-        check_precoder_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), snr_db, n_layers)
-        to_host = config.get("channel_output", "numpy") != "torch"
-        if to_host:
+        from .engine import check_precoder_call
+        self._required_snr("compute_precoders", snr_db)
+        params = self._call_params(params)
+        check_precoder_call(params, self._loaded_paths(), snr_db, n_layers)
+        if config.get("channel_output", "numpy") != "torch":                   # before any GPU work is spent on it
             n_ant = [int(np.prod(params[k][c.PARAMSET_ANT_SHAPE])) for k in (c.PARAMSET_ANT_BS, c.PARAMSET_ANT_UE)]
             k_sel = int(np.size(params[c.PARAMSET_OFDM][c.PARAMSET_OFDM_SC_SAMP]))
             per_entry = 4 * min(n_ant) + 8 * int(n_layers) * (n_ant[0] + (n_ant[1] if combiners else 0))
             self._guard_host_copy(int(self.n_ue) * k_sel * per_entry)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
-        res = eng.precoders(prep, snr_db, n_layers=int(n_layers), rx=bool(combiners))
-        return tuple(t.cpu().numpy() for t in res) if to_host else res
+        return self._deliver(eng.precoders(prep, snr_db, n_layers=int(n_layers), rx=bool(combiners)))
 
     def compute_angle_delay(self, params: Optional[ChannelGenParameters] = None, *, n_taps=None, n_fft=None, codebook="dft"):
         """Angle-delay representation of every user's channel, with no channel tensor written anywhere (extension) - what
@@ -563,9 +562,7 @@ class Dataset(DotDict):
         from .geometry import dft_codebook
         if n_taps is None:
             raise ValueError("compute_angle_delay: n_taps (keyword) is required")
-        if params is None:
-            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
-        self.set_channel_params(params)
+        params = self._call_params(params)
         bs_shape = params[c.PARAMSET_ANT_BS][c.PARAMSET_ANT_SHAPE]
         m_tx = int(bs_shape[0]) * int(bs_shape[1])
         if codebook is None:
@@ -579,14 +576,13 @@ class Dataset(DotDict):
             if len(cb.shape) != 2 or cb.shape[1] != m_tx or cb.shape[0] < 1:
                 raise ValueError(f"compute_angle_delay: codebook must be [R, {m_tx}], got {tuple(cb.shape)}")
         n_rows = m_tx if cb is None else int(cb.shape[0])
-        n_fft = check_angle_delay_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), n_rows, n_fft, n_taps)
+        n_fft = check_angle_delay_call(params, self._loaded_paths(), n_rows, n_fft, n_taps)
         if config.get("channel_output", "numpy") != "torch":                   # before any GPU work is spent on it
             m_rx = int(np.prod(params[c.PARAMSET_ANT_UE][c.PARAMSET_ANT_SHAPE]))
             self._guard_host_copy(8 * int(self.n_ue) * m_rx * n_rows * int(n_taps))
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
-        X = eng.angle_delay(prep, int(n_taps), n_fft=n_fft, tx_codebook=cb)
-        return X if config.get("channel_output", "numpy") == "torch" else X.cpu().numpy()
+        return self._deliver(eng.angle_delay(prep, int(n_taps), n_fft=n_fft, tx_codebook=cb))
 
     def compute_codebook_rate(self, params: Optional[ChannelGenParameters] = None, *, codebook="dft", snr_db=None,
                               per_codeword: bool = False):
@@ -607,21 +603,23 @@ class Dataset(DotDict):
         ``compute_subband_pmi`` adds a PMI per subband and ``compute_csi_report`` the rank.  Frequency domain without
         ``rx_filter``, at most 32 used paths and 8 UE elements (include/deepmimo_amd.h has the rule): anything else raises
         ValueError before any GPU work.  Not cached."""
-        from .engine import check_codebook_rate_call, snr_linear_from_db
-        if snr_db is None:
-            raise ValueError("compute_codebook_rate: snr_db (dB, keyword) is required")
-        snr_linear_from_db(snr_db)
-        if params is None:
-            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
-        self.set_channel_params(params)
-        cb = _precoding_codebook("compute_codebook_rate", params, codebook)
-        check_codebook_rate_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), int(cb.shape[0]), int(cb.shape[1]), snr_db)
+        return self._codebook_rate("compute_codebook_rate", params, codebook, snr_db, per_codeword)
+
+    def _codebook_rate(self, who: str, params, codebook, snr_db, per_codeword, subbands: bool = False, subband_size=None):
+        """`compute_codebook_rate`, or with `subbands` `compute_subband_pmi`: the same checks and preparation, the launch
+        without or with a PMI per subband.  `who`: the public method, for the messages."""
+        from .engine import check_codebook_rate_call, check_subband_size
+        self._required_snr(who, snr_db)
+        if subbands:
+            subband_size = check_subband_size(subband_size)
+        params = self._call_params(params)
+        cb = _precoding_codebook(who, params, codebook)
+        check_codebook_rate_call(params, self._loaded_paths(), int(cb.shape[0]), int(cb.shape[1]), snr_db)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
-        res = eng.codebook_rate(prep, cb, snr_db, per_codeword=bool(per_codeword))
-        if config.get("channel_output", "numpy") == "torch":
-            return res
-        return tuple(t.cpu().numpy() for t in res)
+        if subbands:
+            return self._deliver(eng.codebook_rate_subbands(prep, cb, snr_db, subband_size, per_codeword=bool(per_codeword)))
+        return self._deliver(eng.codebook_rate(prep, cb, snr_db, per_codeword=bool(per_codeword)))
 
     def compute_subband_pmi(self, params: Optional[ChannelGenParameters] = None, *, codebook="dft", snr_db=None,
                             subband_size=None, per_codeword: bool = False):
@@ -640,22 +638,7 @@ class Dataset(DotDict):
         ``compute_codebook_rate`` returns for the selection ``sc[s B : (s + 1) B]`` bit for bit; with one subband all of it
         equals ``compute_codebook_rate``.  ``codebook``, ``snr_db``, the shapes taken and the return convention are those of
         ``compute_codebook_rate``; anything else raises ValueError before any GPU work.  Not cached."""
-        from .engine import check_codebook_rate_call, check_subband_size, snr_linear_from_db
-        if snr_db is None:
-            raise ValueError("compute_subband_pmi: snr_db (dB, keyword) is required")
-        snr_linear_from_db(snr_db)
-        subband_size = check_subband_size(subband_size)
-        if params is None:
-            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
-        self.set_channel_params(params)
-        cb = _precoding_codebook("compute_subband_pmi", params, codebook)
-        check_codebook_rate_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), int(cb.shape[0]), int(cb.shape[1]), snr_db)
-        np.random.seed(1001)
-        eng, prep = self._run_prep(want_side="light")
-        res = eng.codebook_rate_subbands(prep, cb, snr_db, subband_size, per_codeword=bool(per_codeword))
-        if config.get("channel_output", "numpy") == "torch":
-            return res
-        return tuple(t.cpu().numpy() for t in res)
+        return self._codebook_rate("compute_subband_pmi", params, codebook, snr_db, per_codeword, True, subband_size)
 
     def compute_csi_report(self, params: Optional[ChannelGenParameters] = None, *, codebooks=None, snr_db=None,
                            subband_size=None):
@@ -673,14 +656,10 @@ class Dataset(DotDict):
         duplicate L, an empty ``codebooks`` or a shape not taken raises ValueError before any GPU work.  Mapping a rate to a
         CQI index is a table lookup left to the caller.  Not cached."""
         import torch
-        from .engine import check_codebook_rate_call, check_subband_size, snr_linear_from_db
-        if snr_db is None:
-            raise ValueError("compute_csi_report: snr_db (dB, keyword) is required")
-        snr_linear_from_db(snr_db)
+        from .engine import check_codebook_rate_call, check_subband_size
+        self._required_snr("compute_csi_report", snr_db)
         subband_size = check_subband_size(subband_size)
-        if params is None:
-            params = ChannelGenParameters() if self._data.get(c.CH_PARAMS_PARAM_NAME) is None else self.ch_params
-        self.set_channel_params(params)
+        params = self._call_params(params)
         if codebooks is None or isinstance(codebooks, (str, bool, int, float, complex)) or hasattr(codebooks, "shape") or \
                 len(codebooks) == 0:
             raise ValueError("compute_csi_report: codebooks must be a non-empty sequence of arrays [C, L, M_tx], one per rank")
@@ -689,7 +668,7 @@ class Dataset(DotDict):
         if len(set(ranks)) != len(ranks):
             raise ValueError(f"compute_csi_report: the codebooks must have distinct layer counts, got L = {ranks}")
         for cb in cbs:
-            check_codebook_rate_call(params, int(np.shape(self[c.POWER_PARAM_NAME])[1]), int(cb.shape[0]), int(cb.shape[1]), snr_db)
+            check_codebook_rate_call(params, self._loaded_paths(), int(cb.shape[0]), int(cb.shape[1]), snr_db)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
         per_rank = [eng.codebook_rate_subbands(prep, cb, snr_db, subband_size) for cb in cbs]
@@ -702,9 +681,7 @@ class Dataset(DotDict):
             rate_sb, pmi_sb = torch.where(take[:, None], rs, rate_sb), torch.where(take[:, None], ps, pmi_sb)
         out = dict(rank=rank, rate=rate, pmi=pmi, rate_sb=rate_sb, pmi_sb=pmi_sb,
                    rate_by_rank=torch.stack([t[0] for t in per_rank], dim=1))
-        if config.get("channel_output", "numpy") != "torch":
-            out = {k: t.cpu().numpy() for k, t in out.items()}
-        return DotDict(out)
+        return DotDict(self._deliver(out))
 
     def compute_pathloss(self, coherent: bool = True) -> np.ndarray:
         """Path loss in dB assuming 0 dBm transmitted power (dataset.py:541-566); cached as ``pathloss``."""
@@ -998,8 +975,7 @@ class MacroDataset:
         elements; include/deepmimo_amd.h has the rule): anything else raises ValueError before any GPU work.  Not cached."""
         from .engine import check_cell_rate_call
         B = len(self.datasets)
-        if snr_db is None:
-            raise ValueError("compute_cell_rate: snr_db (dB, keyword) is required")
+        Dataset._required_snr("compute_cell_rate", snr_db, scalar=False)      # one per link: check_cell_rate_call's
         if not 1 <= B <= 8:
             raise ValueError(f"compute_cell_rate: {B} children, the call takes 1..8 base stations")
         n_ue = int(self.datasets[0].n_ue)
@@ -1013,18 +989,13 @@ class MacroDataset:
             serving = np.asarray(serving)
             if serving.dtype.kind not in "iu" or serving.shape != (n_ue,):
                 raise ValueError(f"compute_cell_rate: serving must be None, an int or an int array of shape ({n_ue},)")
-        for i, d in enumerate(self.datasets):
-            if plist[i] is None:
-                plist[i] = ChannelGenParameters() if d._data.get(c.CH_PARAMS_PARAM_NAME) is None else d.ch_params
-            d.set_channel_params(plist[i])
-        check_cell_rate_call(plist, [int(np.shape(d[c.POWER_PARAM_NAME])[1]) for d in self.datasets], snr_db)
+        plist = [d._call_params(prm) for d, prm in zip(self.datasets, plist)]
+        check_cell_rate_call(plist, [d._loaded_paths() for d in self.datasets], snr_db)
         np.random.seed(1001)
         runs = [d._run_prep(want_side="light") for d in self.datasets]
         res = runs[0][0].cell_rate([prep for _, prep in runs], snr_db, serving=serving, per_subcarrier=per_subcarrier,
                                    details=details)
-        if config.get("channel_output", "numpy") == "torch":
-            return res
-        return tuple(t.cpu().numpy() for t in res) if isinstance(res, tuple) else res.cpu().numpy()
+        return Dataset._deliver(res)
 
     def __getitem__(self, idx):
         if isinstance(idx, (int, slice)):

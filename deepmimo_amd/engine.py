@@ -180,6 +180,11 @@ def covariance_side(side) -> int:
     return nat.COV_SIDES[side]
 
 
+def _ptr(t: Optional[torch.Tensor]):
+    """The pointer argument of a tensor a C call reads or writes; None (NULL) for one that is not there."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 def _fill_shape_fields(p: nat.DmxParams, params, n_selected: int):
     """The fields of dmx_params that say how large a call is: all the host-only dmx_*_supported queries read."""
     bs, ue, ofdm = params[c.PARAMSET_ANT_BS], params[c.PARAMSET_ANT_UE], params[c.PARAMSET_OFDM]
@@ -192,25 +197,47 @@ def _fill_shape_fields(p: nat.DmxParams, params, n_selected: int):
     p.bandwidth = float(ofdm[c.PARAMSET_OFDM_BANDWIDTH])
 
 
+def _query_params(who: str, params, needs: Optional[str] = None, promise_stride: bool = False):
+    """(dmx_params of a host-only dmx_*_supported query, the int64 selection) for validated ChannelGenParameters.  Time
+    domain and rx_filter are ValueErrors under `who` (`needs`: the head of the first where it is not "`who`: needs"), an index
+    outside int32 is check_selection's.  `promise_stride`: sc_first / sc_stride from `uniform_stride` of the selection."""
+    ofdm = params[c.PARAMSET_OFDM]
+    if not params[c.PARAMSET_FD_CH]:
+        raise ValueError(f"{needs or who + ': needs'} the frequency-domain channel (freq_domain = 1)")
+    if ofdm[c.PARAMSET_OFDM_LPF]:
+        raise ValueError(f"{who}: ofdm.rx_filter = 1 is not covered")
+    sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
+    p = nat.DmxParams()
+    _fill_shape_fields(p, params, sel.size)
+    if promise_stride:
+        p.sc_first, p.sc_stride = uniform_stride(sel)
+    p._host_sel = (C.c_int32 * max(1, int(sel.size)))()       # the query reads the count, never the array; lives with p
+    p.selected_subcarriers = C.addressof(p._host_sel)
+    return p, sel
+
+
+def _ask(who: str, query: str, *args, refusal: str = "shape not supported: "):
+    """Ask the library's host-only `query`; anything but "taken" is a ValueError with the library's message, which names
+    the limit."""
+    lib = nat.load()
+    if getattr(lib, query)(*args) != 1:
+        raise ValueError(f"{who}: {refusal}" + lib.dmx_last_error().decode("utf-8", "replace"))
+
+
+def _int_arg(who: str, name: str, v) -> int:
+    """`v` as a C int32 argument (clipped, so the library refuses what is out of range); no integer: ValueError."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError(f"{who}: {name} must be an integer, got {v!r}")
+    return int(np.clip(v, -2 ** 31, 2 ** 31 - 1))
+
+
 def check_covariance_call(params, n_paths_loaded: int, side) -> int:
     """Everything `Dataset.compute_covariance` can refuse without a GPU, as ValueError: the side, time domain, rx_filter,
     and a shape dmx_covariance_supported does not take (the message is the library's and names the limit).  `params`:
     validated ChannelGenParameters.  Returns the side id."""
     sid = covariance_side(side)
-    ofdm = params[c.PARAMSET_OFDM]
-    if not params[c.PARAMSET_FD_CH]:
-        raise ValueError("covariance: needs the frequency-domain channel (freq_domain = 1)")
-    if ofdm[c.PARAMSET_OFDM_LPF]:
-        raise ValueError("covariance: ofdm.rx_filter = 1 is not covered")
-    sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
-    p = nat.DmxParams()
-    _fill_shape_fields(p, params, sel.size)
-    host_sel = (C.c_int32 * max(1, int(sel.size)))()          # the query reads the count, never the array
-    p.selected_subcarriers = C.addressof(host_sel)
-    lib = nat.load()
-    rc = lib.dmx_covariance_supported(C.byref(p), int(n_paths_loaded), sid)
-    if rc != 1:
-        raise ValueError("covariance: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
+    p, _ = _query_params("covariance", params)
+    _ask("covariance", "dmx_covariance_supported", C.byref(p), int(n_paths_loaded), sid)
     return sid
 
 
@@ -221,76 +248,34 @@ def snr_linear_from_db(snr_db) -> float:
     return 10.0 ** (float(snr_db) / 10.0)
 
 
+def _check_rate_call(who: str, query: str, params, n_paths_loaded: int, snr_db) -> float:
+    snr = snr_linear_from_db(snr_db)
+    p, _ = _query_params(who, params)
+    _ask(who, query, C.byref(p), int(n_paths_loaded))
+    return snr
+
+
 def check_rate_call(params, n_paths_loaded: int, snr_db) -> float:
     """Everything `Dataset.compute_rate` can refuse without a GPU, as ValueError: time domain, rx_filter, an snr_db that is
     not finite, and a shape dmx_rate_supported does not take (the message is the library's and names the limit).  `params`:
     validated ChannelGenParameters.  Returns the linear SNR."""
-    snr = snr_linear_from_db(snr_db)
-    ofdm = params[c.PARAMSET_OFDM]
-    if not params[c.PARAMSET_FD_CH]:
-        raise ValueError("rate: needs the frequency-domain channel (freq_domain = 1)")
-    if ofdm[c.PARAMSET_OFDM_LPF]:
-        raise ValueError("rate: ofdm.rx_filter = 1 is not covered")
-    sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
-    p = nat.DmxParams()
-    _fill_shape_fields(p, params, sel.size)
-    host_sel = (C.c_int32 * max(1, int(sel.size)))()          # the query reads the count, never the array
-    p.selected_subcarriers = C.addressof(host_sel)
-    lib = nat.load()
-    rc = lib.dmx_rate_supported(C.byref(p), int(n_paths_loaded))
-    if rc != 1:
-        raise ValueError("rate: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
-    return snr
+    return _check_rate_call("rate", "dmx_rate_supported", params, n_paths_loaded, snr_db)
 
 
 def check_spectrum_call(params, n_paths_loaded: int, snr_db) -> float:
     """`check_rate_call` for `Dataset.compute_eigenmodes` and the water-filling rate: the same refusals (the spectrum call
     takes exactly the shapes of the rate), asked of dmx_spectrum_supported.  Returns the linear SNR."""
-    snr = snr_linear_from_db(snr_db)
-    ofdm = params[c.PARAMSET_OFDM]
-    if not params[c.PARAMSET_FD_CH]:
-        raise ValueError("spectrum: needs the frequency-domain channel (freq_domain = 1)")
-    if ofdm[c.PARAMSET_OFDM_LPF]:
-        raise ValueError("spectrum: ofdm.rx_filter = 1 is not covered")
-    sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
-    p = nat.DmxParams()
-    _fill_shape_fields(p, params, sel.size)
-    host_sel = (C.c_int32 * max(1, int(sel.size)))()          # the query reads the count, never the array
-    p.selected_subcarriers = C.addressof(host_sel)
-    lib = nat.load()
-    rc = lib.dmx_spectrum_supported(C.byref(p), int(n_paths_loaded))
-    if rc != 1:
-        raise ValueError("spectrum: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
-    return snr
+    return _check_rate_call("spectrum", "dmx_spectrum_supported", params, n_paths_loaded, snr_db)
 
 
 def check_precoder_call(params, n_paths_loaded: int, snr_db, n_layers) -> float:
     """`check_spectrum_call` for `Dataset.compute_precoders`: the same refusals, and an `n_layers` that is not an integer
     in 1..min(M_rx, M_tx), asked of dmx_precoder_supported.  Returns the linear SNR."""
     snr = snr_linear_from_db(snr_db)
-    if isinstance(n_layers, bool) or not isinstance(n_layers, (int, np.integer)):
-        raise ValueError(f"precoders: n_layers must be an integer, got {n_layers!r}")
-    ofdm = params[c.PARAMSET_OFDM]
-    if not params[c.PARAMSET_FD_CH]:
-        raise ValueError("precoders: needs the frequency-domain channel (freq_domain = 1)")
-    if ofdm[c.PARAMSET_OFDM_LPF]:
-        raise ValueError("precoders: ofdm.rx_filter = 1 is not covered")
-    sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
-    p = nat.DmxParams()
-    _fill_shape_fields(p, params, sel.size)
-    host_sel = (C.c_int32 * max(1, int(sel.size)))()          # the query reads the count, never the array
-    p.selected_subcarriers = C.addressof(host_sel)
-    lib = nat.load()
-    rc = lib.dmx_precoder_supported(C.byref(p), int(n_paths_loaded), int(np.clip(n_layers, -2 ** 31, 2 ** 31 - 1)))
-    if rc != 1:
-        raise ValueError("precoders: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
+    n_layers = _int_arg("precoders", "n_layers", n_layers)
+    p, _ = _query_params("precoders", params)
+    _ask("precoders", "dmx_precoder_supported", C.byref(p), int(n_paths_loaded), n_layers)
     return snr
-
-
-def _int_arg(name: str, v) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f"angle-delay: {name} must be an integer, got {v!r}")
-    return int(np.clip(v, -2 ** 31, 2 ** 31 - 1))
 
 
 def check_angle_delay_call(params, n_paths_loaded: int, n_rows, n_fft, n_taps) -> int:
@@ -298,27 +283,13 @@ def check_angle_delay_call(params, n_paths_loaded: int, n_rows, n_fft, n_taps) -
     that is not uniformly spaced, `n_rows` / `n_fft` / `n_taps` that are no integers, and a shape dmx_angle_delay_supported
     does not take (the message is the library's and names the limit).  `params`: validated ChannelGenParameters;
     `n_fft` None = the number of selected subcarriers.  Returns n_fft."""
-    ofdm = params[c.PARAMSET_OFDM]
-    if not params[c.PARAMSET_FD_CH]:
-        raise ValueError("angle-delay: needs the frequency-domain channel (freq_domain = 1)")
-    if ofdm[c.PARAMSET_OFDM_LPF]:
-        raise ValueError("angle-delay: ofdm.rx_filter = 1 is not covered")
-    sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
-    first, stride = uniform_stride(sel)
-    if stride <= 0:
+    p, sel = _query_params("angle-delay", params, promise_stride=True)
+    if p.sc_stride <= 0:
         raise ValueError("angle-delay: ofdm.selected_subcarriers must be uniformly spaced, first + k * stride with 0 < stride < 2^20 "
                          "and |first| < 2^30 (the delay transform is an inverse DFT over the selection)")
-    n_fft = int(sel.size) if n_fft is None else _int_arg("n_fft", n_fft)
-    p = nat.DmxParams()
-    _fill_shape_fields(p, params, sel.size)
-    p.sc_first, p.sc_stride = first, stride
-    host_sel = (C.c_int32 * max(1, int(sel.size)))()          # the query reads the count, never the array
-    p.selected_subcarriers = C.addressof(host_sel)
-    lib = nat.load()
-    rc = lib.dmx_angle_delay_supported(C.byref(p), int(n_paths_loaded), _int_arg("n_rows", n_rows), n_fft,
-                                       _int_arg("n_taps", n_taps))
-    if rc != 1:
-        raise ValueError("angle-delay: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
+    n_fft = int(sel.size) if n_fft is None else _int_arg("angle-delay", "n_fft", n_fft)
+    _ask("angle-delay", "dmx_angle_delay_supported", C.byref(p), int(n_paths_loaded), _int_arg("angle-delay", "n_rows", n_rows),
+         n_fft, _int_arg("angle-delay", "n_taps", n_taps))
     return n_fft
 
 
@@ -328,24 +299,9 @@ def check_codebook_rate_call(params, n_paths_loaded: int, n_codewords, n_layers,
     (the message is the library's and names the limit).  `params`: validated ChannelGenParameters.  Returns the linear
     SNR."""
     snr = snr_linear_from_db(snr_db)
-    for name, v in (("n_codewords", n_codewords), ("n_layers", n_layers)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"codebook rate: {name} must be an integer, got {v!r}")
-    ofdm = params[c.PARAMSET_OFDM]
-    if not params[c.PARAMSET_FD_CH]:
-        raise ValueError("codebook rate: needs the frequency-domain channel (freq_domain = 1)")
-    if ofdm[c.PARAMSET_OFDM_LPF]:
-        raise ValueError("codebook rate: ofdm.rx_filter = 1 is not covered")
-    sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
-    p = nat.DmxParams()
-    _fill_shape_fields(p, params, sel.size)
-    host_sel = (C.c_int32 * max(1, int(sel.size)))()          # the query reads the count, never the array
-    p.selected_subcarriers = C.addressof(host_sel)
-    lib = nat.load()
-    clip = lambda v: int(np.clip(v, -2 ** 31, 2 ** 31 - 1))   # noqa: E731
-    rc = lib.dmx_codebook_rate_supported(C.byref(p), int(n_paths_loaded), clip(n_codewords), clip(n_layers))
-    if rc != 1:
-        raise ValueError("codebook rate: shape not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
+    n_codewords, n_layers = _int_arg("codebook rate", "n_codewords", n_codewords), _int_arg("codebook rate", "n_layers", n_layers)
+    p, _ = _query_params("codebook rate", params)
+    _ask("codebook rate", "dmx_codebook_rate_supported", C.byref(p), int(n_paths_loaded), n_codewords, n_layers)
     return snr
 
 
@@ -384,27 +340,15 @@ def check_cell_rate_call(params_list, n_paths_loaded_list, snr_db):
     links = (nat.DmxLink * B)()
     keep, first_sel = [], None
     for b, params in enumerate(params_list):
-        ofdm = params[c.PARAMSET_OFDM]
-        if not params[c.PARAMSET_FD_CH]:
-            raise ValueError(f"cell rate: link {b} needs the frequency-domain channel (freq_domain = 1)")
-        if ofdm[c.PARAMSET_OFDM_LPF]:
-            raise ValueError(f"cell rate: link {b}: ofdm.rx_filter = 1 is not covered")
-        sel, _ = check_selection(ofdm[c.PARAMSET_OFDM_SC_SAMP])
+        p, sel = _query_params(f"cell rate: link {b}", params, needs=f"cell rate: link {b} needs")
         if b and not np.array_equal(sel, first_sel):
             raise ValueError(f"cell rate: link {b} selects other subcarriers than link 0; the links must share the selection")
         first_sel = sel if b == 0 else first_sel
-        p = nat.DmxParams()
-        _fill_shape_fields(p, params, sel.size)
-        host_sel = (C.c_int32 * max(1, int(sel.size)))()      # the query reads the count, never the array
-        p.selected_subcarriers = C.addressof(host_sel)
-        keep += [p, host_sel]
+        keep.append(p)
         links[b].prm = C.pointer(p)
         links[b].n_paths_loaded = int(loaded[b])
         links[b].snr_linear = snrs[b]
-    lib = nat.load()
-    rc = lib.dmx_cell_rate_supported(links, B)
-    if rc != 1:
-        raise ValueError("cell rate: links not supported: " + lib.dmx_last_error().decode("utf-8", "replace"))
+    _ask("cell rate", "dmx_cell_rate_supported", links, B, refusal="links not supported: ")
     return snrs
 
 
@@ -419,9 +363,7 @@ class ChannelEngine:
         fields = {}
         shape = None
         for k in c.RAY_FIELDS:
-            v = data[k]
-            t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
-            t = t.to(device=self.device, dtype=torch.float32).contiguous()
+            t = self._to_dev_f32(data[k])
             if t.dim() != 2:
                 raise ValueError(f"ray matrix '{k}' must be 2-D [n_ue, n_paths], got {tuple(t.shape)}")
             if shape is None:
@@ -436,9 +378,13 @@ class ChannelEngine:
             da = self._to_dev_f32(data[c.DOPPLER_ACC_PARAM_NAME])
         return DeviceRays(n_ue=shape[0], n_paths=shape[1], fields=fields, doppler_vel=dv, doppler_acc=da)
 
+    def _to_dev(self, v, dtype, np_dtype=None):
+        """`v` (NumPy or torch) as a contiguous device tensor of `dtype`; `np_dtype`: convert a NumPy input on the host first."""
+        t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v, dtype=np_dtype))
+        return t.to(device=self.device, dtype=dtype).contiguous()
+
     def _to_dev_f32(self, v):
-        t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
-        return t.to(device=self.device, dtype=torch.float32).contiguous()
+        return self._to_dev(v, torch.float32, np.float32)
 
     # ------------------------------------------------------------------ C structs
     def _params_struct(self, params, bs_fov, ue_fov, ue_rot_per_user: Optional[torch.Tensor],
@@ -495,18 +441,28 @@ class ChannelEngine:
         off = (-buf.data_ptr()) % 256
         return buf[off:off + n]
 
+    def _outs(self, out, wanted, torch_names: bool = False):
+        """The tensors a call writes: `wanted` is a list of (shape, dtype).  `out` None: new ones; else the tensor, or the
+        tuple / list of tensors in the same order, to write into - each has to be the contiguous tensor of its shape and
+        dtype.  `torch_names`: the message spells the dtype "torch.float32", not "float32"."""
+        given = list(out) if isinstance(out, (tuple, list)) else [out] * (out is not None)
+        if out is not None and len(given) != len(wanted):
+            raise ValueError(f"out must hold {len(wanted)} tensors, one per requested output")
+        res = []
+        for i, (shape, dt) in enumerate(wanted):
+            t = given[i] if given else torch.empty(shape, dtype=dt, device=self.device)
+            if t.dtype != dt or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+                raise ValueError(f"out must be a contiguous {dt if torch_names else str(dt)[6:]} tensor of shape {shape}")
+            res.append(t)
+        return res
+
     def _out(self, out: Optional[torch.Tensor], shape) -> torch.Tensor:
         """`out` when it is the contiguous complex64 tensor of `shape` a kernel writes, a new one when it is None."""
-        if out is None:
-            return torch.empty(shape, dtype=torch.complex64, device=self.device)
-        if out.dtype != torch.complex64 or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous complex64 tensor of shape {shape}")
-        return out
+        return self._outs(out, [(shape, torch.complex64)])[0]
 
     def _codebook(self, tx_codebook, m_tx: int, min_beams: int = 0) -> torch.Tensor:
         """[n_beams, M_tx] beamforming matrix as a contiguous complex64 device tensor."""
-        cb = tx_codebook if isinstance(tx_codebook, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tx_codebook))
-        cb = cb.to(device=self.device, dtype=torch.complex64).contiguous()
+        cb = self._to_dev(tx_codebook, torch.complex64)
         if cb.dim() != 2 or cb.shape[1] != m_tx or cb.shape[0] < min_beams:
             raise ValueError(f"tx_codebook must be [n_beams, {m_tx}], got {tuple(cb.shape)}")
         return cb
@@ -691,10 +647,7 @@ class ChannelEngine:
         """dmx_fd_direct_supported for these rays and parameters (host-only query; `channels_direct` raises where it
         says no).  structs: what `_call_structs` returned for the same arguments, to build them once."""
         p = (structs or self._call_structs(rays, params, **prepare_kwargs))[0]
-        rc = self.lib.dmx_fd_direct_supported(C.byref(p), rays.n_paths)
-        if rc < 0:
-            nat.check(rc, "dmx_fd_direct_supported")
-        return rc == 1
+        return self._supported("dmx_fd_direct_supported", C.byref(p), rays.n_paths)
 
     def auto_fd_choice(self, p: nat.DmxParams, n_paths_loaded: int, sc_abs_max: int) -> int:
         """The kernel ``variant = 0`` runs for this parameter block (dmx_fd_kernel_choice, with `fd_variant`'s rule for
@@ -818,8 +771,7 @@ class ChannelEngine:
         Returns (mean_amplitude float32 [user_count, n_beams], best_beam int32 [user_count] or None), both in HBM:
         mean_amplitude[u, b] = np.abs(F @ H[u]).mean(axis=0).mean(axis=-1)."""
         p = prep.params_struct
-        if user_count is None:
-            user_count = prep.n_ue - user_begin
+        user_count = self._users(prep.n_ue, user_begin, user_count)
         m_tx = p.bs_shape[0] * p.bs_shape[1]
         cb = self._codebook(tx_codebook, m_tx, min_beams=1)
         if not p.freq_domain or p.rx_filter:
@@ -833,19 +785,35 @@ class ChannelEngine:
         with torch.cuda.device(self.device):
             nbytes = int(self.lib.dmx_beam_workspace_bytes(C.byref(p), user_count, prep.n_paths_loaded, nb))
             bws = self._scratch(nbytes)
-            rc = self.lib.dmx_beam_power(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue, prep.n_paths_loaded,
-                                         user_begin, user_count, C.c_void_p(cb.data_ptr()), nb,
-                                         C.c_void_p(bws.data_ptr()), nbytes, C.c_void_p(amp.data_ptr()),
-                                         C.c_void_p(best.data_ptr()) if want_best else None, self._stream_ptr())
+            rc = self.lib.dmx_beam_power(*self._record_args(prep, user_begin, user_count), _ptr(cb), nb, _ptr(bws), nbytes,
+                                         _ptr(amp), _ptr(best), self._stream_ptr())
             nat.check(rc, "dmx_beam_power")
         return amp, best
 
+    # ------------------------------------------------------------------ consumers of the path records
+    def _supported(self, query: str, *args) -> bool:
+        """A host-only dmx_*_supported query: its yes or no; a bad argument raises."""
+        rc = getattr(self.lib, query)(*args)
+        if rc < 0:
+            nat.check(rc, query)
+        return rc == 1
+
+    def _prep_supported(self, query: str, prep: PrepResult, *ints) -> bool:
+        return self._supported(query, C.byref(prep.params_struct), prep.n_paths_loaded, *map(int, ints))
+
+    @staticmethod
+    def _users(n_ue: int, user_begin: int, user_count: Optional[int]) -> int:
+        """`user_count` of a call: None means up to the last user."""
+        return n_ue - user_begin if user_count is None else user_count
+
+    def _record_args(self, prep: PrepResult, user_begin: int, user_count: int):
+        """The leading arguments of every C call on a preparation's records."""
+        return (C.byref(prep.params_struct), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue, prep.n_paths_loaded,
+                int(user_begin), int(user_count))
+
     def covariance_supported(self, prep: PrepResult, side="tx") -> bool:
         """dmx_covariance_supported for this preparation (host-only query; `covariance` raises where it says no)."""
-        rc = self.lib.dmx_covariance_supported(C.byref(prep.params_struct), prep.n_paths_loaded, covariance_side(side))
-        if rc < 0:
-            nat.check(rc, "dmx_covariance_supported")
-        return rc == 1
+        return self._prep_supported("dmx_covariance_supported", prep, covariance_side(side))
 
     def covariance(self, prep: PrepResult, side="tx", user_begin: int = 0, user_count: Optional[int] = None,
                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -855,23 +823,18 @@ class ChannelEngine:
         `prep` - the channel tensor is not written.  Every block is exactly Hermitian."""
         sid = covariance_side(side)
         p = prep.params_struct
-        if user_count is None:
-            user_count = prep.n_ue - user_begin
+        user_count = self._users(prep.n_ue, user_begin, user_count)
         m = p.bs_shape[0] * p.bs_shape[1] if sid == 0 else p.ue_shape[0] * p.ue_shape[1]
         out = self._out(out, (user_count, m, m))
         with torch.cuda.device(self.device):
-            rc = self.lib.dmx_channel_covariance(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
-                                                 prep.n_paths_loaded, int(user_begin), int(user_count), sid,
-                                                 C.c_void_p(out.data_ptr()), self._stream_ptr())
+            rc = self.lib.dmx_channel_covariance(*self._record_args(prep, user_begin, user_count), sid, _ptr(out),
+                                                 self._stream_ptr())
         nat.check(rc, "dmx_channel_covariance")
         return out
 
     def rate_supported(self, prep: PrepResult) -> bool:
         """dmx_rate_supported for this preparation (host-only query; `rate` raises where it says no)."""
-        rc = self.lib.dmx_rate_supported(C.byref(prep.params_struct), prep.n_paths_loaded)
-        if rc < 0:
-            nat.check(rc, "dmx_rate_supported")
-        return rc == 1
+        return self._prep_supported("dmx_rate_supported", prep)
 
     def rate(self, prep: PrepResult, snr_db, user_begin: int = 0, user_count: Optional[int] = None,
              per_subcarrier: bool = False, out=None):
@@ -881,33 +844,26 @@ class ChannelEngine:
         `per_subcarrier` the pair (rate, rate_k), rate_k float32 [user_count, K].  `out`: the tensor (or the pair of
         tensors) to write into."""
         snr = snr_linear_from_db(snr_db)
-        p = prep.params_struct
-        if user_count is None:
-            user_count = prep.n_ue - user_begin
-        out_r, out_k = (out if isinstance(out, (tuple, list)) else (out, None)) if out is not None else (None, None)
-
-        def f32(t, shape):
-            if t is None:
-                return torch.empty(shape, dtype=torch.float32, device=self.device)
-            if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-                raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
-            return t
-        r = f32(out_r, (user_count,))
-        rk = f32(out_k, (user_count, int(p.n_selected))) if per_subcarrier else None
+        user_count = self._users(prep.n_ue, user_begin, user_count)
+        out_r, out_k = out if isinstance(out, (tuple, list)) else (out, None)
+        r, = self._outs(out_r, [((user_count,), torch.float32)])
+        rk = self._outs(out_k, [((user_count, int(prep.params_struct.n_selected)), torch.float32)])[0] if per_subcarrier else None
         with torch.cuda.device(self.device):
-            rc = self.lib.dmx_channel_rate(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
-                                           prep.n_paths_loaded, int(user_begin), int(user_count), snr,
-                                           C.c_void_p(r.data_ptr()), C.c_void_p(rk.data_ptr()) if per_subcarrier else None,
+            rc = self.lib.dmx_channel_rate(*self._record_args(prep, user_begin, user_count), snr, _ptr(r), _ptr(rk),
                                            self._stream_ptr())
         nat.check(rc, "dmx_channel_rate")
         return (r, rk) if per_subcarrier else r
 
     def spectrum_supported(self, prep: PrepResult) -> bool:
         """dmx_spectrum_supported for this preparation (host-only query; `spectrum` raises where it says no)."""
-        rc = self.lib.dmx_spectrum_supported(C.byref(prep.params_struct), prep.n_paths_loaded)
-        if rc < 0:
-            nat.check(rc, "dmx_spectrum_supported")
-        return rc == 1
+        return self._prep_supported("dmx_spectrum_supported", prep)
+
+    def _wanted_outs(self, out, outputs, torch_names: bool = False):
+        """`_outs` of the wanted ones of a call's optional outputs, `outputs` = [(wanted, shape, dtype)]: (the tensors, for
+        every output its pointer argument - None where it is not wanted)."""
+        res = self._outs(out, [(shape, dt) for want, shape, dt in outputs if want], torch_names)
+        it = iter(res)
+        return res, [_ptr(next(it)) if want else None for want, _, _ in outputs]
 
     def spectrum(self, prep: PrepResult, snr_db, user_begin: int = 0, user_count: Optional[int] = None,
                  gamma: bool = True, rate: bool = False, per_subcarrier: bool = False, out=None):
@@ -921,34 +877,18 @@ class ChannelEngine:
         if not (gamma or rate or per_subcarrier):
             raise ValueError("spectrum: at least one of gamma, rate and per_subcarrier must be asked for")
         p = prep.params_struct
-        if user_count is None:
-            user_count = prep.n_ue - user_begin
+        user_count = self._users(prep.n_ue, user_begin, user_count)
         K, m = int(p.n_selected), min(p.bs_shape[0] * p.bs_shape[1], p.ue_shape[0] * p.ue_shape[1])
-        shapes = [sh for want, sh in ((gamma, (user_count, K, m)), (rate, (user_count,)), (per_subcarrier, (user_count, K))) if want]
-        given = list(out) if isinstance(out, (tuple, list)) else [out] * (out is not None)
-        if out is not None and len(given) != len(shapes):
-            raise ValueError(f"out must hold {len(shapes)} tensors, one per requested output")
-        res = []
-        for i, shape in enumerate(shapes):
-            t = given[i] if given else torch.empty(shape, dtype=torch.float32, device=self.device)
-            if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-                raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
-            res.append(t)
-        it = iter(res)
-        ptr = [C.c_void_p(next(it).data_ptr()) if want else None for want in (gamma, rate, per_subcarrier)]
+        res, ptr = self._wanted_outs(out, [(gamma, (user_count, K, m), torch.float32), (rate, (user_count,), torch.float32),
+                                           (per_subcarrier, (user_count, K), torch.float32)])
         with torch.cuda.device(self.device):
-            rc = self.lib.dmx_channel_spectrum(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
-                                               prep.n_paths_loaded, int(user_begin), int(user_count), snr,
-                                               ptr[0], ptr[1], ptr[2], self._stream_ptr())
+            rc = self.lib.dmx_channel_spectrum(*self._record_args(prep, user_begin, user_count), snr, *ptr, self._stream_ptr())
         nat.check(rc, "dmx_channel_spectrum")
         return res[0] if len(res) == 1 else tuple(res)
 
     def precoder_supported(self, prep: PrepResult, n_layers: int = 1) -> bool:
         """dmx_precoder_supported for this preparation (host-only query; `precoders` raises where it says no)."""
-        rc = self.lib.dmx_precoder_supported(C.byref(prep.params_struct), prep.n_paths_loaded, int(n_layers))
-        if rc < 0:
-            nat.check(rc, "dmx_precoder_supported")
-        return rc == 1
+        return self._prep_supported("dmx_precoder_supported", prep, n_layers)
 
     def precoders(self, prep: PrepResult, snr_db, n_layers: int = 1, user_begin: int = 0, user_count: Optional[int] = None,
                   gamma: bool = True, tx: bool = True, rx: bool = True, out=None):
@@ -963,30 +903,16 @@ class ChannelEngine:
         if not (gamma or tx or rx):
             raise ValueError("precoders: at least one of gamma, tx and rx must be asked for")
         p = prep.params_struct
-        if user_count is None:
-            user_count = prep.n_ue - user_begin
+        user_count = self._users(prep.n_ue, user_begin, user_count)
         m_tx, m_rx = p.bs_shape[0] * p.bs_shape[1], p.ue_shape[0] * p.ue_shape[1]
         K, L = int(p.n_selected), int(n_layers)
-        wanted = [(sh, dt) for want, sh, dt in ((gamma, (user_count, K, min(m_tx, m_rx)), torch.float32),
-                                                (tx, (user_count, K, L, m_tx), torch.complex64),
-                                                (rx, (user_count, K, L, m_rx), torch.complex64)) if want]
-        given = list(out) if isinstance(out, (tuple, list)) else [out] * (out is not None)
-        if out is not None and len(given) != len(wanted):
-            raise ValueError(f"out must hold {len(wanted)} tensors, one per requested output")
         if not self.precoder_supported(prep, L):                    # DMX_ERR_SHAPE, before an L < 1 reaches torch.empty
             nat.check(-2, "dmx_channel_precoders")
-        res = []
-        for i, (shape, dt) in enumerate(wanted):
-            t = given[i] if given else torch.empty(shape, dtype=dt, device=self.device)
-            if t.dtype != dt or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-                raise ValueError(f"out must be a contiguous {dt} tensor of shape {shape}")
-            res.append(t)
-        it = iter(res)
-        ptr = [C.c_void_p(next(it).data_ptr()) if want else None for want in (gamma, tx, rx)]
+        res, ptr = self._wanted_outs(out, [(gamma, (user_count, K, min(m_tx, m_rx)), torch.float32),
+                                           (tx, (user_count, K, L, m_tx), torch.complex64),
+                                           (rx, (user_count, K, L, m_rx), torch.complex64)], torch_names=True)
         with torch.cuda.device(self.device):
-            rc = self.lib.dmx_channel_precoders(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
-                                                prep.n_paths_loaded, int(user_begin), int(user_count), snr, L,
-                                                ptr[0], ptr[1], ptr[2], self._stream_ptr())
+            rc = self.lib.dmx_channel_precoders(*self._record_args(prep, user_begin, user_count), snr, L, *ptr, self._stream_ptr())
         nat.check(rc, "dmx_channel_precoders")
         return res[0] if len(res) == 1 else tuple(res)
 
@@ -1003,10 +929,7 @@ class ChannelEngine:
         """dmx_cell_rate_supported for these preparations, one per link (host-only query; `cell_rate` raises where it says
         no)."""
         preps = list(preps)
-        rc = self.lib.dmx_cell_rate_supported(self._links(preps, [1.0] * len(preps)), len(preps))
-        if rc < 0:
-            nat.check(rc, "dmx_cell_rate_supported")
-        return rc == 1
+        return self._supported("dmx_cell_rate_supported", self._links(preps, [1.0] * len(preps)), len(preps))
 
     def cell_rate(self, preps, snr_db, serving=None, user_begin: int = 0, user_count: Optional[int] = None,
                   per_subcarrier: bool = False, details: bool = False):
@@ -1027,8 +950,7 @@ class ChannelEngine:
         n_ue = preps[0].n_ue
         if any(p.n_ue != n_ue for p in preps):
             raise ValueError("cell rate: the links must cover the same users (equal n_ue)")
-        if user_count is None:
-            user_count = n_ue - user_begin
+        user_count = self._users(n_ue, user_begin, user_count)
         serv = None
         if serving is not None:
             if isinstance(serving, (int, np.integer)) and not isinstance(serving, bool):
@@ -1043,21 +965,16 @@ class ChannelEngine:
         rk = torch.empty((user_count, K), dtype=torch.float32, device=self.device) if per_subcarrier else None
         sv = torch.empty((user_count,), dtype=torch.int32, device=self.device) if details else None
         ls = torch.empty((user_count, B), dtype=torch.float32, device=self.device) if details else None
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None     # noqa: E731
         with torch.cuda.device(self.device):
-            rc = self.lib.dmx_cell_rate(self._links(preps, snrs), B, n_ue, int(user_begin), int(user_count), ptr(serv),
-                                        ptr(r), ptr(rk), ptr(sv), ptr(ls), self._stream_ptr())
+            rc = self.lib.dmx_cell_rate(self._links(preps, snrs), B, n_ue, int(user_begin), int(user_count), _ptr(serv),
+                                        _ptr(r), _ptr(rk), _ptr(sv), _ptr(ls), self._stream_ptr())
         nat.check(rc, "dmx_cell_rate")
         res = (r,) + ((rk,) if per_subcarrier else ()) + ((sv, ls) if details else ())
         return res[0] if len(res) == 1 else res
 
     def angle_delay_supported(self, prep: PrepResult, n_rows: int, n_fft: int, n_taps: int) -> bool:
         """dmx_angle_delay_supported for this preparation (host-only query; `angle_delay` raises where it says no)."""
-        rc = self.lib.dmx_angle_delay_supported(C.byref(prep.params_struct), prep.n_paths_loaded, int(n_rows), int(n_fft),
-                                                int(n_taps))
-        if rc < 0:
-            nat.check(rc, "dmx_angle_delay_supported")
-        return rc == 1
+        return self._prep_supported("dmx_angle_delay_supported", prep, n_rows, n_fft, n_taps)
 
     def angle_delay(self, prep: PrepResult, n_taps: int, n_fft: Optional[int] = None, tx_codebook=None, user_begin: int = 0,
                     user_count: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1067,8 +984,7 @@ class ChannelEngine:
         delay-domain channel of every antenna pair).  n_fft: None = the number of selected subcarriers.  The selection has
         to be uniformly spaced."""
         p = prep.params_struct
-        if user_count is None:
-            user_count = prep.n_ue - user_begin
+        user_count = self._users(prep.n_ue, user_begin, user_count)
         m_rx, m_tx = p.ue_shape[0] * p.ue_shape[1], p.bs_shape[0] * p.bs_shape[1]
         cb = None if tx_codebook is None else self._codebook(tx_codebook, m_tx, min_beams=1)
         rows = m_tx if cb is None else int(cb.shape[0])
@@ -1079,11 +995,8 @@ class ChannelEngine:
             if cb is not None and user_count > 0:
                 nbytes = int(self.lib.dmx_beam_workspace_bytes(C.byref(p), user_count, prep.n_paths_loaded, rows))
                 bws = self._scratch(nbytes)
-            rc = self.lib.dmx_channels_angle_delay(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
-                                                   prep.n_paths_loaded, int(user_begin), int(user_count),
-                                                   None if cb is None else C.c_void_p(cb.data_ptr()), rows,
-                                                   None if bws is None else C.c_void_p(bws.data_ptr()), nbytes, n_fft,
-                                                   int(n_taps), C.c_void_p(out.data_ptr()), self._stream_ptr())
+            rc = self.lib.dmx_channels_angle_delay(*self._record_args(prep, user_begin, user_count), _ptr(cb), rows, _ptr(bws),
+                                                   nbytes, n_fft, int(n_taps), _ptr(out), self._stream_ptr())
         nat.check(rc, "dmx_channels_angle_delay")
         return out
 
@@ -1093,12 +1006,11 @@ class ChannelEngine:
         """(complex64 [C, L, M_tx] on the device, C, L) of the `codebook` argument of the codebook-rate calls"""
         p = prep.params_struct
         m_tx = p.bs_shape[0] * p.bs_shape[1]
-        cb = codebook if isinstance(codebook, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(codebook))
+        cb = self._to_dev(codebook, torch.complex64)
         if cb.dim() == 2:
             cb = cb[:, None, :]
         if cb.dim() != 3 or cb.shape[2] != m_tx or cb.shape[0] < 1 or cb.shape[1] < 1:
             raise ValueError(f"codebook must be [C, L, {m_tx}] or [C, {m_tx}], got {tuple(cb.shape)}")
-        cb = cb.to(device=self.device, dtype=torch.complex64).contiguous()
         return cb, int(cb.shape[0]), int(cb.shape[1])
 
     def _codebook_user_blocks(self, prep: PrepResult, user_count: int, n_rows: int):
@@ -1114,11 +1026,7 @@ class ChannelEngine:
 
     def codebook_rate_supported(self, prep: PrepResult, n_codewords: int, n_layers: int = 1) -> bool:
         """dmx_codebook_rate_supported for this preparation (host-only query; `codebook_rate` raises where it says no)."""
-        rc = self.lib.dmx_codebook_rate_supported(C.byref(prep.params_struct), prep.n_paths_loaded, int(n_codewords),
-                                                  int(n_layers))
-        if rc < 0:
-            nat.check(rc, "dmx_codebook_rate_supported")
-        return rc == 1
+        return self._prep_supported("dmx_codebook_rate_supported", prep, n_codewords, n_layers)
 
     def codebook_rate(self, prep: PrepResult, codebook, snr_db, per_codeword: bool = False, user_begin: int = 0,
                       user_count: Optional[int] = None):
@@ -1131,9 +1039,7 @@ class ChannelEngine:
         `per_codeword` also rate_c float32 [user_count, C], all in HBM.  Users go in blocks whose beam workspace stays within
         CODEBOOK_WS_BYTES; a block equals the same rows of one launch bit for bit."""
         snr = snr_linear_from_db(snr_db)
-        p = prep.params_struct
-        if user_count is None:
-            user_count = prep.n_ue - user_begin
+        user_count = self._users(prep.n_ue, user_begin, user_count)
         cb, n_cw, n_layers = self._codebook_on_device(prep, codebook)
         if not self.codebook_rate_supported(prep, n_cw, n_layers):   # DMX_ERR_SHAPE, before anything is allocated
             nat.check(-2, "dmx_codebook_rate")
@@ -1142,22 +1048,15 @@ class ChannelEngine:
         rate_c = torch.empty((user_count, n_cw), dtype=torch.float32, device=self.device) if per_codeword else None
         with torch.cuda.device(self.device):
             for b, cnt, bws, nbytes in self._codebook_user_blocks(prep, user_count, n_cw * n_layers):
-                rc = self.lib.dmx_codebook_rate(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
-                                                prep.n_paths_loaded, int(user_begin) + b, cnt, C.c_void_p(cb.data_ptr()),
-                                                n_cw, n_layers, C.c_void_p(bws.data_ptr()), nbytes, snr,
-                                                C.c_void_p(rate[b:].data_ptr()), C.c_void_p(pmi[b:].data_ptr()),
-                                                C.c_void_p(rate_c[b:].data_ptr()) if per_codeword else None,
-                                                self._stream_ptr())
+                rc = self.lib.dmx_codebook_rate(*self._record_args(prep, int(user_begin) + b, cnt), _ptr(cb), n_cw, n_layers,
+                                                _ptr(bws), nbytes, snr, _ptr(rate[b:]), _ptr(pmi[b:]),
+                                                _ptr(rate_c[b:]) if per_codeword else None, self._stream_ptr())
                 nat.check(rc, "dmx_codebook_rate")
         return (rate, pmi, rate_c) if per_codeword else (rate, pmi)
 
     def codebook_rate_subbands_supported(self, prep: PrepResult, n_codewords: int, n_layers: int = 1, subband_size: int = 1) -> bool:
         """dmx_codebook_rate_subbands_supported for this preparation (host-only query)."""
-        rc = self.lib.dmx_codebook_rate_subbands_supported(C.byref(prep.params_struct), prep.n_paths_loaded, int(n_codewords),
-                                                           int(n_layers), int(subband_size))
-        if rc < 0:
-            nat.check(rc, "dmx_codebook_rate_subbands_supported")
-        return rc == 1
+        return self._prep_supported("dmx_codebook_rate_subbands_supported", prep, n_codewords, n_layers, subband_size)
 
     def codebook_rate_subbands(self, prep: PrepResult, codebook, snr_db, subband_size, per_codeword: bool = False,
                                user_begin: int = 0, user_count: Optional[int] = None):
@@ -1170,11 +1069,9 @@ class ChannelEngine:
         outputs add the subbands in order (another summation order than `codebook_rate`).  User blocks as `codebook_rate`."""
         snr = snr_linear_from_db(snr_db)
         B = check_subband_size(subband_size)
-        p = prep.params_struct
-        K = int(p.n_selected)
+        K = int(prep.params_struct.n_selected)
         B = max(1, K) if B is None else min(B, max(1, K))
-        if user_count is None:
-            user_count = prep.n_ue - user_begin
+        user_count = self._users(prep.n_ue, user_begin, user_count)
         cb, n_cw, n_layers = self._codebook_on_device(prep, codebook)
         if not self.codebook_rate_subbands_supported(prep, n_cw, n_layers, B):   # DMX_ERR_SHAPE, before anything is allocated
             nat.check(-2, "dmx_codebook_rate_subbands")
@@ -1184,14 +1081,13 @@ class ChannelEngine:
         rate_sb, pmi_sb = new((user_count, n_sb), torch.float32), new((user_count, n_sb), torch.int32)
         rate_c = new((user_count, n_cw), torch.float32) if per_codeword else None
         rate_sb_c = new((user_count, n_sb, n_cw), torch.float32) if per_codeword else None
-        ptr = lambda t, b: C.c_void_p(t[b:].data_ptr()) if t is not None else None   # noqa: E731
+        ptr = lambda t, b: None if t is None else _ptr(t[b:])   # noqa: E731
         with torch.cuda.device(self.device):
             for b, cnt, bws, nbytes in self._codebook_user_blocks(prep, user_count, n_cw * n_layers):
-                rc = self.lib.dmx_codebook_rate_subbands(C.byref(p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue,
-                                                         prep.n_paths_loaded, int(user_begin) + b, cnt, C.c_void_p(cb.data_ptr()),
-                                                         n_cw, n_layers, C.c_void_p(bws.data_ptr()), nbytes, snr, B,
-                                                         ptr(rate_sb, b), ptr(pmi_sb, b), ptr(rate_sb_c, b), ptr(rate, b),
-                                                         ptr(pmi, b), ptr(rate_c, b), self._stream_ptr())
+                rc = self.lib.dmx_codebook_rate_subbands(*self._record_args(prep, int(user_begin) + b, cnt), _ptr(cb), n_cw, n_layers,
+                                                         _ptr(bws), nbytes, snr, B, ptr(rate_sb, b), ptr(pmi_sb, b),
+                                                         ptr(rate_sb_c, b), ptr(rate, b), ptr(pmi, b), ptr(rate_c, b),
+                                                         self._stream_ptr())
                 nat.check(rc, "dmx_codebook_rate_subbands")
         res = (rate, pmi, rate_sb, pmi_sb)
         return res + (rate_c, rate_sb_c) if per_codeword else res
