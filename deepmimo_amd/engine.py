@@ -558,9 +558,21 @@ class ChannelEngine:
         q.sc_first, q.sc_stride = 0, 0
         return self.lib.dmx_fd_kernel_choice(C.byref(q), n_paths_loaded) == 9
 
+    def reprepare(self, prep: PrepResult) -> PrepResult:
+        """Re-issue stage 1 of an existing preparation on the current stream, reading whatever the ray tensors hold
+        NOW: the delay maximum is zeroed and dmx_path_prep writes the same workspace and side tensors again.  No
+        allocation, no host-device copy, no synchronisation, so a HIP graph can capture it in front of any consumer of
+        the records ("new rays -> records -> rate"; tests/test_gpu_graph_capture.py)."""
+        with torch.cuda.device(self.device):
+            prep.side["max_delay_key"].zero_()
+            nat.check(self.lib.dmx_path_prep(C.byref(prep.rays_struct), C.byref(prep.params_struct),
+                                             C.c_void_p(prep.workspace.data_ptr()), prep.workspace_bytes,
+                                             C.byref(prep.side_struct), self._stream_ptr()), "dmx_path_prep")
+        return prep
+
     def relaunch(self, prep: PrepResult, out: torch.Tensor, variant: int = 0) -> torch.Tensor:
-        """Re-issue stage 1 + stage 2 of an existing preparation on the current stream, reading whatever the
-        ray tensors hold NOW.  No allocation, no host-device copy, no synchronisation: the two C-ABI calls only
+        """Re-issue stage 1 (`reprepare`) + stage 2 of an existing preparation on the current stream, reading whatever
+        the ray tensors hold NOW.  No allocation, no host-device copy, no synchronisation: the two C-ABI calls only
         enqueue kernels, so this is what a HIP graph captures (tests/test_gpu_parity.py::test_hip_graph_replay)
         and what a serving loop calls per batch.  Frequency domain without rx_filter, or time domain."""
         p = prep.params_struct
@@ -570,11 +582,9 @@ class ChannelEngine:
         if p.freq_domain:
             variant = self.fd_variant(prep, variant)
         wsp = C.c_void_p(prep.workspace.data_ptr())
+        self.reprepare(prep)
         stream = self._stream_ptr()
         with torch.cuda.device(self.device):
-            prep.side["max_delay_key"].zero_()
-            nat.check(self.lib.dmx_path_prep(C.byref(prep.rays_struct), C.byref(p), wsp, prep.workspace_bytes,
-                                             C.byref(prep.side_struct), stream), "dmx_path_prep")
             if out.numel():
                 if p.freq_domain:
                     rc = self.lib.dmx_channels_fd(C.byref(p), wsp, prep.n_ue, prep.n_paths_loaded, 0, prep.n_ue,

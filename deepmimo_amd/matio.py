@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import mmap
+import threading
 import zlib
 from typing import Optional, Tuple
 
@@ -41,6 +42,8 @@ def find_array(buf, name: Optional[str]) -> Tuple[nat.DmxMatInfo, object]:
 
 
 _PINNED = {"buf": None}          # host staging buffer, page-locked once and reused by every load of the process
+_PINNED_LOCK = threading.Lock()  # one load at a time owns it, from `_staging` until its stream has drained: dmx_mats_to_device runs
+                                 # with the GIL released, so a second loading thread would `pread` into the same bytes
 
 
 def _staging(nbytes: int) -> torch.Tensor:
@@ -132,30 +135,31 @@ def _load_group(items, device, rx_idxs=None, max_paths: Optional[int] = None) ->
             return {m["key"]: torch.empty((0, m["cols"] if max_paths is None else min(int(max_paths), m["cols"])),
                                           dtype=torch.float32, device=dev) for m in metas}
         d_idx, n_idx = torch.from_numpy(idx).to(dev), int(idx.size)
-    stage = _staging(total)
-    stage_np = stage.numpy()
-    jobs = (nat.DmxMatJob * len(metas))()
-    out, keepalive = {}, []
-    stream = torch.cuda.current_stream(dev)
-    with torch.cuda.device(dev):
-        for j, m in zip(jobs, metas):
-            keep = m["cols"] if max_paths is None else min(int(max_paths), m["cols"])
-            n_sel = m["rows"] if d_idx is None else n_idx
-            d_payload = torch.empty(m["nbytes"], dtype=torch.uint8, device=dev)
-            o = torch.empty((n_sel, keep), dtype=torch.float32, device=dev)
-            if m["inflated"] is not None:                       # not in the file as stored: staged here, path = NULL
-                stage_np[m["stage"]: m["stage"] + m["nbytes"]] = np.frombuffer(m["inflated"], dtype=np.uint8, count=m["nbytes"],
-                                                                              offset=m["off"])
-            j.path = None if m["inflated"] is not None else os.fsencode(m["path"])
-            j.file_offset, j.nbytes, j.stage_offset = m["off"], m["nbytes"], m["stage"]
-            j.d_payload, j.d_out = d_payload.data_ptr(), o.data_ptr()
-            j.data_type, j.cols_keep, j.rows, j.cols = int(m["info"].data_type), keep, m["rows"], m["cols"]
-            keepalive.append(d_payload)
-            out[m["key"]] = o
-        rc = lib.dmx_mats_to_device(jobs, len(metas), C.c_void_p(stage.data_ptr()),
-                                    None if d_idx is None else C.c_void_p(d_idx.data_ptr()), 0 if d_idx is None else n_idx,
-                                    max(1, min(8, os.cpu_count() or 1)), C.c_void_p(stream.cuda_stream))
-        stream.synchronize()                                    # staging buffer, d_payload, d_idx are free again
+    with _PINNED_LOCK:
+        stage = _staging(total)
+        stage_np = stage.numpy()
+        jobs = (nat.DmxMatJob * len(metas))()
+        out, keepalive = {}, []
+        stream = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            for j, m in zip(jobs, metas):
+                keep = m["cols"] if max_paths is None else min(int(max_paths), m["cols"])
+                n_sel = m["rows"] if d_idx is None else n_idx
+                d_payload = torch.empty(m["nbytes"], dtype=torch.uint8, device=dev)
+                o = torch.empty((n_sel, keep), dtype=torch.float32, device=dev)
+                if m["inflated"] is not None:                       # not in the file as stored: staged here, path = NULL
+                    stage_np[m["stage"]: m["stage"] + m["nbytes"]] = np.frombuffer(m["inflated"], dtype=np.uint8, count=m["nbytes"],
+                                                                                  offset=m["off"])
+                j.path = None if m["inflated"] is not None else os.fsencode(m["path"])
+                j.file_offset, j.nbytes, j.stage_offset = m["off"], m["nbytes"], m["stage"]
+                j.d_payload, j.d_out = d_payload.data_ptr(), o.data_ptr()
+                j.data_type, j.cols_keep, j.rows, j.cols = int(m["info"].data_type), keep, m["rows"], m["cols"]
+                keepalive.append(d_payload)
+                out[m["key"]] = o
+            rc = lib.dmx_mats_to_device(jobs, len(metas), C.c_void_p(stage.data_ptr()),
+                                        None if d_idx is None else C.c_void_p(d_idx.data_ptr()), 0 if d_idx is None else n_idx,
+                                        max(1, min(8, os.cpu_count() or 1)), C.c_void_p(stream.cuda_stream))
+            stream.synchronize()                                    # staging buffer, d_payload, d_idx are free again
     nat.check(rc, "dmx_mats_to_device")
     return out
 

@@ -1,0 +1,458 @@
+"""One table of entry-point cases: every C-ABI function that takes a stream (include/deepmimo_amd.h) and every `__global__`
+kernel of deepmimo_amd/csrc/, each driven through ChannelEngine at the smallest shape that selects it.
+
+tests/test_entry_calls_cpu.py checks the table against the header, the kernel files and the host-only launch rules;
+tests/test_gpu_stream_order.py runs every case on a side stream behind a device-side delay, tests/test_gpu_graph_capture.py
+captures every capturable case in a HIP graph and replays it on new rays.  A plain module: NumPy only at module level, torch
+and the package are imported inside the functions that need them (as tests/_persistent_routes.py).
+
+A case is
+  id          its name
+  abi         the dmx_* function its call drives
+  kernels     every `__global__` kernel the sequence "reprepare every preparation, then the call" launches
+  build       () -> dict: the parameters of every preparation, the ray shapes (users, loaded paths), `state` and `call` (below), and the
+              `route` tag by which tests/test_entry_calls_cpu.py derives the kernels from the host-only rules
+  rule        the host rule the kernel claim is checked against, or the test that documents the route where there is none
+  capturable  False only for dmx_mats_to_device, which reads files at call time
+
+  state(eng, rays, preps) -> dict   device constants (codebooks as complex64 device tensors, call structs) and the output
+                                    tensors of the methods that take `out=`; runs once, outside stream scope and capture
+  call(eng, rays, preps, outs) -> tuple of tensors   the entry call on the current stream.  Nothing in it copies from the host.
+                                    Methods without `out=` (beam_power, cell_rate, codebook_rate*, pathloss) allocate their
+                                    results: the caller keeps the returned tensors.
+
+Sizes: 61 users (no multiple of 2, 4 or 8 waves per workgroup; user 3 has no path), 10 loaded paths (40 where more than 32
+kept paths are the point), and as many subcarriers as the route needs.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Callable, Tuple
+
+import numpy as np
+
+N_UE = 61
+NONE_USER = 3
+L = 10
+L_EXTRA = 40
+BANDWIDTH = 10e6
+SNR_DB = 100.0                      # ray powers are -140 .. -60 dBW
+SEED_A, SEED_B = 4101, 4202
+
+RAY_KEYS = ("power", "phase", "delay", "aoa_az", "aoa_el", "aod_az", "aod_el", "inter")
+
+
+@dataclass(frozen=True)
+class Case:
+    id: str
+    abi: str
+    kernels: Tuple[str, ...]
+    build: Callable[[], dict]
+    rule: str
+    capturable: bool = True
+    reason: str = ""
+
+
+# ---- inputs -------------------------------------------------------------------------------------------------------------
+def fd_case(bs, ue, sel, loaded=L, N=512, rx_filter=0, freq_domain=1, num_paths=None, bs_rot=(0, 10, 45)):
+    """case description in the form tests/_cases.py `oracle_params` and `dm_params` below take"""
+    return dict(bs_shape=list(bs), ue_shape=list(ue), bs_spacing=0.5, ue_spacing=0.5, bs_rot=list(bs_rot), bs_pattern="isotropic",
+                ue_pattern="isotropic", num_paths=loaded if num_paths is None else num_paths, L=loaded, freq_domain=freq_domain,
+                subcarriers=N, selected=[int(s) for s in sel], bandwidth=BANDWIDTH, rx_filter=rx_filter, bs_fov=None, ue_fov=None)
+
+
+def dm_params(cd, n=N_UE):
+    """validated ChannelGenParameters of a case description"""
+    import deepmimo_amd as dm
+    p = dm.ChannelGenParameters()
+    p.bs_antenna.shape, p.ue_antenna.shape = np.array(cd["bs_shape"]), np.array(cd["ue_shape"])
+    p.bs_antenna.spacing, p.ue_antenna.spacing = cd["bs_spacing"], cd["ue_spacing"]
+    p.bs_antenna.rotation, p.ue_antenna.rotation = np.array(cd["bs_rot"]), np.zeros(3)
+    p.bs_antenna.radiation_pattern, p.ue_antenna.radiation_pattern = cd["bs_pattern"], cd["ue_pattern"]
+    p.num_paths = cd["num_paths"]
+    p.freq_domain = cd["freq_domain"]
+    p.ofdm.subcarriers = cd["subcarriers"]
+    p.ofdm.selected_subcarriers = np.array(cd["selected"])
+    p.ofdm.bandwidth = cd["bandwidth"]
+    p.ofdm.rx_filter = cd["rx_filter"]
+    return p.validate(n)
+
+
+_RAYS = {}
+
+
+def case_rays(built, which):
+    """the rays `which` ("a" | "b") of a built case: oracle_np.synth_rays with user NONE_USER emptied (shared, read-only).
+    Delays stay below 0.9 N samples, so that an rx_filter case keeps its paths."""
+    from oracle import oracle_np as onp
+    n, loaded = built["n"], built["L"]
+    max_delay = min(2e-6, 0.9 * built["preps"][0]["case"]["subcarriers"] / BANDWIDTH) if built["preps"] else 2e-6
+    key = (n, loaded, which, max_delay)
+    if key not in _RAYS:
+        r = onp.synth_rays(n, loaded, seed=(SEED_A if which == "a" else SEED_B) + loaded, max_delay=max_delay)
+        r = {k: r[k] for k in RAY_KEYS}
+        for v in r.values():
+            v[NONE_USER, :] = np.nan
+            v.setflags(write=False)
+        _RAYS[key] = r
+    return _RAYS[key]
+
+
+def upload(eng, built, which):
+    """rays `which` of a built case as resident tensors of their own"""
+    return eng.upload_rays({k: v.copy() for k, v in case_rays(built, which).items()})
+
+
+def valid_counts(rays):
+    return np.isfinite(rays["power"]).sum(axis=1)
+
+
+def steering_codebook(bs, nb):
+    """[nb, M_tx] complex64 steering vectors over -60 .. 60 degrees of azimuth (the codebook of tests/_beam_cases.py)"""
+    from oracle import oracle_np as onp
+    m = bs[0] * bs[1]
+    return np.array([onp.steering_vec(bs, phi=a).ravel() for a in np.around(np.linspace(-60, 60, nb), 2)]).reshape(nb, m).astype(np.complex64)
+
+
+def layered_codebook(bs, n_codewords, n_layers, seed=7):
+    """[C, L, M_tx] complex64 with rows of unit norm"""
+    rng = np.random.default_rng(seed)
+    m = bs[0] * bs[1]
+    w = rng.normal(size=(n_codewords, n_layers, m)) + 1j * rng.normal(size=(n_codewords, n_layers, m))
+    return (w / np.linalg.norm(w, axis=-1, keepdims=True)).astype(np.complex64)
+
+
+# ---- builders -------------------------------------------------------------------------------------------------------------
+def _built(preps, state, call, route, n=N_UE, loaded=L, kind="rays"):
+    return dict(n=n, L=loaded, preps=preps, state=state, call=call, route=route, kind=kind)
+
+
+def _prep(cd, want_side="light"):
+    return dict(case=cd, want_side=want_side)
+
+
+def _dev(eng, a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(eng.device)
+
+
+def _empty(eng, shape, dtype="complex64"):
+    import torch
+    return torch.empty(shape, dtype=getattr(torch, dtype), device=eng.device)
+
+
+def _stage1(want_side="light", loaded=L):
+    """dmx_path_prep alone: the call is a reader of the records (the fp32 vector kernel), the side products are compared by
+    the harness for every case"""
+    cd = fd_case([2, 1], [1, 1], range(8), loaded=loaded)
+    return lambda: _built([_prep(cd, want_side)],
+                          lambda eng, rays, preps: dict(out=_empty(eng, eng.channel_shape(preps[0]))),
+                          lambda eng, rays, preps, outs: (eng.channels(preps[0], out=outs["out"], variant=1),),
+                          ("fd", 1, False), loaded=loaded)
+
+
+def _fd(bs, ue, sel, variant, auto=None, loaded=L, N=512):
+    """dmx_channels_fd; auto: what dmx_fd_kernel_choice must answer where variant = 0"""
+    cd = fd_case(bs, ue, sel, loaded=loaded, N=N)
+    return lambda: _built([_prep(cd)],
+                          lambda eng, rays, preps: dict(out=_empty(eng, eng.channel_shape(preps[0]))),
+                          lambda eng, rays, preps, outs: (eng.channels(preps[0], out=outs["out"], variant=variant),),
+                          ("fd", variant if auto is None else auto, auto is not None), loaded=loaded)
+
+
+def _direct(bs, ue, sel):
+    cd = fd_case(bs, ue, sel)
+
+    def state(eng, rays, preps):
+        s = eng._call_structs(rays, dm_params(cd))
+        return dict(structs=s, params=dm_params(cd), out=_empty(eng, (N_UE, ue[0] * ue[1], bs[0] * bs[1], len(cd["selected"]))))
+
+    def call(eng, rays, preps, outs):
+        out, side = eng.channels_direct(rays, outs["params"], out=outs["out"], structs=outs["structs"])
+        return (out,) + tuple(side[k] for k in ("num_paths", "los", "max_delay_key"))
+
+    return lambda: _built([], state, call, ("direct", cd))
+
+
+def _lpf(bs, ue, N, sel, loaded=L):
+    cd = fd_case(bs, ue, sel, loaded=loaded, N=N, rx_filter=1)
+    return lambda: _built([_prep(cd)],
+                          lambda eng, rays, preps: dict(out=_empty(eng, eng.channel_shape(preps[0]))),
+                          lambda eng, rays, preps, outs: (eng.channels(preps[0], out=outs["out"]),),
+                          ("lpf",), loaded=loaded)
+
+
+def _beams(bs, ue, nb, sel):
+    cd = fd_case(bs, ue, sel, bs_rot=(0, 0, 0))
+
+    def state(eng, rays, preps):
+        shape = eng.channel_shape(preps[0])
+        return dict(cb=_dev(eng, steering_codebook(bs, nb)), out=_empty(eng, (shape[0], shape[1], nb, shape[3])))
+
+    return lambda: _built([_prep(cd)], state,
+                          lambda eng, rays, preps, outs: (eng.channels(preps[0], out=outs["out"], tx_codebook=outs["cb"]),),
+                          ("beams", nb))
+
+
+def _beam_power(bs, ue, nb, sel):
+    cd = fd_case(bs, ue, sel, bs_rot=(0, 0, 0))
+    return lambda: _built([_prep(cd)],
+                          lambda eng, rays, preps: dict(cb=_dev(eng, steering_codebook(bs, nb))),
+                          lambda eng, rays, preps, outs: tuple(eng.beam_power(preps[0], outs["cb"])),
+                          ("beam_power", nb))
+
+
+def _td(bs, ue):
+    cd = fd_case(bs, ue, [0], freq_domain=0, N=64)
+    return lambda: _built([_prep(cd)],
+                          lambda eng, rays, preps: dict(out=_empty(eng, eng.channel_shape(preps[0]))),
+                          lambda eng, rays, preps, outs: (eng.channels(preps[0], out=outs["out"]),),
+                          ("td",))
+
+
+CONSUMER_BS, CONSUMER_UE, CONSUMER_SEL = [4, 2], [2, 1], range(0, 24, 2)           # 8 x 2 antennas, 12 subcarriers
+
+
+def _consumer(name, state, call, route_args=(), bs=CONSUMER_BS, ue=CONSUMER_UE, sel=CONSUMER_SEL):
+    cd = fd_case(bs, ue, sel)
+    return lambda: _built([_prep(cd)], state, call, ("consumer", name) + tuple(route_args))
+
+
+def _covariance(side):
+    m = {"tx": 8, "rx": 2}[side]
+    return _consumer("covariance", lambda eng, rays, preps: dict(out=_empty(eng, (N_UE, m, m))),
+                     lambda eng, rays, preps, outs: (eng.covariance(preps[0], side=side, out=outs["out"]),), (side,))
+
+
+def _rate():
+    K = len(CONSUMER_SEL)
+    return _consumer("rate", lambda eng, rays, preps: dict(out=(_empty(eng, (N_UE,), "float32"), _empty(eng, (N_UE, K), "float32"))),
+                     lambda eng, rays, preps, outs: tuple(eng.rate(preps[0], SNR_DB, per_subcarrier=True, out=outs["out"])))
+
+
+def _spectrum():
+    K, m = len(CONSUMER_SEL), 2
+    return _consumer("spectrum", lambda eng, rays, preps: dict(out=(_empty(eng, (N_UE, K, m), "float32"), _empty(eng, (N_UE,), "float32"),
+                                                                    _empty(eng, (N_UE, K), "float32"))),
+                     lambda eng, rays, preps, outs: tuple(eng.spectrum(preps[0], SNR_DB, rate=True, per_subcarrier=True, out=outs["out"])))
+
+
+def _precoders(n_layers=2):
+    K, m = len(CONSUMER_SEL), 2
+    return _consumer("precoders", lambda eng, rays, preps: dict(out=(_empty(eng, (N_UE, K, m), "float32"), _empty(eng, (N_UE, K, n_layers, 8)),
+                                                                     _empty(eng, (N_UE, K, n_layers, 2)))),
+                     lambda eng, rays, preps, outs: tuple(eng.precoders(preps[0], SNR_DB, n_layers=n_layers, out=outs["out"])), (n_layers,))
+
+
+def _cell_rate():
+    """two links: the same users seen from two base stations of different panels and rotations"""
+    links = [fd_case([4, 2], CONSUMER_UE, CONSUMER_SEL), fd_case([2, 2], CONSUMER_UE, CONSUMER_SEL, bs_rot=(0, 0, -120))]
+    return lambda: _built([_prep(cd) for cd in links], lambda eng, rays, preps: {},
+                          lambda eng, rays, preps, outs: tuple(eng.cell_rate(preps, [SNR_DB, SNR_DB - 6.0], per_subcarrier=True, details=True)),
+                          ("consumer", "cell_rate"))
+
+
+def _angle_delay(n_rows=None, n_taps=5, n_fft=16):
+    def state(eng, rays, preps):
+        rows = 8 if n_rows is None else n_rows
+        s = dict(out=_empty(eng, (N_UE, 2, rows, n_taps)))
+        if n_rows is not None:
+            s["cb"] = _dev(eng, steering_codebook(CONSUMER_BS, n_rows))
+        return s
+
+    return _consumer("angle_delay", state,
+                     lambda eng, rays, preps, outs: (eng.angle_delay(preps[0], n_taps, n_fft=n_fft, tx_codebook=outs.get("cb"), out=outs["out"]),),
+                     (n_rows, n_fft, n_taps))
+
+
+def _codebook_rate(n_codewords, n_layers, subband_size=None):
+    def call(eng, rays, preps, outs):
+        if subband_size is None:
+            return tuple(eng.codebook_rate(preps[0], outs["cb"], SNR_DB, per_codeword=True))
+        return tuple(eng.codebook_rate_subbands(preps[0], outs["cb"], SNR_DB, subband_size, per_codeword=True))
+
+    return _consumer("codebook_rate", lambda eng, rays, preps: dict(cb=_dev(eng, layered_codebook(CONSUMER_BS, n_codewords, n_layers))),
+                     call, (n_codewords, n_layers, subband_size))
+
+
+def _pathloss():
+    return lambda: _built([], lambda eng, rays, preps: {}, lambda eng, rays, preps, outs: (eng.pathloss(rays, coherent=True),), ("pathloss",))
+
+
+# ---- the loader: the resident input is a stored payload, not ray matrices -----------------------------------------------------
+MAT_ROWS, MAT_COLS, MAT_KEEP = 77, 10, 7
+MAT_KEY = "power"
+
+
+def mat_values(which):
+    """the stored float64 [MAT_ROWS, MAT_COLS] matrix `which` ("a" | "b"), with NaN padding as the converter writes it"""
+    rng = np.random.default_rng(SEED_A if which == "a" else SEED_B)
+    v = rng.uniform(-140, -60, (MAT_ROWS, MAT_COLS))
+    v[rng.uniform(size=v.shape) < 0.2] = np.nan
+    return v
+
+
+def mat_selection():
+    return np.arange(MAT_ROWS - 1, -1, -2, dtype=np.int64)                # every second receiver, last first
+
+
+def _mat_kernel():
+    """dmx_mat_to_rowmajor_f32 on a payload resident in HBM.  outs: payload (uint8), idx (int64), out (float32 [n_sel, keep])"""
+    def call(eng, rays, preps, outs):
+        import ctypes as C
+        from deepmimo_amd import _native as nat
+        from tests._mat5_cases import MI_DOUBLE
+        rc = eng.lib.dmx_mat_to_rowmajor_f32(C.c_void_p(outs["payload"].data_ptr()), MI_DOUBLE, MAT_ROWS, MAT_COLS,
+                                             C.c_void_p(outs["idx"].data_ptr()), int(outs["idx"].numel()), MAT_KEEP,
+                                             C.c_void_p(outs["out"].data_ptr()), eng._stream_ptr())
+        nat.check(rc, "dmx_mat_to_rowmajor_f32")
+        return (outs["out"],)
+
+    return lambda: _built([], None, call, ("loader",), n=MAT_ROWS, loaded=MAT_COLS, kind="loader")
+
+
+def _mat_pipeline():
+    """dmx_mats_to_device through matio.load_matrix_to_device.  outs: path (the file to load)"""
+    def call(eng, rays, preps, outs):
+        from deepmimo_amd import matio
+        return (matio.load_matrix_to_device(outs["path"], MAT_KEY, eng.device, rx_idxs=mat_selection(), max_paths=MAT_KEEP),)
+
+    return lambda: _built([], None, call, ("loader",), n=MAT_ROWS, loaded=MAT_COLS, kind="loader")
+
+
+# ---- the table --------------------------------------------------------------------------------------------------------------
+K1, K1F = "k1_path_prep", "k1_path_prep_full"
+MFMA_ARRAYS, VALU_ARRAYS = ([8, 4], [2, 2]), ([2, 1], [1, 1])             # tests/_lpf_routes.py ARRAYS
+R_STAGE1 = "stage1_form (k1_path_math.h), restated in tests/test_entry_calls_cpu.py"
+R_CHOICE = "dmx_fd_kernel_choice"
+R_VARIANT = "explicit variant (include/deepmimo_amd.h, dmx_channels_fd)"
+R_LPF = "tests/_lpf_routes.py lpf_route and mfma_preferred"
+R_BEAM = "tests/_beam_cases.py projection_route"
+R_TD = "tests/_td_cases.py td_form"
+
+CASES = (
+    # stage 1: the full form (rotated angles and powers asked for), the lean form, and one user per wave beyond 32 loaded paths
+    Case("prep_full", "dmx_path_prep", (K1F, "k2_fd_valu"), _stage1(True), R_STAGE1),
+    Case("prep_lean", "dmx_path_prep", (K1, "k2_fd_valu"), _stage1("light"), R_STAGE1),
+    Case("prep_lean_40", "dmx_path_prep", (K1, "k2_fd_valu"), _stage1("light", L_EXTRA), R_STAGE1),
+    # stage 2, frequency domain: every kernel variant 0 chooses from, and the forms of the folded one
+    Case("fd_valu", "dmx_channels_fd", (K1, "k2_fd_valu"), _fd([2, 1], [1, 1], list(range(19)) + [25], 0, auto=1, N=64), R_CHOICE),
+    Case("fd_mfma", "dmx_channels_fd", (K1, "k2_fd_mfma"), _fd([8, 8], [2, 2], range(16), 0, auto=2), R_CHOICE),
+    Case("fd_fold_wave", "dmx_channels_fd", (K1, "k2_fd_fold"), _fd([8, 1], [1, 1], range(16), 0, auto=12), R_CHOICE),
+    Case("fd_fold_shared", "dmx_channels_fd", (K1, "k2_fd_fold"), _fd([8, 4], [2, 1], range(0, 32, 2), 0, auto=12), R_CHOICE),
+    Case("fd_small", "dmx_channels_fd", (K1, "k2_fd_small"), _fd([8, 1], [1, 1], [0], 0, auto=9), R_CHOICE),
+    Case("fd_small_forced", "dmx_channels_fd", (K1, "k2_fd_small"), _fd([8, 4], [1, 1], [3, 9, 27], 9), R_VARIANT),
+    # more than 32 kept paths: launch_extra_path_passes adds them with the fp32 vector kernel
+    Case("fd_extra_mfma", "dmx_channels_fd", (K1, "k2_fd_mfma", "k2_fd_valu"), _fd([4, 4], [1, 1], range(8), 2, loaded=L_EXTRA), R_VARIANT),
+    Case("fd_extra_small", "dmx_channels_fd", (K1, "k2_fd_small", "k2_fd_valu"), _fd([8, 1], [1, 1], [0, 5], 9, loaded=L_EXTRA), R_VARIANT),
+    Case("fd_direct", "dmx_channels_fd_direct", ("k12_fd_direct",), _direct([8, 1], [1, 1], [0]), "dmx_fd_direct_supported"),
+    # rx_filter: the gains kernel of every FFT route, then the contraction (matrix cores over the packed or the float table,
+    # or the fp32 vector kernel); lpf_extra adds accumulate passes over the float table
+    Case("lpf_fft512", "dmx_channels_fd_lpf", (K1, "k3_lpf_fft512", "k2_fd_mfma"), _lpf(*MFMA_ARRAYS, 512, range(8)), R_LPF),
+    Case("lpf_pow2", "dmx_channels_fd_lpf", (K1, "k3_lpf_fft_pow2", "k2_fd_valu"), _lpf(*VALU_ARRAYS, 64, range(8)), R_LPF),
+    Case("lpf_wave", "dmx_channels_fd_lpf", (K1, "k3_lpf_fft_wave", "k2_fd_mfma"), _lpf(*MFMA_ARRAYS, 64, range(70)), R_LPF),
+    Case("lpf_wave_2048", "dmx_channels_fd_lpf", (K1, "k3_lpf_fft_wave", "k2_fd_valu"), _lpf(*VALU_ARRAYS, 2048, range(8)), R_LPF),
+    Case("lpf_wave_1024", "dmx_channels_fd_lpf", (K1, "k3_lpf_fft_wave", "k2_fd_valu"), _lpf(*VALU_ARRAYS, 1024, range(1025)), R_LPF),
+    Case("lpf_fft", "dmx_channels_fd_lpf", (K1, "k3_lpf_fft", "k2_fd_valu"), _lpf(*VALU_ARRAYS, 32, range(8)), R_LPF),
+    Case("lpf_gains", "dmx_channels_fd_lpf", (K1, "k3_lpf_gains", "k2_fd_mfma"), _lpf(*MFMA_ARRAYS, 48, range(8)), R_LPF),
+    Case("lpf_extra", "dmx_channels_fd_lpf", (K1, "k3_lpf_fft_pow2", "k2_fd_mfma", "k2_fd_valu"),
+         _lpf(*MFMA_ARRAYS, 64, range(8), loaded=L_EXTRA), R_LPF),
+    # beam space: both projection kernels, each followed by the contraction or by the fused reduction
+    Case("beams_mfma", "dmx_channels_fd_beams", (K1, "k2b_beam_project_mfma", "k2_fd_mfma"), _beams([4, 2], [2, 1], 8, range(8)), R_BEAM),
+    Case("beams_scalar", "dmx_channels_fd_beams", (K1, "k2b_beam_project", "k2_fd_mfma"), _beams([4, 2], [1, 1], 129, range(8)), R_BEAM),
+    Case("beam_power_32", "dmx_beam_power", (K1, "k2b_beam_project_mfma", "k2c_beam_power"), _beam_power([4, 2], [2, 2], 8, range(8)), R_BEAM),
+    Case("beam_power_320", "dmx_beam_power", (K1, "k2b_beam_project_mfma", "k2c_beam_power"), _beam_power([4, 2], [2, 2], 80, range(8)), R_BEAM),
+    Case("beam_power_scalar", "dmx_beam_power", (K1, "k2b_beam_project", "k2c_beam_power"), _beam_power([4, 2], [1, 1], 129, range(8)), R_BEAM),
+    # time domain with and without the steering tables in LDS
+    Case("td_tab", "dmx_channels_td", (K1, "k4_td_tab"), _td([4, 2], [2, 1]), R_TD),
+    Case("td_plain", "dmx_channels_td", (K1, "k4_td"), _td([32, 32], [1, 1]), R_TD),
+    # consumers of the records
+    Case("cov_tx", "dmx_channel_covariance", (K1, "k6_covariance"), _covariance("tx"), "dmx_covariance_supported"),
+    Case("cov_rx", "dmx_channel_covariance", (K1, "k6_covariance"), _covariance("rx"), "dmx_covariance_supported"),
+    Case("rate", "dmx_channel_rate", (K1, "k7_rate"), _rate(), "dmx_rate_supported"),
+    Case("spectrum", "dmx_channel_spectrum", (K1, "k7_rate"), _spectrum(), "dmx_spectrum_supported"),
+    Case("precoders", "dmx_channel_precoders", (K1, "k7_rate"), _precoders(), "dmx_precoder_supported"),
+    Case("cell_rate_2", "dmx_cell_rate", (K1, "k8_cell_rate"), _cell_rate(), "dmx_cell_rate_supported"),
+    Case("angle_delay", "dmx_channels_angle_delay", (K1, "k9_angle_delay"), _angle_delay(), "dmx_angle_delay_supported"),
+    Case("angle_delay_cb", "dmx_channels_angle_delay", (K1, "k2b_beam_project_mfma", "k9_angle_delay"), _angle_delay(n_rows=6),
+         "dmx_angle_delay_supported, " + R_BEAM),
+    Case("cb_rate", "dmx_codebook_rate", (K1, "k2b_beam_project_mfma", "k10_codebook_rate"), _codebook_rate(8, 2),
+         "dmx_codebook_rate_supported, " + R_BEAM),
+    Case("cb_rate_scalar", "dmx_codebook_rate", (K1, "k2b_beam_project", "k10_codebook_rate"), _codebook_rate(130, 1),
+         "dmx_codebook_rate_supported, " + R_BEAM),
+    Case("cb_rate_subbands", "dmx_codebook_rate_subbands", (K1, "k2b_beam_project_mfma", "k10_codebook_rate_sb"), _codebook_rate(8, 2, 5),
+         "dmx_codebook_rate_subbands_supported, " + R_BEAM),
+    Case("pathloss", "dmx_pathloss", ("k5_pathloss",), _pathloss(), "tests/test_gpu_pathloss.py (one kernel, no choice)"),
+    # the loader
+    Case("mat_rowmajor", "dmx_mat_to_rowmajor_f32", ("k_mat_to_rowmajor",), _mat_kernel(), "tests/test_gpu_mat_loader.py (one kernel, no choice)"),
+    Case("mats_to_device", "dmx_mats_to_device", ("k_mat_to_rowmajor",), _mat_pipeline(), "tests/test_gpu_mat_loader.py (one kernel, no choice)",
+         capturable=False, reason="reads the files at call time: reader threads pread into the staging buffer while the call runs, and "
+                                  "matio synchronises the stream before it returns"),
+)
+BY_ID = {c.id: c for c in CASES}
+RAY_CASE_IDS = [c.id for c in CASES if c.build()["kind"] == "rays"]
+CAPTURABLE_RAY_CASE_IDS = [i for i in RAY_CASE_IDS if BY_ID[i].capturable]
+
+# A launcher that passes its current request as the cap of the dynamic-LDS attribute: (the case captured in a graph, the case
+# of the same kernel instantiation with a smaller request still above 64 KiB that runs eagerly before the replay), or the
+# reason why the launcher admits no such pair.
+LDS_DEFAULT = 64 * 1024
+LDS_CAP_PAIRS = {
+    "k3_lpf_fft_wave": ("lpf_wave_2048", "lpf_wave_1024"),          # 155,712 B, then 77,888 B (tests/_lpf_routes.py wave_lds_bytes)
+    "k2c_beam_power": ("beam_power_320", "beam_power_32"),          # two row blocks 68,112 B, then one 67,088 B (tests/_beam_cases.py)
+    "k2_fd_fold": "fold_chunk_blocks keeps three workgroups per CU wherever the tables allow it: the largest request of any "
+                  "shape the launcher takes (M <= 128 pairs) is 54,592 B at M = 121, below the 64 KiB from which launch_dyn_lds "
+                  "touches the attribute at all (fold_lds_bytes below; tests/test_entry_calls_cpu.py scans every M and block count)",
+}
+
+
+# ---- launch_channels_fd_fold's LDS request, restated (k2_channel_fd_fold.hip) ------------------------------------------------
+FOLD_TROW, FOLD_MAX_M, FOLD_SHARED_FROM = 272, 128, 33
+
+
+def fold_lds_bytes(M, nblk):
+    """the tables of k2_fd_fold for M antenna pairs and nblk blocks of 16 subcarriers, before the FOLD_MIN_LDS floor"""
+    align = lambda x, a: (x + a - 1) // a * a                                # noqa: E731
+    sets = 1 if M >= FOLD_SHARED_FROM else 4
+    size = lambda c: ((M * c + 31) // 32 * 32) * 12 + align(M * 4, 16) + sets * (256 + (M + c) * FOLD_TROW)   # noqa: E731
+    for want in (4, 3, 2):
+        for ch in (32, 16, 8):
+            c = min(ch, nblk)
+            if size(c) * want <= 160 * 1024:
+                return size(c)
+    return size(min(8, nblk))
+
+
+# ---- what both GPU files do with a case -----------------------------------------------------------------------------------------
+def same_bits(got, want):
+    """torch.equal on the bits (NaN side products compare equal to themselves)"""
+    import torch
+    if got.shape != want.shape or got.dtype != want.dtype:
+        return False
+    if got.is_complex():
+        got, want = torch.view_as_real(got), torch.view_as_real(want)
+    return torch.equal(got.contiguous().view(torch.uint8), want.contiguous().view(torch.uint8))
+
+
+def prepare_all(eng, built, rays):
+    """a preparation per link of the case on the resident `rays`"""
+    return [eng.prepare(rays, dm_params(p["case"], built["n"]), want_side=p["want_side"]) for p in built["preps"]]
+
+
+def observed(result, preps):
+    """everything of a run that is compared: the call's tensors, then every side product of every preparation"""
+    return list(result) + [t for p in preps for _, t in sorted(p.side.items()) if t is not None]
+
+
+def fresh_run(eng, built, which):
+    """upload, prepare and call on the current stream with tensors of its own; clones of everything `observed`"""
+    rays = upload(eng, built, which)
+    preps = prepare_all(eng, built, rays)
+    outs = built["state"](eng, rays, preps)
+    return [t.clone() for t in observed(built["call"](eng, rays, preps, outs), preps)]
+
+
+def copy_rays(rays, src):
+    """the new batch into the SAME resident tensors"""
+    for k, t in rays.fields.items():
+        t.copy_(src.fields[k])
