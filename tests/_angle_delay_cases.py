@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from tests import _consumer_shapes as shapes
 from tests._angle_delay_ref import adp_from_channel, adp_from_paths, dft_codebook
 from tests._cases import fov_args, oracle_params
 from tests._path_count_cases import flat
@@ -60,8 +61,14 @@ def _cases():
     cs.append(_case("ant_8x8", 13, 25, [8, 8], [2, 1], 512, range(64), 64, 32, "ant"))
     cs.append(_case("identity_4x2", 29, 25, [4, 2], [2, 1], 512, range(64), 64, 32, "identity"))
     cs.append(_case("identity_4x2_ant", 29, 25, [4, 2], [2, 1], 512, range(64), 64, 32, "ant"))
-    for ue in ([1, 1], [2, 1], [3, 1], [2, 2], [4, 2]):
+    for ue in ([1, 1], [2, 1], [3, 1], [2, 2], [4, 2]) + shapes.ANGLE_DELAY_UE:      # every M_rx the kernel is instantiated for
         cs.append(_case(f"mrx{ue[0] * ue[1]}", 19, 25, [4, 2], ue, 512, range(64), 64, 32, "dft"))
+    # antenna rows of an odd BS panel (15 rows, bs_mh = 5) under a UE whose first dimension is neither 1 nor M_rx
+    cs.append(_case(shapes.ANGLE_DELAY_ODD_TX, 13, 25, [5, 3], [3, 2], 512, range(64), 64, 32, "ant"))
+    # every kept-path count 0 .. 32 (tests/_consumer_shapes.py), on that table's selection of three subcarriers
+    ec = shapes.EVERY_COUNT
+    cs.append(_case(shapes.ANGLE_DELAY_EVERY_COUNT, ec["n"], ec["L"], ec["bs_shape"], ec["ue_shape"], 512, ec["selected"], 64, 32, "ant",
+                    num_paths=ec["num_paths"], rays="every_count"))
     # path counts
     _both(cs, "counts_and_holes", 45, 25, [4, 2], [2, 1], 512, range(64), 64, 32, rays="counts")
     # one loaded path: its delay inside the tap window (28 of 32 samples) - outside it a user keeps nothing but one sidelobe,
@@ -108,7 +115,9 @@ def on_tap_delays():
 def case_rays(c):
     from oracle import oracle_np as onp
     kind = c["rays"]
-    if kind == "counts":                                         # tests/test_gpu_rate.py `_case_rays`
+    if kind == "every_count":
+        return shapes.every_count_rays(c)
+    if kind == "counts":                                        # tests/test_gpu_rate.py `_case_rays`
         rays = onp.synth_rays(c["n"], c["L"], seed=900 + c["n"], all_valid=True, max_delay=c["max_delay"])
         keys = [k for k in rays if k not in ("rx_pos", "tx_pos")]
         rng = np.random.default_rng(4)

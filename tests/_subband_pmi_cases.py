@@ -2,6 +2,8 @@
 tests/test_subband_pmi_cpu.py (the conditions on the inputs) and tests/test_gpu_subband_pmi.py.  The shapes are the smallest at
 which each part of the subband nest of k10_codebook_rate.hip can go wrong; a plain module, no torch, no GPU."""
 
+from tests._consumer_shapes import SUBBAND_CASES as _EVERY_PAIR
+
 SUBBAND_CASES = [
     # one subband: all six outputs are dmx_codebook_rate's, bit for bit
     ("K65", 65), ("K65", 1000),
@@ -26,6 +28,8 @@ SUBBAND_CASES = [
     # stage-1 features through the records
     ("per_user_rot", 1), ("doppler", 2), ("adaptive_workspace", 5),
 ]
+# every (M_rx, layers) pair at K = 3 under subbands of 2: a full subband and a short last one
+SUBBAND_CASES += _EVERY_PAIR
 
 # compute_csi_report: the cases whose references pick at least two ranks (tests/test_subband_pmi_cpu.py holds that), ranks 1..4
 RANK_CASES = ("slices_K7", "L4_4x4")

@@ -108,6 +108,12 @@ def test_case_table_reaches_the_branches_it_names():
     assert lds_rule([4, 2], 10 ** 6, 2 ** 20, 32) == 2 and (8 + RC + TAP_CHUNK) * 32 * 8 == 26624
     assert {_rows(BY_ID[f"rows{R}"]) for R in (1, 3, 31, 32, 33, 65)} == {1, 3, RC - 1, RC, RC + 1, 2 * RC + 1}
     assert _rows(BY_ID["ant_8x8"]) == 64 and BY_ID["taps65_dft"]["n_taps"] == TAP_CHUNK + 1
+    # every M_rx the kernel is instantiated for; antenna rows of an odd panel; every kept-path count
+    assert {c["ue_shape"][0] * c["ue_shape"][1] for c in CASES} == set(range(1, 9))
+    assert [BY_ID[f"mrx{m}"]["ue_shape"] for m in (5, 6, 7)] == [[5, 1], [3, 2], [7, 1]] and rule("mrx7") == 4
+    assert _rows(BY_ID["ant_5x3"]) == 15 and BY_ID["ant_5x3"]["rows"] == "ant" and BY_ID["ant_5x3"]["ue_shape"] == [3, 2]
+    ec = BY_ID["every_count_ant"]
+    assert np.isfinite(case_inputs(ec)[0]["power"]).sum(axis=1).tolist() == [u % 33 for u in range(ec["n"])] and rule("every_count_ant") == 4
     assert uniform(BY_ID["pad_K40_d8_s3_dft"]["selected"]) == (3, 8, 40) and uniform(BY_ID["taps1_ant"]["selected"]) == (7, 1, 1)
     d = on_tap_delays()
     assert d.dtype == np.float32 and d[3, 0] > 5 > d[4, 0] and float(d[3, 0]) - 5 == 2.0 ** -21 and 5 - float(d[4, 0]) == 2.0 ** -21

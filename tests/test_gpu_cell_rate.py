@@ -16,6 +16,7 @@ import os
 import numpy as np
 import pytest
 
+from tests import _consumer_shapes as shapes
 from tests._cell_rate_ref import cell_rate_from_channels, cell_rate_tolerance, link_snr_reference, link_snrs
 
 pytestmark = pytest.mark.gpu
@@ -83,7 +84,8 @@ def _cells():
     return cs
 
 
-CASES = _cells()
+# and M_rx = 3, 5, 6, 7, links of odd and even M_tx in one launch (tests/_consumer_shapes.py)
+CASES = _cells() + shapes.CELL_CASES
 BY_ID = {c["id"]: c for c in CASES}
 _INPUTS = {}
 
@@ -135,6 +137,14 @@ def case_inputs(cell):
         snrs = link_snrs([l[2] for l in links], cell["serving_db"], cell["inr_db"])
         _INPUTS[cell["id"]] = (links, snrs)
     return _INPUTS[cell["id"]]
+
+
+def set_case_inputs(cell, links, snrs):
+    """The inputs of a cell case whose links were built elsewhere (tests/test_gpu_consumer_shapes.py: one preparation as
+    every link): per link (rays, ue_rot, H, time-domain tensor) as `case_inputs` returns them, and the per-link SNRs.
+    `check_cell` and `link_snr_refs` then hold a launch of that cell to these."""
+    assert len(links) == len(cell["links"]) == len(snrs) and all(len(l) == 4 for l in links)
+    _INPUTS[cell["id"]] = (list(links), list(snrs))
 
 
 def link_snr_refs(cell):
@@ -221,6 +231,7 @@ def test_waves_per_workgroup_of_the_listed_shapes():
     rule = lambda cid: cell_lds_rule(BY_ID[cid]["links"])                    # noqa: E731
     assert rule("wpb4_users41") == 4 and rule("wpb4_users43") == 4 and rule("wpb1_users7") == 1
     assert rule("defaults") == 4 and rule("panel") == 2 and rule("mixed_links") == 4
+    assert rule("ue5_mixed") == 4 and rule("ue6") == 4 and rule("ue7") == 4
     one = lambda c: (c["ue_shape"][0] * c["ue_shape"][1] + c["bs_shape"][0] * c["bs_shape"][1] + 3) * min(c["L"], 25) * 8  # noqa: E731
     assert max(range(3), key=lambda b: one(BY_ID["mixed_links"]["links"][b])) == 0      # the 8 x 8 link sizes the slice
 

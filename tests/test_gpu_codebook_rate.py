@@ -15,6 +15,7 @@ import os
 import numpy as np
 import pytest
 
+from tests import _consumer_shapes as shapes
 from tests._cases import golden_names, load_golden
 from tests._codebook_rate_ref import case_codebook, case_snr, codebook_rate_from_channel, codebook_rate_tolerance
 from tests._rate_ref import rate_from_channel, rate_tolerance
@@ -90,11 +91,14 @@ def _cases():
     return cs
 
 
-CASES = _cases()
+# and every (M_rx, layers) pair the kernel is instantiated for, every kept-path count (tests/_consumer_shapes.py)
+CASES = _cases() + shapes.CODEBOOK_CASES
 _INPUTS = {}
 
 
 def _case_rays(c):
+    if c["rays"] == "every_count":
+        return shapes.every_count_rays(c)
     if c["rays"] != "counts":
         return _rays(c)
     from oracle import oracle_np as onp
@@ -132,6 +136,7 @@ def test_waves_per_workgroup_of_the_listed_shapes():
                                 by[cid]["C"], by[cid]["layers"])
     assert rule("wpb4_users41") == 4 and rule("wpb4_users43") == 4 and rule("wpb2_users7") == 2
     assert rule("defaults") == 4 and rule("K512") == 4 and rule("panel_C64") == 4
+    assert rule("ml_1_1") == 4 and rule("ml_8_4") == 4 and rule("ml_3_3_C11") == 4 and rule("every_count") == 4
 
 
 def check_result(rate, pmi, rate_c, H, ref, what, again=None, alone=None):

@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+from tests import _consumer_shapes as shapes
 from tests._cases import TOL_ABS, TOL_REL, golden_names, load_golden
 from tests._covariance_ref import SIDES, cov_err, cov_from_channel
 from tests.test_covariance_cpu import RX, TX, lds_rule
@@ -71,7 +72,8 @@ def _cases():
     return cs
 
 
-CASES = _cases()
+# and odd arrays on either side, K = 33, every kept-path count (tests/_consumer_shapes.py)
+CASES = _cases() + shapes.COVARIANCE_CASES
 
 
 def test_waves_per_workgroup_of_the_listed_shapes():
@@ -81,9 +83,13 @@ def test_waves_per_workgroup_of_the_listed_shapes():
     assert rule("K512", TX) == (4, 32) and rule("K512", RX) == (4, 32)
     assert rule("wpb4_users41", TX)[0] == 4 and rule("wpb2_users13", TX)[0] == 2 and rule("wpb1_users7", TX)[0] == 1
     assert rule("panel_stride7", TX) == (1, 64) and rule("panel_stride7", RX)[0] == 2
+    assert rule("m5_ue_K33", TX) == (4, 32) and rule("m5_ue_K33", RX) == (4, 32)          # K = 33: a second chunk of one
+    assert rule("every_count", TX) == (4, 8) and rule("every_count", RX) == (4, 16) and rule("ue_5x3", RX) == (4, 16)
 
 
 def _case_rays(c):
+    if c["rays"] == "every_count":
+        return shapes.every_count_rays(c)
     if c["rays"] != "counts":
         return _rays(c)
     from oracle import oracle_np as onp

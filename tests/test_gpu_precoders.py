@@ -3,7 +3,8 @@
 Reference: the definition in complex128 from the NumPy oracle's channel tensor (tests/_precoder_ref.py, pinned against hand
 cases by tests/test_precoder_cpu.py).  The inputs are the cases of tests/test_gpu_rate.py, which hit every hazard of the
 shared kernel body (chunk edges, K < 64 slices, m = 1, 2, 4, 8, the BS array as the smaller one, per-user rotation, FoV and
-dipole, Doppler, the adaptive workspace), and the two rank-deficient ones of tests/test_gpu_spectrum.py at m = 4; one SNR per
+dipole, Doppler, the adaptive workspace; with tests/_consumer_shapes.py also m = 3, 5, 6, 7 in both orientations, an odd larger
+array and every kept-path count), and the rank-deficient ones of tests/test_gpu_spectrum.py at m = 3, 4 and 5; one SNR per
 case as there.  Every case runs at n_layers = m.  Criteria, tests/_precoder_ref.py (gamma is the kernel's own output, x_i the
 smaller-side vector, y_i the larger-side one, B = H_k^H or H_k):
     C1  |sqrt(snr) B x_i - sqrt(gamma_i) y_i|_2 <= 2 sqrt(snr) e
@@ -73,7 +74,7 @@ def check_precoders(gamma, w_tx, w_rx, H, snr, what, n_layers):
           + ", ".join(f"{k} {res[k]:.3g}" for k in CRITERIA if k in res) + f", C5 applies to {res.get('C5_share', 0.0):.3f} of the entries (without the division by |x_0|^2: {res.get('C5_unnormalised', 0.0):.3g})")
     WORST[what] = res
     assert res["borderline"] == 0, f"{what}: {res['borderline']} layers within 1e-5 of the presence floor"
-    if what == "L1_m4":
+    if what in gs.RANK_ONE:
         assert not present[..., 1:].any() and present[live][..., 0].all(), f"{what}: a rank-1 channel shows a second layer"
     for k in CRITERIA:
         assert res.get(k, 0.0) <= 1.0, f"{what}: criterion {k} missed, worst err / tol = {res[k]:.4g}"

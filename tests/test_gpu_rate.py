@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+from tests import _consumer_shapes as shapes
 from tests._cases import golden_names, load_golden
 from tests._rate_ref import median_snr, rate_from_channel, rate_tolerance
 from tests.test_rate_cpu import LDS_MAX, rate_lds_rule
@@ -75,11 +76,14 @@ def _cases():
     return cs
 
 
-CASES = _cases()
+# and Gram orders 3, 5, 6, 7 in both orientations, odd arrays, every kept-path count (tests/_consumer_shapes.py)
+CASES = _cases() + shapes.RATE_CASES + [shapes.EVERY_COUNT]
 _INPUTS = {}
 
 
 def _case_rays(c):
+    if c["rays"] == "every_count":
+        return shapes.every_count_rays(c)
     if c["rays"] != "counts":
         return _rays(c)
     from oracle import oracle_np as onp
@@ -113,6 +117,7 @@ def test_waves_per_workgroup_of_the_listed_shapes():
                                      min(by[cid]["num_paths"], by[cid]["L"]))
     assert rule("wpb4_users41") == 4 and rule("wpb4_users43") == 4 and rule("wpb1_users7") == 1
     assert rule("defaults") == 4 and rule("K512") == 4 and rule("panel") == 2
+    assert rule("m5_ue_K1") == 4 and rule("m6_ue_K70") == 2 and rule("m7_ue_5x3_K70") == 2 and rule("every_count") == 4
 
 
 def check_rate(rate, rate_k, H, snr, what, again=None):

@@ -2,7 +2,8 @@
 
 Reference: the definition in complex128 from the NumPy oracle's channel tensor (tests/_spectrum_ref.py, pinned against hand
 cases by tests/test_spectrum_cpu.py).  The inputs are the cases of tests/test_gpu_rate.py, which hit every hazard of the
-shared kernel body, and two rank-deficient ones at m = 4.  One SNR per case, from its reference alone: a tenth of
+shared kernel body (tests/_consumer_shapes.py adds Gram orders 3, 5, 6, 7 in both orientations, odd arrays and every kept-path
+count), and rank-deficient ones at m = 4 and, from that module, at m = 3 and m = 5.  One SNR per case, from its reference alone: a tenth of
 tests/_rate_ref.median_snr, the median live user at 10 dB (tests/test_spectrum_cpu.py has the share condition that picks
 it; the eigenmode criterion does not depend on the SNR, both sides scale with it).  Criteria, tests/_spectrum_ref.py:
     |gamma - ref| <= tol_g                                                 every mode
@@ -20,6 +21,7 @@ import os
 import numpy as np
 import pytest
 
+from tests import _consumer_shapes as shapes
 from tests import _spectrum_ref as sr
 from tests._rate_ref import median_snr, rate_tolerance
 
@@ -42,7 +44,8 @@ def _extra():
     return cs
 
 
-EXTRA = _extra()
+EXTRA = _extra() + shapes.RANK_CASES                 # the same at m = 3 and m = 5
+RANK_ONE = {c["id"] for c in EXTRA if c["L"] == 1}
 RANK_DEFICIENT = {c["id"] for c in EXTRA}
 CASES = g.CASES + EXTRA
 # goldens whose stored tensor breaks the share condition of the bracket (many one-path users behind a FoV or a dipole null
@@ -83,7 +86,7 @@ def check_spectrum(gamma, rate, rate_k, H, snr, what, bracket=True, equal_rate_k
     assert (eg <= tol_g[..., None]).all(), f"{what}: {(eg > tol_g[..., None]).sum()} modes out of tolerance, worst {ratio_g:.3f}"
     trace = snr * (np.abs(H.astype(np.complex128)) ** 2).sum(axis=(1, 2))
     assert (np.abs(ga.astype(np.float64).sum(axis=-1) - trace) <= np.sqrt(m) * tol_g).all(), f"{what}: the trace is off"
-    if what == "L1_m4":
+    if what in RANK_ONE:
         assert (ga[..., 1:] <= tol_g[..., None]).all(), f"{what}: a rank-1 channel shows a second mode"
     own = sr.waterfill(ga)                                                   # float64, from the kernel's own modes
     assert (np.abs(rk - own) <= sr.log_rounding(m, own)).all(), \

@@ -239,7 +239,7 @@ def test_jacobi_model_with_the_committed_sweep_table():
     the need plus one sweep; so two sweeps fewer fail, the table is not padding).  With SWEEPS[m] sweeps the norm
     criterion holds and the eigenvalues are within c_J 2^-24 |G|_F of eigvalsh, also on the repeated-eigenvalue set."""
     by = _case_grams()
-    assert {1, 2, 4, 8} <= set(by)
+    assert set(range(1, 9)) <= set(by)                                       # every order the kernel is instantiated for
     assert sr.SWEEPS[1] == 0 and sr.ROUNDINGS == 13
     needed = {}
     for m in range(1, 9):

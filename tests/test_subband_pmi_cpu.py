@@ -267,6 +267,10 @@ def test_the_case_table_names_cases_of_the_codebook_rate_tests():
     assert n_sb["K512-B4"] == 128 and n_sb["K512-B100"] == 6 and n_sb["slices_K33-B4"] == 9 and n_sb["slices_K33-B32"] == 2
     assert by["L1_C33"]["C"] > 32 and by["panel_C64"]["C"] > 32 and by["L4_C9"]["C"] * 4 > 32 and by["L3_C11"]["C"] * 3 > 30
     assert all(cid in by and by[cid]["ue_shape"][0] * by[cid]["ue_shape"][1] >= max(RANK_LAYERS) for cid in RANK_CASES)
+    # every (M_rx, layers) pair the subband kernel is instantiated for, each with a short last subband
+    pairs = {(by[cid]["ue_shape"][0] * by[cid]["ue_shape"][1], by[cid]["layers"]) for cid, _ in SUBBAND_CASES}
+    assert pairs == {(M, L) for M in range(1, 9) for L in range(1, min(M, 4) + 1)} and len(pairs) == 26
+    assert n_sb["ml_7_3-B2"] == 2 and subband_edges(3, 2) == [(0, 2), (2, 3)] and n_sb["ml_3_3_C11-B2"] == 2
 
 
 @needs_lib
