@@ -16,11 +16,11 @@ from .config import config
 from .general_utils import DotDict
 from .channel import ChannelGenParameters
 from .dataset import Dataset, MacroDataset
-from .geometry import dft_codebook, steering_vec
+from .geometry import dft_codebook, pattern_gain, steering_vec
 from .core import generate, load
 from .generator_utils import get_idxs_with_limits, LinearPath
 
 __version__ = consts.VERSION
 
 __all__ = ["generate", "load", "Dataset", "MacroDataset", "ChannelGenParameters", "config", "steering_vec", "dft_codebook",
-           "get_idxs_with_limits", "LinearPath", "DotDict", "consts"]
+           "pattern_gain", "get_idxs_with_limits", "LinearPath", "DotDict", "consts"]

@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = ("dmx_version", "dmx_last_error", "dmx_workspace_bytes", "dmx
                     "dmx_codebook_rate_subbands")
 
 MAX_LINKS = 8                             # DMX_MAX_LINKS
-PATTERN_IDS = {"isotropic": 0, "halfwave-dipole": 1}
+PATTERN_IDS = {"isotropic": 0, "halfwave-dipole": 1, "tr38901": 2}     # DMX_PATTERN_*
 COV_SIDES = {"tx": 0, "rx": 1}            # DMX_COV_TX / DMX_COV_RX
 
 _f32p = C.POINTER(C.c_float)

@@ -78,7 +78,7 @@ PARAMSET_ANT_SHAPE = "shape"
 PARAMSET_ANT_SPACING = "spacing"
 PARAMSET_ANT_ROTATION = "rotation"
 PARAMSET_ANT_RAD_PAT = "radiation_pattern"
-PARAMSET_ANT_RAD_PAT_VALS = ["isotropic", "halfwave-dipole"]
+PARAMSET_ANT_RAD_PAT_VALS = ["isotropic", "halfwave-dipole", "tr38901"]
 
 DATASET_ALIASES = {
     "los_status": LOS_PARAM_NAME,

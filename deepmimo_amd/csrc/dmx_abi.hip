@@ -25,6 +25,13 @@ int device_cu_count() {
     return cus;
 }
 
+static int check_patterns(const dmx_params* p) {
+    if (p->bs_pattern < 0 || p->bs_pattern > DMX_PATTERN_TR38901 || p->ue_pattern < 0 || p->ue_pattern > DMX_PATTERN_TR38901) {
+        set_error("unknown radiation pattern id"); return DMX_ERR_ARG;
+    }
+    return DMX_OK;
+}
+
 static int check_params(const dmx_params* p) {
     if (!p) { set_error("params is NULL"); return DMX_ERR_ARG; }
     for (int i = 0; i < 2; ++i) {
@@ -33,9 +40,7 @@ static int check_params(const dmx_params* p) {
     if ((int64_t)p->bs_shape[0] * p->bs_shape[1] > 65536 || (int64_t)p->ue_shape[0] * p->ue_shape[1] > 65536) {
         set_error("antenna panel larger than 65536 elements"); return DMX_ERR_SHAPE;
     }
-    if (p->bs_pattern < 0 || p->bs_pattern > 1 || p->ue_pattern < 0 || p->ue_pattern > 1) {
-        set_error("unknown radiation pattern id"); return DMX_ERR_ARG;
-    }
+    if (check_patterns(p)) return DMX_ERR_ARG;
     if (p->num_paths < 0) { set_error("num_paths must be >= 0"); return DMX_ERR_ARG; }
     if ((p->flags & ~DMX_FLAG_ADAPTIVE_TERMS) != 0 || p->reserved0 != 0) { set_error("unknown bits in dmx_params.flags / reserved0"); return DMX_ERR_ARG; }
     if (p->freq_domain) {
@@ -246,6 +251,7 @@ int dmx_fd_kernel_choice(const dmx_params* prm, int32_t n_paths_loaded) {
     if (!prm) { set_error("params is NULL"); return DMX_ERR_ARG; }
     if (n_paths_loaded < 0 || prm->n_selected < 0 || prm->bs_shape[0] < 1 || prm->bs_shape[1] < 1 || prm->ue_shape[0] < 1 ||
         prm->ue_shape[1] < 1) { set_error("bad shape"); return DMX_ERR_SHAPE; }
+    if (check_patterns(prm)) return DMX_ERR_ARG;
     WsView ws{};
     ws.P = used_paths(prm, n_paths_loaded);
     return fd_auto_choice(*prm, ws);

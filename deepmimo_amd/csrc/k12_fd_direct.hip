@@ -57,7 +57,7 @@ struct LdsRecords {
     __device__ double rx_z(int l) const { return r->rx_z[l]; }
 };
 
-// MODE = Stage1Form: 0 = angles as numbers (FoV, dipole pattern), 1 = lean, 2 = lean with exactly zero rotations (<= 32 loaded paths)
+// MODE = Stage1Form: 0 = angles as numbers (FoV, dipole or sector pattern), 1 = lean, 2 = lean with exactly zero rotations (<= 32 loaded paths)
 template <int KC, int MODE>
 __global__ __launch_bounds__(256) void k12_fd_direct(DirectArgs a, float2* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];

@@ -1,5 +1,5 @@
 // Per-path arithmetic of stage 1, shared by k1_path_prep.hip and the single-pass kernel k12_fd_direct.hip: the
-// constants, NumPy's float32 sin / cos, the float64 rotation, the field-of-view test, the dipole gain, the small
+// constants, NumPy's float32 sin / cos, the float64 rotation, the field-of-view test, the dipole and sector-element gains, the small
 // ballot helpers, and on top of them stage1_path - the whole per-path body from the ray loads to the record values -
 // with the lane-0 epilogue stage1_user_out.  Every function is __forceinline__ and follows the reference's dtype flow;
 // the including file decides the FMA contraction: both k1_path_prep.hip and k12_fd_direct.hip are compiled with
@@ -159,6 +159,17 @@ __device__ __forceinline__ double dipole_gain(double th) {
     if (!(fabs(s) > 1e-10)) return 0.0;
     const double c = cos(HALF_PI * cos(th));
     return 1.643 * (c * c / s);
+}
+
+// The sector element of 3GPP TR 38.901 Table 7.3-1 (DMX_PATTERN_TR38901) on the rotated, FoV-masked angles: boresight at
+// zenith pi/2, azimuth 0, 65 degree beamwidths, 8 dBi, each cut and their sum capped at 30 dB.  Linear power gain in
+// float64; NaN (no path, or masked by the FoV) -> 0 like the dipole's - fmin would drop the NaN, so it is tested.
+static constexpr double TR38901_BW = 65.0 * D2R_D;
+__device__ __forceinline__ double tr38901_gain(double th, double ph) {
+    if (isnan(th) || isnan(ph)) return 0.0;
+    const double v = (th - HALF_PI) / TR38901_BW, h = ph / TR38901_BW;
+    const double av = fmin(12.0 * (v * v), 30.0), ah = fmin(12.0 * (h * h), 30.0);
+    return exp10((8.0 - fmin(av + ah, 30.0)) / 10.0);
 }
 
 // the bits of a 64-lane ballot that belong to group `grp` of LPU lanes, shifted down to bit 0
@@ -325,8 +336,10 @@ __device__ __forceinline__ Stage1Path stage1_path(const Stage1Params& a, const d
     if (LEAN || iso) {
         pw = (double)pl;
     } else {
-        const double gt = a.bs_pat == DMX_PATTERN_HALFWAVE_DIPOLE ? dipole_gain(th_t) : 1.0;
-        const double gr = a.ue_pat == DMX_PATTERN_HALFWAVE_DIPOLE ? dipole_gain(th_r) : 1.0;
+        const double gt = a.bs_pat == DMX_PATTERN_HALFWAVE_DIPOLE ? dipole_gain(th_t)
+                                                                  : (a.bs_pat == DMX_PATTERN_TR38901 ? tr38901_gain(th_t, ph_t) : 1.0);
+        const double gr = a.ue_pat == DMX_PATTERN_HALFWAVE_DIPOLE ? dipole_gain(th_r)
+                                                                  : (a.ue_pat == DMX_PATTERN_TR38901 ? tr38901_gain(th_r, ph_r) : 1.0);
         pw = (double)pl * (gt * gr);
     }
     if constexpr (!LEAN) {
@@ -414,7 +427,7 @@ __device__ __forceinline__ void stage1_user_out(const dmx_side& side, const int 
 
 // The arithmetic form of stage 1 for a launch - ONE rule for launch_path_prep and launch_channels_fd_direct, whose
 // results are bit-identical by contract:
-//   STAGE1_FULL       something needs the angles as numbers (FoV, dipole pattern, angle / power / mask side outputs)
+//   STAGE1_FULL       something needs the angles as numbers (FoV, dipole or sector pattern, angle / power / mask side outputs)
 //   STAGE1_LEAN       nothing does: arccos / atan2 / FoV / dipole compiled out, sincos_lean
 //   STAGE1_LEAN_ZROT  lean, both rotations exactly zero and the same for every user, AND at most 32 loaded paths: the
 //                     zero-rotation form exists for the two-users-per-wave instantiation only, and it differs from the

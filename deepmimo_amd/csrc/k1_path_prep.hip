@@ -131,7 +131,10 @@ struct PrepArgsFull {
     double fc;
 };
 
-template <int LPU>
+// SECTOR: a side has the TR 38.901 sector element (DMX_PATTERN_TR38901).  An instantiation of its own, because with the
+// branch in the one body the dipole and FoV launches ran 1.6 - 2.2 % longer at 200k users (222 instead of 202 registers,
+// the same two waves per SIMD; profiles/README.md, r12): without it the body compiles to the instructions it had.
+template <int LPU, bool SECTOR = false>
 __global__ __launch_bounds__(64 * K1_WAVES, 8 / K1_WAVES) void k1_path_prep_full(PrepArgsFull a) {
     constexpr bool LEAN = false, ZROT = false;
     constexpr int UPW = 64 / LPU;                           // users per wave
@@ -236,8 +239,10 @@ __global__ __launch_bounds__(64 * K1_WAVES, 8 / K1_WAVES) void k1_path_prep_full
         if (LEAN || iso) {
             pw = (double)pl;
         } else {
-            const double gt = a.bs_pat == DMX_PATTERN_HALFWAVE_DIPOLE ? dipole_gain(th_t) : 1.0;
-            const double gr = a.ue_pat == DMX_PATTERN_HALFWAVE_DIPOLE ? dipole_gain(th_r) : 1.0;
+            const double gt = a.bs_pat == DMX_PATTERN_HALFWAVE_DIPOLE ? dipole_gain(th_t)
+                              : ((SECTOR && a.bs_pat == DMX_PATTERN_TR38901) ? tr38901_gain(th_t, ph_t) : 1.0);
+            const double gr = a.ue_pat == DMX_PATTERN_HALFWAVE_DIPOLE ? dipole_gain(th_r)
+                              : ((SECTOR && a.ue_pat == DMX_PATTERN_TR38901) ? tr38901_gain(th_r, ph_r) : 1.0);
             pw = (double)pl * (gt * gr);
         }
         if constexpr (!LEAN) {
@@ -369,6 +374,8 @@ int launch_path_prep(const dmx_rays& rays, const dmx_params& prm, const WsView& 
         a.bs_spacing = s1.bs_spacing; a.ue_spacing = s1.ue_spacing;
         a.P = s1.P; a.freq_domain = prm.freq_domain; a.n_sc = s1.n_sc; a.ts32 = s1.ts32;
         a.doppler = s1.doppler; a.rx_filter = rx_filter; a.need_angles = need_angles; a.sort_paths = sort_paths; a.fc = s1.fc;
+        if (s1.bs_pat == DMX_PATTERN_TR38901 || s1.ue_pat == DMX_PATTERN_TR38901)
+            return launch_dyn_lds(two ? k1_path_prep_full<32, true> : k1_path_prep_full<64, true>, "k1_path_prep", grid, block, 0, LDS_NO_RAISE, stream, a);
         return launch_dyn_lds(two ? k1_path_prep_full<32> : k1_path_prep_full<64>, "k1_path_prep", grid, block, 0, LDS_NO_RAISE, stream, a);
     }
     PrepArgs a;

@@ -4,7 +4,8 @@ The per-path geometry of the hot path (rotation, FoV, array response) runs on th
 (csrc/k1_path_prep.hip, csrc/k2_channel_fd*.hip).  What stays on the host is the one-vector
 utility ``steering_vec`` (geometry.py:322-339, exported at deepmimo/__init__.py:36-38) that users
 call to build beam codebooks, the orthonormal DFT codebook ``dft_codebook`` (extension: the angular side of
-``Dataset.compute_angle_delay``), and the element-index helper they need."""
+``Dataset.compute_angle_delay``), the element-index helper they need, and ``pattern_gain`` (extension): the element gain
+stage 1 applies for each ``radiation_pattern``, restated in NumPy for plotting and checking."""
 from __future__ import annotations
 
 import numpy as np
@@ -28,6 +29,39 @@ def steering_vec(array, phi: float = 0, theta: float = 0, spacing: float = 0.5) 
     gamma = 1j * kd * np.array([np.sin(zen) * np.cos(az), np.sin(zen) * np.sin(az), np.cos(zen)])
     resp = np.exp(idx @ gamma).reshape(-1, 1)
     return resp / np.linalg.norm(resp)
+
+
+def pattern_gain(name: str, theta, phi=None):
+    """Linear power gain of one antenna element with the radiation pattern `name`, as stage 1 applies it to a path
+    (``power_linear_ant_gain = power_linear * g_tx * g_rx``): NumPy float64, angles in RADIANS in the panel's own frame
+    (after ``rotation``): zenith `theta` in [0, pi], azimuth `phi` in (-pi, pi], boresight theta = pi/2, phi = 0.
+
+    * ``"isotropic"``: the float 1.0.
+    * ``"halfwave-dipole"``: 1.643 cos^2(pi/2 cos theta) / sin theta where |sin theta| > 1e-10, else 0 (`phi` unused).
+    * ``"tr38901"`` (extension): the sector element of 3GPP TR 38.901 Table 7.3-1, with b = 65 degrees,
+
+          A_v = min(12 ((theta - pi/2) / b)^2, 30),  A_h = min(12 (phi / b)^2, 30),  A = min(A_v + A_h, 30)
+          gain = 10^((8 - A) / 10)            8 dBi at boresight, floor -22 dBi
+
+    A NaN angle (no path, or a path the field of view masks) gives 0."""
+    if name == "isotropic":
+        return 1.0
+    theta = np.asarray(theta, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        if name == "halfwave-dipole":
+            s = np.sin(theta)
+            ok = np.abs(s) > 1e-10                               # False for NaN
+            return np.where(ok, 1.643 * (np.cos(np.pi / 2 * np.cos(theta)) ** 2 / np.where(ok, s, 1.0)), 0.0)
+        if name == "tr38901":
+            if phi is None:
+                raise ValueError("pattern_gain: 'tr38901' depends on the azimuth, give phi")
+            phi = np.asarray(phi, dtype=np.float64)
+            b = np.deg2rad(65.0)
+            a_v = np.minimum(12.0 * ((theta - np.pi / 2) / b) ** 2, 30.0)
+            a_h = np.minimum(12.0 * (phi / b) ** 2, 30.0)
+            gain = 10.0 ** ((8.0 - np.minimum(a_v + a_h, 30.0)) / 10.0)
+            return np.where(np.isnan(theta) | np.isnan(phi), 0.0, gain)
+    raise NotImplementedError(f"The given '{name}' antenna radiation pattern is not applicable.")
 
 
 def dft_codebook(shape) -> np.ndarray:

@@ -39,6 +39,13 @@ extern "C" {
 /* radiation patterns: deepmimo/consts.py:254, deepmimo/generator/ant_patterns.py:21-71 */
 #define DMX_PATTERN_ISOTROPIC        0
 #define DMX_PATTERN_HALFWAVE_DIPOLE  1
+/* The sector element of 3GPP TR 38.901 Table 7.3-1 (Sionna's "tr38901"; not in the reference).  On a path's rotated,
+ * FoV-masked angles - zenith th in [0, pi], azimuth ph in (-pi, pi], boresight th = pi/2, ph = 0: the panel lies in the
+ * y-z plane and faces +x, where the FoV test is centred - in float64, with b = 65 degrees in radians:
+ *   A_v = min(12 ((th - pi/2) / b)^2, 30),  A_h = min(12 (ph / b)^2, 30),  A = min(A_v + A_h, 30),
+ *   gain = 10^((8 - A) / 10)     linear power gain, 8 dBi at boresight, floor -22 dBi; 0 where th or ph is NaN
+ * It multiplies the path power like the dipole's gain.  Either side takes any of the three, independently. */
+#define DMX_PATTERN_TR38901          2
 
 /* Ray-path records of one (TX, RX-set) pair: the float32 matrices of core.py:209-219. */
 typedef struct dmx_rays {
