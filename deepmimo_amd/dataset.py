@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import inspect
 import types as _types
+from collections.abc import Mapping
 from typing import Any, Dict, Optional
 
 import numpy as np
@@ -38,6 +39,16 @@ _ROT_KEYS = (c.AOD_EL_ROT_PARAM_NAME, c.AOD_AZ_ROT_PARAM_NAME, c.AOA_EL_ROT_PARA
 _FOV_ANGLE_KEYS = (c.AOD_EL_FOV_PARAM_NAME, c.AOD_AZ_FOV_PARAM_NAME, c.AOA_EL_FOV_PARAM_NAME, c.AOA_AZ_FOV_PARAM_NAME)
 _UE_ROT_RESOLVED = "_ue_rotation_resolved"     # [n_ue, 3] degrees actually used for the cached rotated angles
 _PATTERNS_IN_EFFECT = "_patterns_in_effect"    # (bs, ue) radiation patterns behind the cached `_power_linear_ant_gain`
+
+# channel time series (DESIGN.md "Channel time series")
+_TIME_BLOCK_BYTES = 1 << 30                    # most the tiled ray matrices of one block of snapshots may take
+_RX_VEL, _TX_VEL = "rx_vel", "tx_vel"
+_TIMES, _N_TIMES, _N_UE_PER_TIME = "times", "n_times", "n_ue_per_time"
+_TIME_KEYS = (_TIMES, _N_TIMES, _N_UE_PER_TIME)
+_FOV_KEYS = ("bs_fov", "ue_fov")
+_NOT_PER_USER = (_TX_VEL, c.TX_POS_PARAM_NAME) + _FOV_KEYS + _TIME_KEYS      # never the user axis, whatever their length
+# what a block of snapshots needs to run a channel call, and nothing a caller of the view might read beside it
+_BLOCK_KEYS = c.RAY_FIELDS + (c.DOPPLER_VEL_PARAM_NAME, c.DOPPLER_ACC_PARAM_NAME, c.CH_PARAMS_PARAM_NAME) + _FOV_KEYS
 
 _engines: Dict[int, Any] = {}
 
@@ -220,7 +231,10 @@ class Dataset(DotDict):
         if cached is not None:
             return cached
         if rot.ndim == 2 and rot.shape == (3, 2):
-            rot = np.random.uniform(rot[:, 0], rot[:, 1], (self.n_ue, 3))
+            if _N_TIMES in self._data:            # a view of `at_times`: a UE keeps its orientation over the snapshots
+                rot = np.tile(np.random.uniform(rot[:, 0], rot[:, 1], (self._data[_N_UE_PER_TIME], 3)), (self._data[_N_TIMES], 1))
+            else:
+                rot = np.random.uniform(rot[:, 0], rot[:, 1], (self.n_ue, 3))
         rot = np.ascontiguousarray(rot, dtype=np.float64).reshape(-1, 3)
         self._data[_UE_ROT_RESOLVED] = rot
         return rot
@@ -269,11 +283,12 @@ class Dataset(DotDict):
             self._store_side(prep, None if want_side is True else (rays, params.deepcopy(), kw))
         return eng, prep
 
-    def _run_single_pass(self, inputs, to_host: bool):
+    def _run_single_pass(self, inputs, to_host: bool, out=None):
         """The single-pass route of `compute_channels` (engine.single_pass_route): rays -> channels in one launch, the
         light side products from the same kernel, the heavy ones deferred to a stage-1 pass on their first read.
         Returns ((channels, max delay) or None when the route does not apply and the two calls have to run, the call
-        structs if they were built on the way - stage 1 then takes them instead of building them again)."""
+        structs if they were built on the way - stage 1 then takes them instead of building them again).  `out`: the
+        resident tensor to write into (not with `to_host`)."""
         from .engine import single_pass_preferred, single_pass_route
         eng, params, rays, kw = inputs
         cfg = (config.get("single_pass", "auto"), config.get("fd_kernel_variant", 0), config.get("adaptive_precision", False))
@@ -289,7 +304,7 @@ class Dataset(DotDict):
                                  not (to_host and eng.host_copy_chunks(rays.n_ue, m_rx * m_tx * p.n_selected)),
                                  single_pass_preferred(m_rx + m_tx, rays.n_paths, p.n_selected)):
             return None, structs
-        out, side = eng.channels_direct(rays, params, structs=structs)
+        out, side = eng.channels_direct(rays, params, out=out, structs=structs)
         prep = _types.SimpleNamespace(side=side)
         self._store_side(prep, (rays, params.deepcopy(), kw))
         return ((out.cpu().numpy() if to_host else out), eng.max_delay(prep)), structs
@@ -362,37 +377,59 @@ class Dataset(DotDict):
     def __setstate__(self, state):
         object.__setattr__(self, "_data", state["_data"])
 
-    def compute_channels(self, params: Optional[ChannelGenParameters] = None):
+    def compute_channels(self, params: Optional[ChannelGenParameters] = None, *, times=None, carrier_freq=None):
         """dataset.py:224-268.  Returns complex64 [n_ue, M_rx, M_tx, K] (freq_domain) or
         [n_ue, M_rx, M_tx, num_paths]: a NumPy array by default, the HBM-resident torch tensor when
-        ``config('channel_output') == 'torch'``.  Cached as ``dataset.channel``."""
+        ``config('channel_output') == 'torch'``.  Cached as ``dataset.channel``.
+
+        ``times`` (keyword, extension): a 1-D array of T seconds gives the snapshots of ``at_times(times, carrier_freq)``
+        as [T, n_ue, M_rx, M_tx, K], time-major - ``out[t]`` has the layout of one call - and a scalar the one snapshot
+        without the leading axis; nothing is cached then.  A per-user [n_ue, 3] UE rotation holds for every snapshot."""
+        if times is not None:
+            return self._channels_over_time(params, times, carrier_freq)
         params = self._call_params(params)
         np.random.seed(1001)                                                   # dataset.py:250
         to_host = config.get("channel_output", "numpy") != "torch"
         if to_host:                                                            # before any GPU work is spent on it
-            ofdm_, n_ant = params[c.PARAMSET_OFDM], [int(np.prod(params[s_][c.PARAMSET_ANT_SHAPE])) for s_ in (c.PARAMSET_ANT_BS, c.PARAMSET_ANT_UE)]
-            last = len(np.atleast_1d(ofdm_[c.PARAMSET_OFDM_SC_SAMP])) if params[c.PARAMSET_FD_CH] else int(params[c.PARAMSET_NUM_PATHS])
-            self._guard_host_copy(8 * int(self.n_ue) * n_ant[0] * n_ant[1] * last)
-        inputs = self._prep_inputs()
-        direct, structs = self._run_single_pass(inputs, to_host)
-        if direct is not None:
-            out, max_delay = direct
-        else:
-            eng, prep = self._run_prep(want_side="light", inputs=inputs, structs=structs)
-            variant = int(config.get("fd_kernel_variant", 0))
-            out = eng.channels_to_host(prep, variant=variant) if to_host else eng.channels(prep, variant=variant)
-            max_delay = eng.max_delay(prep) if params[c.PARAMSET_FD_CH] else None
+            self._guard_host_copy(8 * int(np.prod(self._channel_shape(params))))
+        out, max_delay = self._channels_once(params, to_host)
         ofdm = params[c.PARAMSET_OFDM]
         if params[c.PARAMSET_FD_CH]:
             self._warn_symbol_duration(max_delay, ofdm)
         self[c.CHANNEL_PARAM_NAME] = out
         return out
 
-    def iter_channels(self, params: Optional[ChannelGenParameters] = None, chunk_users: int = 4096):
+    def _channel_shape(self, params):
+        """(n_ue, M_rx, M_tx, K or num_paths): the tensor the host guard of `compute_channels` sizes."""
+        ofdm_, n_ant = params[c.PARAMSET_OFDM], [int(np.prod(params[s_][c.PARAMSET_ANT_SHAPE])) for s_ in (c.PARAMSET_ANT_BS, c.PARAMSET_ANT_UE)]
+        last = len(np.atleast_1d(ofdm_[c.PARAMSET_OFDM_SC_SAMP])) if params[c.PARAMSET_FD_CH] else int(params[c.PARAMSET_NUM_PATHS])
+        return int(self.n_ue), n_ant[1], n_ant[0], last
+
+    def _channels_once(self, params, to_host: bool, out=None):
+        """The GPU part of `compute_channels` for the stored parameters `params`: the single pass where it applies, else
+        stage 1 and stage 2.  Returns (channels, the delay maximum or None in the time domain).  `out`: the resident
+        tensor to write into (not with `to_host`)."""
+        inputs = self._prep_inputs()
+        direct, structs = self._run_single_pass(inputs, to_host, out)
+        if direct is not None:
+            return direct
+        eng, prep = self._run_prep(want_side="light", inputs=inputs, structs=structs)
+        variant = int(config.get("fd_kernel_variant", 0))
+        H = eng.channels_to_host(prep, variant=variant) if to_host else eng.channels(prep, out=out, variant=variant)
+        return H, (eng.max_delay(prep) if params[c.PARAMSET_FD_CH] else None)
+
+    def iter_channels(self, params: Optional[ChannelGenParameters] = None, chunk_users: int = 4096, *, times=None,
+                      carrier_freq=None):
         """Generate channels in user chunks (extension): yields ``(user_begin, H_chunk)`` with ``H_chunk`` a
         NumPy complex64 array [<= chunk_users, M_rx, M_tx, K].  For scenarios whose full tensor (1 MB per user at
         64x4 antennas x 512 subcarriers) fits neither host memory nor one NumPy array; stage 1 runs once, stage 2
-        per chunk through the C-ABI's user_begin / user_count range.  Nothing is cached as ``channel``."""
+        per chunk through the C-ABI's user_begin / user_count range.  Nothing is cached as ``channel``.
+
+        With ``times`` (keyword; as in ``compute_channels``) it yields ``(t_index, user_begin, H_chunk)``, the snapshots
+        in order and the users of a snapshot in order; stage 1 runs once per block of snapshots."""
+        if times is not None:
+            yield from self._iter_channels_over_time(params, chunk_users, times, carrier_freq)
+            return
         params = self._call_params(params)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
@@ -831,20 +868,253 @@ class Dataset(DotDict):
         parameters) by reference, every public array whose first axis is the user axis indexed by `idxs`, everything
         else as is; private (cached per-path) entries are dropped and recomputed on demand.  Device-resident rays stay
         on the device."""
+        def take(value):
+            if isinstance(value, np.ndarray):
+                return value[idxs]
+            import torch
+            return value[torch.as_tensor(np.asarray(idxs), device=value.device)]
+        return self._with_users(len(idxs), take, self.to_dict().items(), skip=_TIME_KEYS)
+
+    def _with_users(self, n_new: int, take, items, skip=(), fixed=()) -> "Dataset":
+        """New Dataset of `n_new` users from `items`, (key, value) pairs of this one: the shared objects by reference,
+        every array (NumPy or torch) whose first axis is the user axis through `take`, everything else as is.  Private
+        entries and the keys in `skip` are dropped; the keys in `fixed` never count as per-user arrays."""
         n_ue = self.n_ue
         init = {k: self._host(k) for k in SHARED_PARAMS if k in self._data}
-        init[c.N_UE_PARAM_NAME] = len(idxs)
+        init[c.N_UE_PARAM_NAME] = n_new
         out = Dataset(init)
-        for key, value in self.to_dict().items():
-            if key.startswith("_") or key in init:
+        for key, value in items:
+            if key.startswith("_") or key in init or key in skip:
                 continue
-            if isinstance(value, np.ndarray) and value.ndim > 0 and value.shape[0] == n_ue:
-                value = value[idxs]
-            elif hasattr(value, "detach") and value.dim() > 0 and value.shape[0] == n_ue:
-                import torch
-                value = value[torch.as_tensor(np.asarray(idxs), device=value.device)]
+            if key not in fixed and (
+                    (isinstance(value, np.ndarray) and value.ndim > 0 and value.shape[0] == n_ue) or
+                    (hasattr(value, "detach") and value.dim() > 0 and value.shape[0] == n_ue)):
+                value = take(value)
             out[key] = value
         return out
+
+    # -------------------------------------------------------------- channel time series (extension; DESIGN.md)
+    def set_velocities(self, rx_vel=None, tx_vel=None) -> None:
+        """Per-path Doppler from the velocities of the terminals (extension).  ``rx_vel``: [3] or [n_ue, 3] in m/s, global
+        x / y / z; ``tx_vel``: [3]; None is 0.  Stores them as ``rx_vel`` float64 [n_ue, 3] and ``tx_vel`` float64 [3] and
+        writes the two ray matrices the Doppler model reads, float32 [n_ue, n_paths]:
+
+            doppler_vel[u, l] = -(rx_vel[u] . k(aoa_az, aoa_el) + tx_vel . k(aod_az, aod_el))     # NaN where the path is
+            doppler_acc       = 0
+            k(phi, theta)     = (sin theta cos phi, sin theta sin phi, cos theta)                 # el is the zenith angle
+
+        from the stored, unrotated angles, in float64, rounded once.  k is the vector of the array response
+        ``exp(+j k p . k)``: a terminal displaced by v t sees the phase an array element at v t would see, so a path a
+        terminal moves towards gets a negative ``doppler_vel`` and a positive Doppler shift (``doppler_shifts``).  Changes
+        no result of a call with ``enable_doppler = 0``."""
+        from .doppler import check_velocity, doppler_velocity
+        rx = check_velocity("set_velocities", _RX_VEL, rx_vel, self.n_ue)
+        tx = check_velocity("set_velocities", _TX_VEL, tx_vel)
+        vel = doppler_velocity(self[c.AOA_AZ_PARAM_NAME], self[c.AOA_EL_PARAM_NAME], self[c.AOD_AZ_PARAM_NAME],
+                               self[c.AOD_EL_PARAM_NAME], rx, tx)
+        self._data[_RX_VEL], self._data[_TX_VEL] = rx, tx
+        self._data[c.DOPPLER_VEL_PARAM_NAME] = vel
+        self._data[c.DOPPLER_ACC_PARAM_NAME] = vel.new_zeros(vel.shape) if hasattr(vel, "detach") else np.zeros_like(vel)
+
+    def _doppler_matrices(self, who: str):
+        """(doppler_vel, doppler_acc or None) as stored - v3 data or `set_velocities`; without the first a ValueError."""
+        vel = self._data.get(c.DOPPLER_VEL_PARAM_NAME)
+        if vel is None:
+            raise ValueError(f"{who}: the dataset has no per-path Doppler (doppler_vel): call set_velocities(rx_vel, tx_vel) "
+                             "first, or load rays that carry doppler_vel / doppler_acc")
+        return vel, self._data.get(c.DOPPLER_ACC_PARAM_NAME)
+
+    def _time_carrier(self, who: str, carrier_freq) -> float:
+        """`carrier_freq`, else rt_params.frequency, in Hz; neither finite and > 0 is a ValueError."""
+        fc = self._carrier_freq() if carrier_freq is None else carrier_freq
+        try:
+            fc = float(fc)
+        except (TypeError, ValueError):
+            fc = float("nan")
+        if not (np.isfinite(fc) and fc > 0):
+            raise ValueError(f"{who}: no carrier frequency: pass carrier_freq (Hz, finite and > 0) or set rt_params.frequency")
+        return fc
+
+    def doppler_shifts(self, carrier_freq=None) -> np.ndarray:
+        """Doppler shift of every path in Hz, ``-(f_c / c) * doppler_vel``: NumPy float64 [n_ue, n_paths], NaN where there
+        is no path.  ``f_c``: ``carrier_freq``, else ``rt_params.frequency``."""
+        from .doppler import LIGHTSPEED
+        fc = self._time_carrier("doppler_shifts", carrier_freq)
+        vel, _ = self._doppler_matrices("doppler_shifts")
+        vel = vel.detach().cpu().numpy() if hasattr(vel, "detach") else np.asarray(vel)
+        return -(fc / LIGHTSPEED) * vel.astype(np.float64)
+
+    def at_times(self, times, carrier_freq=None) -> "Dataset":
+        """The dataset at ``times`` (a scalar or a 1-D array of T finite seconds) as a plain Dataset of T * n_ue users,
+        time-major: row t * n_ue + u is user u at times[t] (extension).  Every ``compute_*`` works on it unchanged.
+
+        A snapshot turns each path's phase and nothing else:
+
+            phase[t, u, l] = wrap(phase[u, l] - 360 (f_c / c) (doppler_vel[u, l] t + doppler_acc[u, l] t^2 / 2))
+
+        in float64, wrapped into [-180, 180) and rounded to float32 once; where the turn is 0 the stored phase is kept bit
+        for bit, NaN stays NaN.  ``f_c``: ``carrier_freq``, else ``rt_params.frequency``.  Delays, angles and powers stay
+        what they are: the model holds while |v| t is small against the distances of the scene.  The kernels' own term of
+        ``enable_doppler = 1`` (a phase per path from its delay) multiplies on top; its cross term a t tau is not modelled.
+
+        Every public array whose first axis is the user axis is tiled (as ``subset`` indexes it), shared objects are held
+        by reference, ``ch_params``, ``bs_fov`` and ``ue_fov`` are copied, cached results are not carried.  Rays in HBM
+        are advanced there; with host rays nothing here touches the GPU.  The view also holds ``times`` [T], ``n_times``
+        and ``n_ue_per_time``; ``split_times(x)`` gives a result [T * n_ue, ...] as [T, n_ue, ...].  A UE keeps its
+        orientation: a (3, 2) rotation range is drawn once for the n_ue users and tiled; a per-user rotation passed to
+        the view itself has to be [T * n_ue, 3].  No Doppler matrices (``set_velocities``), a ``times`` that is empty, not
+        finite or more than 1-D, or no carrier frequency raise ValueError."""
+        from .doppler import check_times
+        t, _ = check_times("at_times", times)
+        return self._time_view("at_times", t, carrier_freq)
+
+    def _time_view(self, who: str, t: np.ndarray, carrier_freq, only=None) -> "Dataset":
+        """`at_times` for the checked float64 `t` [T].  `only`: the public keys to carry (a block of the channel calls
+        carries what the call reads and no more)."""
+        from .doppler import advance_phase
+        fc = self._time_carrier(who, carrier_freq)
+        vel, acc = self._doppler_matrices(who)
+        T, n_ue = len(t), int(self.n_ue)
+
+        def tile(value):
+            if isinstance(value, np.ndarray):
+                return np.tile(value, (T,) + (1,) * (value.ndim - 1))
+            return value.repeat(T, *([1] * (value.dim() - 1)))
+
+        cached = (set(self._computed_attributes) - {c.CH_PARAMS_PARAM_NAME}) | {"beam_mean_amplitude", c.PHASE_PARAM_NAME}
+        keys = [k for k in self._data if not k.startswith("_") and k not in cached and (only is None or k in only)]
+        view = self._with_users(T * n_ue, tile, ((k, self._host(k)) for k in keys), skip=_TIME_KEYS, fixed=_NOT_PER_USER)
+        d = view._data
+        d[c.PHASE_PARAM_NAME] = advance_phase(self[c.PHASE_PARAM_NAME], vel, acc, t, fc)
+        if c.CH_PARAMS_PARAM_NAME in d:
+            d[c.CH_PARAMS_PARAM_NAME] = self._tiled_params(self._data[c.CH_PARAMS_PARAM_NAME], T)
+            drawn = self._data.get(_UE_ROT_RESOLVED)                       # the parent's draw: the same UEs, later
+            if drawn is not None:
+                d[_UE_ROT_RESOLVED] = np.tile(drawn, (T, 1))
+        for k in _FOV_KEYS:
+            if isinstance(d.get(k), np.ndarray):
+                d[k] = d[k].copy()
+        d[_TIMES], d[_N_TIMES], d[_N_UE_PER_TIME] = t.copy(), T, n_ue
+        return view
+
+    @staticmethod
+    def _tiled_params(params: ChannelGenParameters, T: int) -> ChannelGenParameters:
+        """A copy of `params` for T * n_ue users: a per-user UE rotation [n_ue, 3] is tiled, everything else holds as is."""
+        params = params.deepcopy()
+        rot = np.asarray(params[c.PARAMSET_ANT_UE][c.PARAMSET_ANT_ROTATION])
+        if rot.ndim == 2 and rot.shape != (3, 2):
+            params[c.PARAMSET_ANT_UE][c.PARAMSET_ANT_ROTATION] = np.tile(rot, (T, 1))
+        return params
+
+    def split_times(self, x):
+        """A result of a ``compute_*`` on a view of ``at_times`` - an array or tensor [T * n_ue, ...], or a tuple or dict
+        of them - as [T, n_ue, ...]: a view of the same memory, never a copy."""
+        T, n = self._data.get(_N_TIMES), self._data.get(_N_UE_PER_TIME)
+        if T is None:
+            raise ValueError("split_times: this dataset is not a view of at_times")
+        if isinstance(x, Mapping):
+            return type(x)({k: self.split_times(v) for k, v in x.items()})
+        if isinstance(x, (tuple, list)):
+            return type(x)(self.split_times(v) for v in x)
+        shape = tuple(x.shape)
+        if not shape or shape[0] != T * n:
+            raise ValueError(f"split_times: the first axis must be n_times * n_ue = {T * n}, got shape {shape}")
+        if hasattr(x, "detach"):
+            return x.view((T, n) + shape[1:])
+        y = x.view()
+        y.shape = (T, n) + shape[1:]                                        # raises where NumPy would have to copy
+        return y
+
+    def _time_blocks(self, T: int):
+        """(begin, count) of the blocks of snapshots a channel call over time runs in: the tiled ray matrices of a block
+        stay under _TIME_BLOCK_BYTES."""
+        per_snapshot = 4 * int(self.n_ue) * self._loaded_paths() * (len(c.RAY_FIELDS) + 2)
+        step = max(1, int(_TIME_BLOCK_BYTES) // max(per_snapshot, 1))
+        return [(b, min(step, T - b)) for b in range(0, T, step)]
+
+    def _time_call(self, who: str, params, times, carrier_freq):
+        """The checks every channel call with `times` makes before any GPU work: (validated parameters, float64 times [T],
+        whether `times` was a scalar, the carrier frequency)."""
+        from .doppler import check_times
+        t, scalar = check_times(who, times)
+        fc = self._time_carrier(who, carrier_freq)
+        self._doppler_matrices(who)
+        return self._call_params(params), t, scalar, fc
+
+    def _in_hbm(self, keys) -> "Dataset":
+        """A Dataset of the same users with `keys` of this one, its per-user NumPy arrays uploaded as they are (dtype kept):
+        the source of the block views of a channel call over time.  The rays then cross PCIe once, untiled, and the tiling
+        and the advance run in HBM in the same float64 steps as on the host."""
+        import torch
+        dev, n_ue = _engine().device, int(self.n_ue)
+        src = Dataset({k: self._host(k) for k in SHARED_PARAMS if k in self._data})
+        d = src._data
+        d[c.N_UE_PARAM_NAME] = n_ue
+        for k in keys:
+            if k not in self._data:
+                continue
+            v = self._host(k)
+            if isinstance(v, np.ndarray) and k not in _NOT_PER_USER and v.ndim > 0 and v.shape[0] == n_ue:
+                v = torch.from_numpy(np.ascontiguousarray(v)).to(dev)
+            d[k] = v
+        if _UE_ROT_RESOLVED in self._data:
+            d[_UE_ROT_RESOLVED] = self._data[_UE_ROT_RESOLVED]
+        return src
+
+    def _block_view(self, who: str, params, t: np.ndarray, fc: float) -> "Dataset":
+        """The view of one block of snapshots with `params` stored for its T * n_ue users."""
+        view = self._time_view(who, t, fc, only=_BLOCK_KEYS)
+        view._call_params(self._tiled_params(params, len(t)))
+        return view
+
+    def _channels_over_time(self, params, times, carrier_freq):
+        """`compute_channels(times=...)`: one stage 1 and one stage 2 (or one single pass) per block of snapshots, written
+        time-major where they are returned from - no channel-sized tensor is ever transposed."""
+        params, t, scalar, fc = self._time_call("compute_channels", params, times, carrier_freq)
+        to_host = config.get("channel_output", "numpy") != "torch"
+        shape = self._channel_shape(params)
+        if not params[c.PARAMSET_FD_CH]:
+            shape = shape[:3] + (min(shape[3], self._loaded_paths()),)
+        T, n_ue = len(t), shape[0]
+        if to_host:                                                            # the whole series, before any GPU work
+            self._guard_host_copy(8 * T * int(np.prod(shape)))
+        blocks = self._time_blocks(T)
+        src = self._in_hbm(_BLOCK_KEYS)
+        out = None
+        for b, nb in blocks:
+            view = src._block_view("compute_channels", params, t[b:b + nb], fc)
+            dst = None
+            if len(blocks) > 1 and not to_host:
+                if out is None:
+                    import torch
+                    out = torch.empty((T,) + shape, dtype=torch.complex64, device=_engine().device)
+                dst = out[b:b + nb].view((nb * n_ue,) + shape[1:])
+            np.random.seed(1001)
+            H, max_delay = view._channels_once(view.ch_params, to_host, out=dst)
+            if b == 0 and params[c.PARAMSET_FD_CH]:                            # the delays are those of every snapshot
+                self._warn_symbol_duration(max_delay, params[c.PARAMSET_OFDM])
+            if len(blocks) == 1:
+                out = H.reshape((T,) + shape)
+            elif to_host:
+                if out is None:
+                    out = np.empty((T,) + shape, dtype=np.complex64)
+                out[b:b + nb] = H.reshape((nb,) + shape)
+        return out[0] if scalar else out
+
+    def _iter_channels_over_time(self, params, chunk_users, times, carrier_freq):
+        """`iter_channels(times=...)`: stage 1 once per block of snapshots, stage 2 per snapshot and user chunk."""
+        params, t, _, fc = self._time_call("iter_channels", params, times, carrier_freq)
+        n_ue, step = int(self.n_ue), max(1, int(chunk_users))
+        variant = int(config.get("fd_kernel_variant", 0))
+        src = self._in_hbm(_BLOCK_KEYS)
+        for b, nb in self._time_blocks(len(t)):
+            view = src._block_view("iter_channels", params, t[b:b + nb], fc)
+            np.random.seed(1001)
+            eng, prep = view._run_prep(want_side="light")
+            for i in range(nb):
+                for ub in range(0, n_ue, step):
+                    cnt = min(step, n_ue - ub)
+                    yield b + i, ub, eng.channels_to_host(prep, variant=variant, user_begin=i * n_ue + ub, user_count=cnt)
 
     def get_active_idxs(self) -> np.ndarray:
         """Users with at least one path (dataset.py:775-781)."""
@@ -921,8 +1191,8 @@ class Dataset(DotDict):
 
 class MacroDataset:
     """List of Datasets (one per TX / RX-set pair); attribute access and method calls fan out to
-    every child, a single child returns its value unwrapped (dataset.py:888-998).  `compute_cell_rate` is the one method
-    of its own: it reads all children in one launch."""
+    every child, a single child returns its value unwrapped (dataset.py:888-998).  Methods of its own: `compute_cell_rate`
+    reads all children in one launch, `at_times` returns a MacroDataset of the children's views."""
 
     SINGLE_ACCESS_METHODS = {"info"}
     PROPAGATE_METHODS = {name for name, _ in inspect.getmembers(Dataset, predicate=inspect.isfunction)
@@ -996,6 +1266,17 @@ class MacroDataset:
         res = runs[0][0].cell_rate([prep for _, prep in runs], snr_db, serving=serving, per_subcarrier=per_subcarrier,
                                    details=details)
         return Dataset._deliver(res)
+
+    def at_times(self, times, carrier_freq=None) -> "MacroDataset":
+        """A MacroDataset of the children's ``Dataset.at_times(times, carrier_freq)`` views - T * n_ue users each, time-major
+        - so ``compute_cell_rate`` runs over time (extension).  ``split_times`` gives its results as [T, n_ue, ...]."""
+        return MacroDataset([d.at_times(times, carrier_freq) for d in self.datasets])
+
+    def split_times(self, x):
+        """``Dataset.split_times`` of the first child: the children of a view share the times and the users."""
+        if not self.datasets:
+            raise IndexError("MacroDataset is empty")
+        return self.datasets[0].split_times(x)
 
     def __getitem__(self, idx):
         if isinstance(idx, (int, slice)):
