@@ -110,8 +110,7 @@ __device__ __forceinline__ void codebook_rate_body(const WsView& ws, const CbArg
     float2* w = ab + (size_t)rc * ld;                                                // [ld][kc]
     const int64_t u = a.user_begin + ul;
     float* oc = out_rate_c ? out_rate_c + (size_t)ul * C : nullptr;
-    int n = __builtin_amdgcn_readfirstlane(ws.n_keep[u]);
-    n = n < ld ? n : ld;
+    const int n = kept_paths(ws, u);
     const int n_sb = SB ? sb.n_sb : 1;
     if (n <= 0) {                                                            // no kept path
         if (oc) for (int i = lane; i < C; i += 64) oc[i] = 0.f;
@@ -134,12 +133,7 @@ __device__ __forceinline__ void codebook_rate_body(const WsView& ws, const CbArg
     const WsRecords rec{ws, (size_t)u * ws.P};
 
     // 1  the a_rx table
-    for (int i = lane; i < M * n; i += 64) {
-        const int t = i / n, l = i - t * n;
-        float s, c;
-        sincos_rev(frac_rev(__builtin_fma((double)(t % a.ue_mh), rec.rx_y(l), (double)(t / a.ue_mh) * rec.rx_z(l))), s, c);
-        as[t * ld + l] = make_float2(c, s);
-    }
+    fill_array_table(as, rec, true, 0, M, a.ue_mh, n, ld, lane);
 
     const int kl = lane & (a.kcp - 1), sl = lane >> a.log2_kcp;              // this lane's subcarrier of the chunk and slice
     // where lane j finds codeword j of a chunk after phase 5: slice j mod S, trip j / S
@@ -150,21 +144,7 @@ __device__ __forceinline__ void codebook_rate_body(const WsView& ws, const CbArg
         const int nc = C - c0 < cpc ? C - c0 : cpc;
         // 3  rows c0 L .. (c0 + nc) L of the row table: one contiguous block on both sides
         wave_lds_fence();                                                    // the last chunk's reads before this chunk's writes
-        {
-            const size_t off = ((size_t)ul * rows_all + (size_t)c0 * L) * ld;
-            const float2* src = a.ftab + off;
-            const int cnt = nc * L * ld;
-            if ((off & 1) == 0) {
-                const float4* s4 = reinterpret_cast<const float4*>(src);
-                for (int i = lane; i < cnt / 2; i += 64) {
-                    const float4 v = s4[i];
-                    ab[2 * i] = make_float2(v.x, v.y); ab[2 * i + 1] = make_float2(v.z, v.w);
-                }
-                if ((cnt & 1) && lane == 0) ab[cnt - 1] = src[cnt - 1];
-            } else {
-                for (int i = lane; i < cnt; i += 64) ab[i] = src[i];
-            }
-        }
+        copy_rows_to_lds(ab, a.ftab, ((size_t)ul * rows_all + (size_t)c0 * L) * ld, nc * L * ld, lane);
 
         float wide = 0.f;                                                    // SB: the subbands' sums of this lane's codeword, in subband order
         for (int b = 0; b < n_sb; ++b) {
@@ -175,15 +155,7 @@ __device__ __forceinline__ void codebook_rate_body(const WsView& ws, const CbArg
                 const int kn = ke - k0 < kc ? ke - k0 : kc;
                 // 2  w of the chunk
                 wave_lds_fence();
-                for (int i = lane; i < n * kn; i += 64) {
-                    const int l = i / kn, k = i - l * kn;
-                    float s, c;
-                    // the fractional part of the EXACT product x * k (k2_small_body.h)
-                    const double x = (double)rec.dn(l) * a.inv_n, kd = (double)a.sc[k0 + k];
-                    sincos_rev((float)__builtin_fma(x, kd, -rint(x * kd)), s, c);
-                    const float cr = rec.c_re(l) * a.scale, ci = rec.c_im(l) * a.scale;
-                    w[l * kc + k] = make_float2(fmaf(cr, c, ci * s), fmaf(ci, c, -(cr * s)));     // c_l (cos - j sin)
-                }
+                fill_w_chunk(w, rec, a.sc, k0, a.inv_n, a.scale, n, kn, kc, lane);
                 wave_lds_fence();
 
                 // 4, 5  one codeword per slice and trip

@@ -73,7 +73,8 @@ struct RateArgs {
     int ld;              // table row stride in path slots (= P)
 };
 
-// 4  epilogue_logdet, and rows_pair of phase 3: k7_rate_body.h, shared with k8_cell_rate.hip
+// 2 .. 4  the w chunk, rows_pair of phase 3, epilogue_logdet and the kept-path count: k7_rate_body.h, shared with the other
+//          consumers.  The array tables of phase 1 are this file's own statement of fill_array_table's body.
 
 // sweeps of the Jacobi iteration per m (index 0 unused)
 constexpr int SWEEPS[9] = {0, 0, 2, 5, 6, 6, 7, 8, 8};
@@ -238,8 +239,7 @@ __global__ __launch_bounds__(256) void k7_rate(WsView ws, RateArgs a, float* __r
     const int L = vo.L;
     float2* os = EPI == EPI_VECTORS && vo.small_side ? vo.small_side + (size_t)ul * K * L * M : nullptr;   // [K][L][M]
     float2* ob = EPI == EPI_VECTORS && vo.big ? vo.big + (size_t)ul * K * L * Mb : nullptr;                // [K][L][Mb]
-    int n = __builtin_amdgcn_readfirstlane(ws.n_keep[u]);
-    n = n < ld ? n : ld;
+    const int n = kept_paths(ws, u);
     if (n <= 0) {                                                            // no kept path: +0.0 everywhere
         if (ok) for (int i = lane; i < K; i += 64) ok[i] = 0.f;
         if (og) for (int i = lane; i < K * M; i += 64) og[i] = 0.f;
@@ -272,15 +272,7 @@ __global__ __launch_bounds__(256) void k7_rate(WsView ws, RateArgs a, float* __r
         const int kn = K - k0 < kc ? K - k0 : kc;
         // 2  w of the chunk
         wave_lds_fence();                                                    // the last chunk's reads before this chunk's writes
-        for (int i = lane; i < n * kn; i += 64) {
-            const int l = i / kn, k = i - l * kn;
-            float s, c;
-            // the fractional part of the EXACT product x * k (k2_small_body.h)
-            const double x = (double)rec.dn(l) * a.inv_n, kd = (double)a.sc[k0 + k];
-            sincos_rev((float)__builtin_fma(x, kd, -rint(x * kd)), s, c);
-            const float cr = rec.c_re(l) * a.scale, ci = rec.c_im(l) * a.scale;
-            w[l * kc + k] = make_float2(fmaf(cr, c, ci * s), fmaf(ci, c, -(cr * s)));     // c_l (cos - j sin)
-        }
+        fill_w_chunk(w, rec, a.sc, k0, a.inv_n, a.scale, n, kn, kc, lane);
         wave_lds_fence();
 
         // 3  this lane's share of the upper triangle of G
@@ -461,8 +453,7 @@ static int launch_rate_epi(const dmx_params& prm, const WsView& ws, int64_t user
     a.small_mh = rx_small ? prm.ue_shape[0] : prm.bs_shape[0];
     a.small_is_rx = rx_small ? 1 : 0;
     a.K = prm.n_selected; a.kc = a.K < 64 ? a.K : 64;
-    a.log2_S = 0;                                                            // the largest power of two with K S <= 64, S <= M_big
-    while (a.K * (2 << a.log2_S) <= 64 && (2 << a.log2_S) <= a.m_big) ++a.log2_S;
+    a.log2_S = gram_slices_log2(a.K, a.m_big);
     a.S = 1 << a.log2_S;
     a.sc = prm.selected_subcarriers;
     a.inv_n = 1.0 / (double)prm.n_subcarriers;

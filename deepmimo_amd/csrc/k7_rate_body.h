@@ -1,14 +1,82 @@
-// Bodies the rate kernels share: k7_rate.hip (one link, white noise) and k8_cell_rate.hip (several links, the other cells'
-// signals as coloured noise) run the same products and the same elimination on one wave's LDS tables, so that a single link
-// gives the same bits through either kernel.
-//   rows_pair         3  h_i[t] of two large-array elements for a lane's subcarrier
+// Bodies the one-wave-per-user consumers of the path records share: k7_rate.hip, k8_cell_rate.hip, k9_angle_delay.hip and
+// k10_codebook_rate.hip run the same table fills, products and elimination on one wave's LDS tables,
+// so that one link gives the same bits through k7_rate and k8_cell_rate, and a single subband the bits of the wideband
+// codebook rate.  By phase, as the kernels' headers number them (k7_rate.hip's numbers; where another kernel's differ
+// they follow in brackets):
+//   kept_paths        0  the user's kept-path count, wave-uniform, at most P
+//   fill_array_table  1  rows of an array's steering table, a[t][l] = exp(j 2pi ((t % mh) y_l + (t / mh) z_l))   [k9: 1, 2']
+//                        (k8, k9, k10; k7_rate.hip keeps its own two loops of the same expression)
+//   fill_w_chunk      2  a chunk of w[l][k] = scale c_l exp(-j 2pi dn_l sc_k / N), path-major
+//   copy_rows_to_lds  -  a chunk of rows of k2b_beam_project's row table, HBM to LDS                              [k9: 2', k10: 3]
+//   rows_pair         3  h_i[t] of two large-array elements for a lane's subcarrier                               [k10: 4]
 //   epilogue_logdet   4  log2 det(I + G) from the pivots of an elimination on the upper triangle
+// Host: gram_slices_log2, the slice rule of phase 3.
 // Tables of one wave (k7_rate.hip has the layout): as [M][ld] the Gram side, ab [Mb][ld] the other array, w [ld][kc]
-// path-major.  fp32, every sum in the order written here.
+// path-major.  fp32, every sum in the order written here.  The callers fence the wave's LDS (wave_lds_fence) between a
+// fill and the reads of it; nothing here does.
 #pragma once
+#include "dmx_common.h"
+#include "k2_small_body.h"
 #include <hip/hip_runtime.h>
 
 namespace dmx {
+
+// 3  log2 of the slices of the large array per subcarrier: the largest power of two S with K S <= 64 and S <= M_big
+__host__ inline int gram_slices_log2(const int K, const int m_big) {
+    int log2_S = 0;
+    while (K * (2 << log2_S) <= 64 && (2 << log2_S) <= m_big) ++log2_S;
+    return log2_S;
+}
+
+// 0  kept paths of user u: one scalar for the wave, at most the P slots of a record row
+__device__ __forceinline__ int kept_paths(const WsView& ws, const int64_t u) {
+    const int n = __builtin_amdgcn_readfirstlane(ws.n_keep[u]);
+    return n < ws.P ? n : ws.P;
+}
+
+// 1  rows row0 .. row0 + rows of the steering table of the UE (rx) or the BS array, first panel dimension mh, for the first
+//    n paths: tab[t][l], t from 0.  float64 phase, reduced to a revolution before the float32 sincos.
+__device__ __forceinline__ void fill_array_table(float2* tab, const WsRecords& rec, const bool rx, const int row0, const int rows,
+                                                 const int mh, const int n, const int ld, const int lane) {
+    for (int i = lane; i < rows * n; i += 64) {
+        const int t = i / n, l = i - t * n, e = row0 + t;
+        const double sy = rx ? rec.rx_y(l) : rec.tx_y(l), sz = rx ? rec.rx_z(l) : rec.tx_z(l);
+        float s, c;
+        sincos_rev(frac_rev(__builtin_fma((double)(e % mh), sy, (double)(e / mh) * sz)), s, c);
+        tab[t * ld + l] = make_float2(c, s);
+    }
+}
+
+// 2  w[l][k] = scale c_l exp(-j 2pi dn_l sc[k0 + k] / N) for the first n paths and the kn subcarriers from position k0, row
+//    stride kc
+__device__ __forceinline__ void fill_w_chunk(float2* w, const WsRecords& rec, const int32_t* sc, const int k0, const double inv_n,
+                                             const float scale, const int n, const int kn, const int kc, const int lane) {
+    for (int i = lane; i < n * kn; i += 64) {
+        const int l = i / kn, k = i - l * kn;
+        float s, c;
+        // the fractional part of the EXACT product x * k (k2_small_body.h)
+        const double x = (double)rec.dn(l) * inv_n, kd = (double)sc[k0 + k];
+        sincos_rev((float)__builtin_fma(x, kd, -rint(x * kd)), s, c);
+        const float cr = rec.c_re(l) * scale, ci = rec.c_im(l) * scale;
+        w[l * kc + k] = make_float2(fmaf(cr, c, ci * s), fmaf(ci, c, -(cr * s)));     // c_l (cos - j sin)
+    }
+}
+
+// cnt values from src + off to dst, one contiguous block on both sides; by 16 bytes where the offset is even (src is 16-byte
+// aligned)
+__device__ __forceinline__ void copy_rows_to_lds(float2* dst, const float2* src, const size_t off, const int cnt, const int lane) {
+    src += off;
+    if ((off & 1) == 0) {
+        const float4* s4 = reinterpret_cast<const float4*>(src);
+        for (int i = lane; i < cnt / 2; i += 64) {
+            const float4 v = s4[i];
+            dst[2 * i] = make_float2(v.x, v.y); dst[2 * i + 1] = make_float2(v.z, v.w);
+        }
+        if ((cnt & 1) && lane == 0) dst[cnt - 1] = src[cnt - 1];
+    } else {
+        for (int i = lane; i < cnt; i += 64) dst[i] = src[i];
+    }
+}
 
 // 4  pivots of I + G by elimination on the upper triangle, each clamped to >= 1: log2 det(I + G)
 template <int M>

@@ -51,6 +51,8 @@ struct CellArgs {
     CellLink link[DMX_MAX_LINKS];
 };
 
+// 1, 2, 4  the table fills, rows_pair of phase 3 and epilogue_logdet: k7_rate_body.h, shared with k7_rate.hip
+
 // 3  slice sl of S of the large array (t = sl, sl + S, ...) for this lane's subcarrier, added to the upper triangle in gr, gi
 template <int M>
 __device__ __forceinline__ void gram_accumulate(const float2* as, const float2* ab, const float2* wk, const int ld, const int kc,
@@ -117,8 +119,7 @@ __global__ __launch_bounds__(256) void k8_cell_rate(CellArgs a, const int32_t* _
     bool any = false;
     for (int b = 0; b < B; ++b) {
         const WsView& ws = a.link[b].ws;
-        int n = __builtin_amdgcn_readfirstlane(ws.n_keep[u]);
-        n = n < ws.P ? n : ws.P;
+        const int n = kept_paths(ws, u);
         float p = 0.f;
         if (lane < n) {                                                      // P <= 32: a lane per path
             const float cr = ws.c_re[(size_t)u * ws.P + lane], ci = ws.c_im[(size_t)u * ws.P + lane];
@@ -135,10 +136,7 @@ __global__ __launch_bounds__(256) void k8_cell_rate(CellArgs a, const int32_t* _
     if (s < 0 || s >= B) s = -1;
     if (out_serving && lane == 0) out_serving[ul] = s;
     int n_s = 0;
-    if (s >= 0) {
-        n_s = __builtin_amdgcn_readfirstlane(a.link[s].ws.n_keep[u]);
-        n_s = n_s < a.link[s].ws.P ? n_s : a.link[s].ws.P;
-    }
+    if (s >= 0) n_s = kept_paths(a.link[s].ws, u);
     if (n_s <= 0) {                                                          // not served, or no kept path to be served by
         if (ok) for (int i = lane; i < K; i += 64) ok[i] = 0.f;
         if (lane == 0) out_rate[ul] = 0.f;
@@ -154,8 +152,7 @@ __global__ __launch_bounds__(256) void k8_cell_rate(CellArgs a, const int32_t* _
         for (int b = 0; b < B; ++b) {
             const CellLink& lk = a.link[b];
             const int ld = lk.ws.P, Mb = lk.m_tx;
-            int n = __builtin_amdgcn_readfirstlane(lk.ws.n_keep[u]);
-            n = n < ld ? n : ld;
+            const int n = kept_paths(lk.ws, u);
             if (n <= 0) continue;                                            // this link does not reach the user
             const WsRecords rec{lk.ws, (size_t)u * ld};
             float2* ab = as + (size_t)M * ld;                                // [Mb][ld]
@@ -163,31 +160,11 @@ __global__ __launch_bounds__(256) void k8_cell_rate(CellArgs a, const int32_t* _
             wave_lds_fence();                                                // the last link's reads before this link's writes
             // 1  array tables of this link
             if (B > 1 || k0 == 0) {
-                for (int i = lane; i < M * n; i += 64) {
-                    const int t = i / n, l = i - t * n;
-                    const double sy = rec.rx_y(l), sz = rec.rx_z(l);
-                    float sn, c;
-                    sincos_rev(frac_rev(__builtin_fma((double)(t % a.rx_mh), sy, (double)(t / a.rx_mh) * sz)), sn, c);
-                    as[t * ld + l] = make_float2(c, sn);
-                }
-                for (int i = lane; i < Mb * n; i += 64) {
-                    const int t = i / n, l = i - t * n;
-                    const double sy = rec.tx_y(l), sz = rec.tx_z(l);
-                    float sn, c;
-                    sincos_rev(frac_rev(__builtin_fma((double)(t % lk.tx_mh), sy, (double)(t / lk.tx_mh) * sz)), sn, c);
-                    ab[t * ld + l] = make_float2(c, sn);
-                }
+                fill_array_table(as, rec, true, 0, M, a.rx_mh, n, ld, lane);
+                fill_array_table(ab, rec, false, 0, Mb, lk.tx_mh, n, ld, lane);
             }
             // 2  w of the chunk
-            for (int i = lane; i < n * kn; i += 64) {
-                const int l = i / kn, k = i - l * kn;
-                float sn, c;
-                // the fractional part of the EXACT product x * k (k2_small_body.h)
-                const double x = (double)rec.dn(l) * a.inv_n, kd = (double)a.sc[k0 + k];
-                sincos_rev((float)__builtin_fma(x, kd, -rint(x * kd)), sn, c);
-                const float cr = rec.c_re(l) * lk.scale, ci = rec.c_im(l) * lk.scale;
-                w[l * kc + k] = make_float2(fmaf(cr, c, ci * sn), fmaf(ci, c, -(cr * sn)));   // c_l (cos - j sin)
-            }
+            fill_w_chunk(w, rec, a.sc, k0, a.inv_n, lk.scale, n, kn, kc, lane);
             wave_lds_fence();
 
             // 3  this lane's share of the upper triangle of the link's Gram, lane = k S + slice
@@ -281,8 +258,7 @@ int launch_cell_rate(const dmx_link* links, int n_links, int64_t n_ue, int64_t u
         ws_carve(const_cast<void*>(src.workspace), n_ue, link_paths(src), &lk.ws);
         lk.m_tx = prm.bs_shape[0] * prm.bs_shape[1];
         lk.tx_mh = prm.bs_shape[0];
-        lk.log2_S = 0;                                                       // the largest power of two with K S <= 64, S <= M_tx
-        while (a.K * (2 << lk.log2_S) <= 64 && (2 << lk.log2_S) <= lk.m_tx) ++lk.log2_S;
+        lk.log2_S = gram_slices_log2(a.K, lk.m_tx);
         lk.S = 1 << lk.log2_S;
         lk.scale = (float)sqrt(src.snr_linear / (double)lk.m_tx);
         lk.snr = src.snr_linear;

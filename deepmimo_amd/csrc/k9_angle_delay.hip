@@ -67,8 +67,7 @@ __global__ __launch_bounds__(256) void k9_angle_delay(WsView ws, AdArgs a, float
     float2* w = ab + (size_t)rc * ld;                                                // [ld][tc]
     const int64_t u = a.user_begin + ul;
     float2* o = out + (size_t)ul * M * R * T;                                        // [M][R][T]
-    int n = __builtin_amdgcn_readfirstlane(ws.n_keep[u]);
-    n = n < ld ? n : ld;
+    const int n = kept_paths(ws, u);
     if (n <= 0) {                                                            // no kept path: +0.0 everywhere
         for (size_t i = lane; i < (size_t)M * R * T; i += 64) o[i] = make_float2(0.f, 0.f);
         return;
@@ -76,12 +75,7 @@ __global__ __launch_bounds__(256) void k9_angle_delay(WsView ws, AdArgs a, float
     const WsRecords rec{ws, (size_t)u * ws.P};
 
     // 1  the a_rx table
-    for (int i = lane; i < M * n; i += 64) {
-        const int t = i / n, l = i - t * n;
-        float s, c;
-        sincos_rev(frac_rev(__builtin_fma((double)(t % a.ue_mh), rec.rx_y(l), (double)(t / a.ue_mh) * rec.rx_z(l))), s, c);
-        as[t * ld + l] = make_float2(c, s);
-    }
+    fill_array_table(as, rec, true, 0, M, a.ue_mh, n, ld, lane);
 
     // D  this lane's path (lanes >= n hold path n - 1 again and are never asked)
     cd e1b, ekb;
@@ -135,26 +129,9 @@ __global__ __launch_bounds__(256) void k9_angle_delay(WsView ws, AdArgs a, float
             // 2' rows r0 .. r0 + nr of the row table
             wave_lds_fence();
             if (a.ftab) {                                                    // [nr][P] is one contiguous block on both sides
-                const size_t off = ((size_t)ul * R + r0) * ld;
-                const float2* src = a.ftab + off;
-                const int cnt = nr * ld;
-                if ((off & 1) == 0) {
-                    const float4* s4 = reinterpret_cast<const float4*>(src);
-                    for (int i = lane; i < cnt / 2; i += 64) {
-                        const float4 v = s4[i];
-                        ab[2 * i] = make_float2(v.x, v.y); ab[2 * i + 1] = make_float2(v.z, v.w);
-                    }
-                    if ((cnt & 1) && lane == 0) ab[cnt - 1] = src[cnt - 1];
-                } else {
-                    for (int i = lane; i < cnt; i += 64) ab[i] = src[i];
-                }
+                copy_rows_to_lds(ab, a.ftab, ((size_t)ul * R + r0) * ld, nr * ld, lane);
             } else {
-                for (int i = lane; i < nr * n; i += 64) {
-                    const int t = i / n, l = i - t * n, tx = r0 + t;
-                    float s, c;
-                    sincos_rev(frac_rev(__builtin_fma((double)(tx % a.bs_mh), rec.tx_y(l), (double)(tx / a.bs_mh) * rec.tx_z(l))), s, c);
-                    ab[t * ld + l] = make_float2(c, s);
-                }
+                fill_array_table(ab, rec, false, r0, nr, a.bs_mh, n, ld, lane);
             }
             wave_lds_fence();
 

@@ -64,6 +64,9 @@ def test_library_exports_the_symbols_with_abi_3():
 def test_kernel_source_has_a_flat_grid_and_shares_the_body():
     src = open(os.path.join(ROOT, "deepmimo_amd", "csrc", "k9_angle_delay.hip")).read()
     assert '#include "k7_rate_body.h"' in src and "rows_pair<M>" in src
+    body = open(os.path.join(ROOT, "deepmimo_amd", "csrc", "k7_rate_body.h")).read()
+    assert src.count("fill_array_table(") == 2 and src.count("copy_rows_to_lds(") == 1 and src.count("kept_paths(") == 1
+    assert "void fill_array_table(" in body and "void copy_rows_to_lds(" in body and "frac_rev" in body and "frac_rev" not in src
     code = "\n".join(line.split("//")[0] for line in src.splitlines())                 # comments say what it does not do
     assert "__syncthreads" not in code and "atomic" not in code.lower() and "blockIdx.y" not in code
     assert "k9_angle_delay.hip" in open(os.path.join(ROOT, "deepmimo_amd", "csrc", "Makefile")).read()

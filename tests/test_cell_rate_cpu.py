@@ -366,7 +366,12 @@ def test_kernel_source_has_a_flat_grid_and_shares_the_header():
     k7 = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "k7_rate.hip")).read())
     body = open(os.path.join(csrc, "k7_rate_body.h")).read()
     assert '#include "k7_rate_body.h"' in k7
-    for fn in ("void rows_pair(", "float epilogue_logdet("):                  # defined once, in the shared header
-        assert fn in body and fn not in k7 and fn not in code
+    for fn in ("void rows_pair(", "float epilogue_logdet(", "void fill_array_table(", "void fill_w_chunk(", "void copy_rows_to_lds(",
+               "int kept_paths(", "int gram_slices_log2("):                                # defined once, in the shared header
+        assert body.count(fn) == 1 and fn not in k7 and fn not in code, fn
+    for call in ("fill_w_chunk(", "kept_paths(", "gram_slices_log2("):
+        assert call in k7 and call in code, call
+    assert code.count("fill_array_table(") == 2 and "fill_array_table(" not in k7         # k7 keeps its own two table loops
+    assert "sincos_rev" in body and "sincos_rev" not in code and "frac_rev" not in code
     mk = open(os.path.join(csrc, "Makefile")).read()
     assert "k8_cell_rate.hip" in mk and "k7_rate_body.h" in mk

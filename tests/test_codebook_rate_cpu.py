@@ -322,5 +322,9 @@ def test_kernel_source_has_a_flat_grid_and_shares_the_headers():
     assert "gridDim" not in code and "__syncthreads" not in code and "atomic" not in code and "asm" not in code
     assert '#include "k7_rate_body.h"' in code and '#include "dmx_common.h"' in code
     assert "rows_pair<M>" in code and "epilogue_logdet<L>" in code and "launch_beam_project" in code
+    body = open(os.path.join(ROOT, "deepmimo_amd", "csrc", "k7_rate_body.h")).read()
+    for call in ("fill_array_table(", "fill_w_chunk(", "copy_rows_to_lds(", "kept_paths("):
+        assert code.count(call) == 1 and body.count("void " + call) + body.count("int " + call) == 1, call
+    assert "sincos_rev" in body and "sincos_rev" not in code and "frac_rev" not in code
     assert "wave_lds_fence" in code and "launch_dyn_lds" in code and "lds_waves_per_block" in code
     assert "k10_codebook_rate.hip" in open(os.path.join(ROOT, "deepmimo_amd", "csrc", "Makefile")).read()

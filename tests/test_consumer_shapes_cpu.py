@@ -68,7 +68,7 @@ def test_rate_launch_rule_and_the_text_of_k7_and_k8():
     _has(body, "a.small_mh = rx_small ? prm.ue_shape[0] : prm.bs_shape[0];")
     _has(body, "a.small_is_rx = rx_small ? 1 : 0;")
     _has(body, "a.K = prm.n_selected; a.kc = a.K < 64 ? a.K : 64;")
-    _has(body, "while (a.K * (2 << a.log2_S) <= 64 && (2 << a.log2_S) <= a.m_big) ++a.log2_S;")
+    _has(body, "a.log2_S = gram_slices_log2(a.K, a.m_big);")
     _has(body, "a.S = 1 << a.log2_S;")
     _has(k7, "const int kl = lane >> a.log2_S, sl = lane & (S - 1);")
     _has(k7, "for (int t = sl; t < Mb; t += 2 * S) {")
@@ -78,12 +78,53 @@ def test_rate_launch_rule_and_the_text_of_k7_and_k8():
     _has(k7, "if (two && vo.vec16) {")
     _has(k7, "vo.vec16 = (rx_small ? m_tx : m_rx) % 2 == 0 && ((uintptr_t)vo.big & 15u) == 0;")
     _has(k7, "sincos_rev(frac_rev(__builtin_fma((double)(t % a.small_mh), sy, (double)(t / a.small_mh) * sz)), s, c);")
+    _has(k7, "sincos_rev(frac_rev(__builtin_fma((double)(t % a.big_mh), sy, (double)(t / a.big_mh) * sz)), s, c);")
     _has(k7, "epilogue_vectors<M>(gr, gi, d, xr, xi, a.small_is_rx ? 1.f : -1.f);")
     _has(k7, "const float hs = a.small_is_rx ? -1.f : 1.f;")
     k8 = _text("k8_cell_rate.hip")
-    _has(k8, "while (a.K * (2 << lk.log2_S) <= 64 && (2 << lk.log2_S) <= lk.m_tx) ++lk.log2_S;")
+    _has(k8, "lk.log2_S = gram_slices_log2(a.K, lk.m_tx);")
+    _has(k8, "lk.S = 1 << lk.log2_S;")
     _has(k8, "for (int t = sl; t < Mb; t += 2 * S) {")
     _has(k8, "const bool two = t + S < Mb;")
+    # the bodies both kernels run live once, in the shared header, and nowhere else
+    shared = _text("k7_rate_body.h")
+    moved = ("while (K * (2 << log2_S) <= 64 && (2 << log2_S) <= m_big) ++log2_S;",
+             "const double sy = rx ? rec.rx_y(l) : rec.tx_y(l), sz = rx ? rec.rx_z(l) : rec.tx_z(l);",
+             "sincos_rev(frac_rev(__builtin_fma((double)(e % mh), sy, (double)(e / mh) * sz)), s, c);",
+             "const double x = (double)rec.dn(l) * inv_n, kd = (double)sc[k0 + k];",
+             "w[l * kc + k] = make_float2(fmaf(cr, c, ci * s), fmaf(ci, c, -(cr * s)));",
+             "const int n = __builtin_amdgcn_readfirstlane(ws.n_keep[u]);",
+             "const float4* s4 = reinterpret_cast<const float4*>(src);")
+    for literal in moved:
+        _has(shared, literal)
+    _has(shared, "const int t = i / n, l = i - t * n, e = row0 + t;")
+    kernels = {k: _code(k + ".hip") for k in ("k7_rate", "k8_cell_rate", "k9_angle_delay", "k10_codebook_rate")}
+    for name, code in kernels.items():
+        assert '#include "k7_rate_body.h"' in code, name
+        for literal in moved:
+            assert literal not in code, (name, literal)
+        for token in ("frac_rev", "n_keep[u]", "const float4*"):
+            assert token not in code or (name, token) == ("k7_rate", "frac_rev"), (name, token)    # k7 keeps its two array tables
+    # calls per kernel: table fills, w chunks, row-table copies, kept-path counts, the slice rule
+    calls = {"fill_array_table(": (0, 2, 2, 1), "fill_w_chunk(": (1, 1, 0, 1), "copy_rows_to_lds(": (0, 0, 1, 1),
+             "kept_paths(": (1, 3, 1, 1), "gram_slices_log2(": (1, 1, 0, 0)}
+    for token, counts in calls.items():
+        for (name, code), count in zip(kernels.items(), counts):
+            _has(code, token, count)
+    _has(k8, "fill_array_table(as, rec, true, 0, M, a.rx_mh, n, ld, lane);")
+    _has(k8, "fill_array_table(ab, rec, false, 0, Mb, lk.tx_mh, n, ld, lane);")
+    _has(k8, "if (kl < kn) gram_accumulate<M>(as, ab, w + kl, ld, kc, n, Mb, sl, lk.S, gr, gi);")
+    # the subcarriers go in as (sc, k0): the chunk's base is added in the index, not in the pointer
+    for name in ("k7_rate", "k8_cell_rate", "k10_codebook_rate"):
+        _has(kernels[name], "fill_w_chunk(w, rec, a.sc, k0, a.inv_n, ")
+    # phase 3's Gram and the xor tree over the slices stay in both kernels: the same text, inline in k7, two functions in k8
+    for text in (k7, k8):
+        _has(text, "rows_pair<M>(as, b0, b1, wk, ld, kc, n, h0, h1);", 2 if text is k7 else 1)
+        _has(text, "r = fmaf(h1[i].x, h1[j].x, fmaf(h1[i].y, h1[j].y, r));")
+        _has(text, "im = fmaf(h1[i].y, h1[j].x, fmaf(-h1[i].x, h1[j].y, im));")
+        _has(text, "for (int d = 1; d < S; d <<= 1) {")
+        _has(text, "gr[i * M + j] += __shfl_xor(gr[i * M + j], d, 64);")
+        _has(text, "if (j > i) gi[i * M + j] += __shfl_xor(gi[i * M + j], d, 64);")
     # the rule at its edges
     assert S.gram_order([4, 2], [3, 1]) == (3, 1, 3, 8, 4) and S.gram_order([3, 2], [7, 1]) == (6, 0, 3, 7, 7)
     assert S.gram_order([2, 2], [2, 2]) == (4, 1, 2, 4, 2)                    # a tie: the UE array
@@ -114,7 +155,17 @@ def test_codebook_and_angle_delay_launch_rules_and_their_text():
     _has(k9, "a.n_taps = n_taps; a.tc = n_taps < 64 ? n_taps : 64;")
     _has(k9, "while ((1 << a.log2_tcp) < a.tc) ++a.log2_tcp;")
     _has(k9, "a.S = 64 / a.tcp;")
-    _has(k9, "sincos_rev(frac_rev(__builtin_fma((double)(tx % a.bs_mh), rec.tx_y(l), (double)(tx / a.bs_mh) * rec.tx_z(l))), s, c);")
+    # the BS-row chunk of the antenna-domain form: rows r0 .. r0 + nr of the shared table body, the UE table from row 0
+    _has(k9, "fill_array_table(ab, rec, false, r0, nr, a.bs_mh, n, ld, lane);")
+    _has(k9, "fill_array_table(as, rec, true, 0, M, a.ue_mh, n, ld, lane);")
+    _has(k9, "copy_rows_to_lds(ab, a.ftab, ((size_t)ul * R + r0) * ld, nr * ld, lane);")
+    _has(k10, "fill_array_table(as, rec, true, 0, M, a.ue_mh, n, ld, lane);")
+    _has(k10, "copy_rows_to_lds(ab, a.ftab, ((size_t)ul * rows_all + (size_t)c0 * L) * ld, nc * L * ld, lane);")
+    shared = _text("k7_rate_body.h")
+    _has(shared, "const int t = i / n, l = i - t * n, e = row0 + t;")
+    _has(shared, "sincos_rev(frac_rev(__builtin_fma((double)(e % mh), sy, (double)(e / mh) * sz)), s, c);")
+    _has(shared, "tab[t * ld + l] = make_float2(c, s);")
+    assert "frac_rev" not in _code("k9_angle_delay.hip") and "frac_rev" not in _code("k10_codebook_rate.hip")
     assert S.ad_launch(32) == dict(tc=32, tcp=32, S=2) and S.ad_launch(33) == dict(tc=33, tcp=64, S=1)
     assert S.ad_launch(1) == dict(tc=1, tcp=1, S=64) and S.ad_launch(128) == dict(tc=64, tcp=64, S=1)
 

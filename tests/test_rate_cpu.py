@@ -266,4 +266,8 @@ def test_kernel_source_has_a_flat_grid_and_shares_the_headers():
     assert "gridDim" not in code and "__syncthreads" not in code and "atomic" not in code and "asm" not in code
     assert '#include "k2_small_body.h"' in code and '#include "dmx_common.h"' in code
     assert "wave_lds_fence" in code and "sincos_rev" in code and "launch_dyn_lds" in code and "lds_waves_per_block" in code
+    # the w chunk and the kept-path count are the shared header's; the two array tables stay here (sincos_rev above)
+    body = open(os.path.join(ROOT, "deepmimo_amd", "csrc", "k7_rate_body.h")).read()
+    assert '#include "k7_rate_body.h"' in code and code.count("fill_w_chunk(") == 1 and code.count("kept_paths(") == 1
+    assert "void fill_w_chunk(" in body and "int kept_paths(" in body and code.count("sincos_rev") == 2 and "rint(" not in code
     assert "k7_rate.hip" in open(os.path.join(ROOT, "deepmimo_amd", "csrc", "Makefile")).read()
