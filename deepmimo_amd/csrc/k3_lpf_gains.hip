@@ -159,27 +159,20 @@ __device__ __forceinline__ float2 caddf(float2 a, float2 b) { const kv2 r = kv2{
 __device__ __forceinline__ float2 csubf(float2 a, float2 b) { const kv2 r = kv2{a.x, a.y} - kv2{b.x, b.y}; return make_float2(r[0], r[1]); }
 __device__ __forceinline__ float2 mul_mi(float2 a) { return make_float2(a.y, -a.x); }          // a * (-j)
 
-template <int R> __device__ __forceinline__ void dft_small(float2 (&v)[R]);
-template <> __device__ __forceinline__ void dft_small<2>(float2 (&v)[2]) {
-    const float2 a = v[0], b = v[1];
-    v[0] = caddf(a, b); v[1] = csubf(a, b);
-}
-template <> __device__ __forceinline__ void dft_small<4>(float2 (&v)[4]) {
-    const float2 t0 = caddf(v[0], v[2]), t1 = csubf(v[0], v[2]), t2 = caddf(v[1], v[3]), t3 = mul_mi(csubf(v[1], v[3]));
-    v[0] = caddf(t0, t2); v[1] = caddf(t1, t3); v[2] = csubf(t0, t2); v[3] = csubf(t1, t3);
-}
-template <> __device__ __forceinline__ void dft_small<8>(float2 (&v)[8]) {
-    constexpr float H = 0.70710678118654752f;
-    float2 a[4], b[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { a[k] = caddf(v[k], v[k + 4]); b[k] = csubf(v[k], v[k + 4]); }
-    b[1] = make_float2((b[1].x + b[1].y) * H, (b[1].y - b[1].x) * H);          // * e^{-j pi/4}
-    b[2] = mul_mi(b[2]);                                                       // * e^{-j pi/2}
-    b[3] = make_float2((b[3].y - b[3].x) * H, -(b[3].x + b[3].y) * H);         // * e^{-j 3pi/4}
-    dft_small<4>(a);
-    dft_small<4>(b);
-#pragma unroll
-    for (int m = 0; m < 4; ++m) { v[2 * m] = a[m]; v[2 * m + 1] = b[m]; }
+// Butterflies in place on the points v[t + S r] of a register array, which they take whole and by reference: handed a
+// pointer into it or a copy of the points, the compiler splits every complex value into two scalars and the Doppler
+// kernels of k3_lpf_fft_pow2 need a dozen registers more.
+template <int R, int S = 1, int NV> __device__ __forceinline__ void dft_small(float2 (&v)[NV], int t = 0) {
+    static_assert(R == 2 || R == 4, "radix 2 or 4");
+    float2 &v0 = v[t], &v1 = v[t + S];
+    if constexpr (R == 2) {
+        const float2 a = v0, b = v1;
+        v0 = caddf(a, b); v1 = csubf(a, b);
+    } else {
+        float2 &v2 = v[t + 2 * S], &v3 = v[t + 3 * S];
+        const float2 t0 = caddf(v0, v2), t1 = csubf(v0, v2), t2 = caddf(v1, v3), t3 = mul_mi(csubf(v1, v3));
+        v0 = caddf(t0, t2); v1 = caddf(t1, t3); v2 = csubf(t0, t2); v3 = csubf(t1, t3);
+    }
 }
 
 // Packed-fp32 forms the compiler does not select (it keeps a swizzled copy of every twiddle - 56 registers instead of 28 -
@@ -219,17 +212,17 @@ __device__ __forceinline__ float2 rot3_pk(float2 b) {                        // 
     return make_float2(r[0], r[1]);
 }
 __device__ __forceinline__ float2 cscale(float2 a, float s) { const kv2 r = kv2{a.x, a.y} * s; return make_float2(r[0], r[1]); }
-// radix-8 butterfly, 28 packed instructions (dft_small<8> with the -j factors folded into the additions)
-__device__ __forceinline__ void dft8_pk(float2 (&v)[8]) {
+// radix-8 butterfly, 28 packed instructions (two dft_small<4> behind a radix-2 step, the -j factors folded into the additions)
+template <int S = 1, int NV> __device__ __forceinline__ void dft8_pk(float2 (&v)[NV], int t = 0) {
     constexpr float H = 0.70710678118654752f;
     float2 a[4], b[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { a[k] = caddf(v[k], v[k + 4]); b[k] = csubf(v[k], v[k + 4]); }
+    for (int k = 0; k < 4; ++k) { a[k] = caddf(v[t + S * k], v[t + S * (k + 4)]); b[k] = csubf(v[t + S * k], v[t + S * (k + 4)]); }
     const float2 b1 = cscale(rot1_pk(b[1]), H), b3 = cscale(rot3_pk(b[3]), H);
     const float2 t0 = caddf(a[0], a[2]), t1 = csubf(a[0], a[2]), t2 = caddf(a[1], a[3]), d = csubf(a[1], a[3]);
-    v[0] = caddf(t0, t2); v[2] = cadd_mj(t1, d); v[4] = csubf(t0, t2); v[6] = csub_mj(t1, d);
+    v[t] = caddf(t0, t2); v[t + 2 * S] = cadd_mj(t1, d); v[t + 4 * S] = csubf(t0, t2); v[t + 6 * S] = csub_mj(t1, d);
     const float2 u0 = cadd_mj(b[0], b[2]), u1 = csub_mj(b[0], b[2]), u2 = caddf(b1, b3), e = csubf(b1, b3);
-    v[1] = caddf(u0, u2); v[3] = cadd_mj(u1, e); v[5] = csubf(u0, u2); v[7] = csub_mj(u1, e);
+    v[t + S] = caddf(u0, u2); v[t + 3 * S] = cadd_mj(u1, e); v[t + 5 * S] = csubf(u0, u2); v[t + 7 * S] = csub_mj(u1, e);
 }
 
 // element e of a transform buffer lives at e + e/16: the pad makes the stride-8 writes of the first pass (lane l writes
@@ -257,6 +250,16 @@ __device__ __forceinline__ void fft_pass(const float2* src, float2* dst, const f
 #pragma unroll
         for (int r = 0; r < R; ++r) dst[fpad(j0 + r * Ns)] = v[r];
     }
+}
+
+// the power-of-two operand scale k2_fd_mfma's stage_item derives for a user from its path records, one per lane:
+// max |c| component -> [512, 1024), two more bits of headroom for the sinc sum
+__device__ __forceinline__ float lpf_pack_scale(float cr_l, float ci_l, int lane, int n_keep) {
+    float m = lane < (n_keep < 32 ? n_keep : 32) ? fmaxf(fabsf(cr_l), fabsf(ci_l)) : 0.f;
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    int e;
+    (void)frexpf(m, &e);
+    return ldexpf(1.0f, 8 - e);
 }
 
 __host__ __device__ inline size_t lpf_buf_elems(int N) { return (size_t)N + N / 16 + 1; }
@@ -295,16 +298,7 @@ __global__ __launch_bounds__(256, K3_WAVES_PER_SIMD) void k3_lpf_fft_wave(WsView
         const float dn_l = lok ? ws.dn[rb + lane] : 0.f, cr_l = lok ? ws.c_re[rb + lane] : 0.f, ci_l = lok ? ws.c_im[rb + lane] : 0.f;
         const float dv_l = (lok && a.doppler) ? ws.dop_v[rb + lane] : 0.f, da_l = (lok && a.doppler) ? ws.dop_a[rb + lane] : 0.f;
         const float s0_l = (float)sinpi((double)dn_l);
-        float gsl = 1.0f;
-        if (a.pack) {
-            // the operand scale k2_fd_mfma's stage_item derives for this user: max |c| component -> [512, 1024), two
-            // more bits of headroom for the sinc sum
-            float m = lane < (n_keep < 32 ? n_keep : 32) ? fmaxf(fabsf(cr_l), fabsf(ci_l)) : 0.f;
-            for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-            int e;
-            (void)frexpf(m, &e);
-            gsl = ldexpf(1.0f, 8 - e);
-        }
+        const float gsl = a.pack ? lpf_pack_scale(cr_l, ci_l, lane, n_keep) : 1.0f;
         for (int l = wave; l < n_keep; l += 4) {
             float dnf, cr, ci, s0, dvf, daf;
             if (l < 64) {                                                        // wave-uniform
@@ -354,51 +348,46 @@ __global__ __launch_bounds__(256, K3_WAVES_PER_SIMD) void k3_lpf_fft_wave(WsView
             __builtin_amdgcn_wave_barrier();
             float2* grow = a.gtab + ((size_t)ul * ws.P + l) * a.K;
             uint2* prow = reinterpret_cast<uint2*>(grow);
+            const auto store = [&](int k, float2 g) {                            // a plain store, scaled here (the taps are not)
+                if (a.pack) {
+                    h2 hi, lo;
+                    split2_f16(g.x * gsl, g.y * gsl, hi, lo, ws.neg_one);
+                    prow[k] = make_uint2(__builtin_bit_cast(unsigned, hi), __builtin_bit_cast(unsigned, lo));
+                } else {
+                    grow[k] = g;
+                }
+            };
             if (bins_in_regs) {
 #pragma unroll
                 for (int j = 0; j < NBIN; ++j) {
                     const int k = lane + 64 * j;
-                    if (k < a.K) {
-                        const float2 g = src[binreg[j]];
-                        if (a.pack) {
-                            h2 hi, lo;
-                            split2_f16(g.x * gsl, g.y * gsl, hi, lo, ws.neg_one);
-                            prow[k] = make_uint2(__builtin_bit_cast(unsigned, hi), __builtin_bit_cast(unsigned, lo));
-                        } else {
-                            grow[k] = g;
-                        }
-                    }
+                    if (k < a.K) store(k, src[binreg[j]]);
                 }
             } else {
-                for (int k = lane; k < a.K; k += 64) {
-                    const float2 g = src[fpad(a.sc[k] & (N - 1))];                // N is a power of two: floor-mod
-                    if (a.pack) {
-                        h2 hi, lo;
-                        split2_f16(g.x * gsl, g.y * gsl, hi, lo, ws.neg_one);
-                        prow[k] = make_uint2(__builtin_bit_cast(unsigned, hi), __builtin_bit_cast(unsigned, lo));
-                    } else {
-                        grow[k] = g;
-                    }
-                }
+                for (int k = lane; k < a.K; k += 64) store(k, src[fpad(a.sc[k] & (N - 1))]);   // N is a power of two: floor-mod
             }
         }
     }
 }
 
-// ---- N = 512 (DeepMIMO's default OFDM size), one WAVE per USER -----------------------------------------------------
+// ---- N = 64 ... 1024 (512 is DeepMIMO's default OFDM size), one WAVE per USER --------------------------------------
 // k3_lpf_fft_wave is generic in N and pays for it: 656 vector instructions per transform (profiles/r2_lpf_summary.txt),
-// which is its time (VALU issue 3.2 of 4.3 ms at the headline shape).  With N fixed at 512 = 8^3 and a lane holding the
-// eight points d = lane + 64 r of its transform:
-//   * the taps a lane generates are exactly the eight inputs of ITS butterfly of the first Stockham pass - no LDS round
-//     trip for the taps, and that pass has no twiddles;
-//   * the twiddles of passes 2 and 3 depend on the lane only (exp(-j 2pi (lane & 7) r / 64), exp(-j 2pi lane r / 512)):
-//     28 registers filled once per wave - no table, no lookups, no address arithmetic;
-//   * a wave's reads of a pass are all issued before its writes and LDS serves a wave in order: ONE buffer per wave,
-//     transformed in place;
-//   * the last pass leaves bins lane + 64 r in the lane - when the selected subcarriers are 0 .. K-1 (IDENT) they are
+// which is its time (VALU issue 3.2 of 4.3 ms at the headline shape).  With N a template parameter, LP = min(64, N / 8)
+// lanes transform one path (PW = 64 / LP paths per wave for N < 512) and a lane holds the E = N / LP points j + LP m
+// (j = lane % LP) of its transform - taps in, bins out:
+//   * every Stockham pass reads and writes that pattern.  Passes 1 and 2 are radix 8 (S1 = E / 8 butterflies per lane,
+//     butterfly t on points t + r S1), pass 3 has radix R3 = N / 64 (2, 4: 64 / LP butterflies per lane; 8, 16: one;
+//     N = 64 ends after pass 2).  The taps a lane generates are exactly the inputs of ITS butterflies of pass 1 - no LDS
+//     round trip for the taps, and that pass has no twiddles;
+//   * the twiddles of passes 2 and 3 depend on the lane only (exp(-j 2pi (j & 7) r / 64), exp(-j 2pi (j + LP t) r / N)):
+//     registers filled once per wave - no table, no lookups; the LDS positions are three per-lane pointers plus
+//     compile-time offsets.  N = 512 has one butterfly per lane and pass and nothing indexed;
+//   * a wave's reads of a pass are all issued before its writes and LDS serves a wave in order: ONE buffer per path,
+//     transformed in place, and a write that follows a read in program order needs no fence in between;
+//   * the last pass leaves bins j + LP m in the lane - when the selected subcarriers are 0 .. K-1 (IDENT) they are
 //     scaled, split and stored from registers; other selections go through the buffer once more;
-//   * sin(pi (d - dn)) = -(-1)^d sin(pi dn) and (-1)^d = (-1)^lane for every point of the lane: tap = (c * S) / (d - dn)
-//     with one per-lane S per path, i.e. subtract, reciprocal, one packed multiply per tap;
+//   * sin(pi (d - dn)) = -(-1)^d sin(pi dn) and (-1)^d = (-1)^j for every point of the lane (LP is even):
+//     tap = (c * S) / (d - dn) with one per-lane S per path, i.e. subtract, reciprocal, one packed multiply per tap;
 //   * a wave owns a USER (all its paths in turn): no workgroup barrier, no 7 / 6 / 6 / 6 imbalance of 25 paths over 4 waves.
 //   * Doppler (float64 phases per tap) is its own instantiation: its registers would halve the others' occupancy.
 template <bool PACK>
@@ -413,142 +402,12 @@ __device__ __forceinline__ void store_gain(float2* grow, uint2* prow, int k, flo
         grow[k] = g;
     }
 }
-template <bool IDENT, bool PACK, bool DOPPLER>
-__global__ __launch_bounds__(256) void k3_lpf_fft512(WsView ws, LpfArgs a, int64_t user_count) {
-    constexpr int N = 512;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    float2* X = reinterpret_cast<float2*>(smem) + (size_t)wave * lpf_buf_elems(N);
-    float2 tw2[8], tw3[8];
-#pragma unroll
-    for (int r = 1; r < 8; ++r) {
-        float s, c;
-        sincos_rev(frac_rev(-(double)((lane & 7) * r) / 64.0), s, c);
-        tw2[r] = make_float2(c, s);
-        sincos_rev(frac_rev(-(double)(lane * r) / 512.0), s, c);
-        tw3[r] = make_float2(c, s);
-    }
-    // LDS positions of this lane: pass 1 writes elements 8 lane + r, reads of passes 2 / 3 take lane + 64 r, pass 2
-    // writes 64 (lane >> 3) + (lane & 7) + 8 r (Stockham autosort, see fft_pass)
-    float2* w1 = X + fpad(8 * lane);                       // + r: same pad for all eight
-    float2* rd = X + fpad(lane);                           // + 68 r
-    float2* w2 = X + fpad(64 * (lane >> 3) + (lane & 7));  // + 8 r + (r >> 1): 64 g + k + 8 r has pad 4 g + (k + 8 r) / 16, k < 8
-    const float lanef = (float)lane;
-    const unsigned sgn = (lane & 1) ? 0u : 0x80000000u;    // S = (-1)^d * (-1) * s0: odd d -> +s0, even d -> -s0
-    int binreg[8];
-    if constexpr (!IDENT) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const int k = lane + 64 * j; binreg[j] = k < a.K ? fpad(a.sc[k] & (N - 1)) : 0; }
-    }
-    const int64_t nwaves = (int64_t)gridDim.x * 4;
-    for (int64_t ul = (int64_t)blockIdx.x * 4 + wave; ul < user_count; ul += nwaves) {
-        const int64_t u = a.user_begin + ul;
-        const int n_keep = ws.n_keep[u];
-        const size_t rb = (size_t)u * ws.P;
-        const bool lok = lane < n_keep;
-        const float dn_l = lok ? ws.dn[rb + lane] : 0.f;
-        float cr_l = lok ? ws.c_re[rb + lane] : 0.f, ci_l = lok ? ws.c_im[rb + lane] : 0.f;
-        const float dv_l = (lok && DOPPLER) ? ws.dop_v[rb + lane] : 0.f, da_l = (lok && DOPPLER) ? ws.dop_a[rb + lane] : 0.f;
-        // sin(pi dn) / pi per path, all paths in parallel (float64 sinpi: dn reaches thousands of samples)
-        const float s0_l = (float)(sinpi((double)dn_l) * (1.0 / LPF_PI));
-        if constexpr (PACK) {
-            // the operand scale k2_fd_mfma's stage_item derives for this user: max |c| component -> [512, 1024), two
-            // more bits of headroom for the sinc sum; a power of two, so scaling c instead of G changes nothing
-            float m = lane < (n_keep < 32 ? n_keep : 32) ? fmaxf(fabsf(cr_l), fabsf(ci_l)) : 0.f;
-            for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-            int e;
-            (void)frexpf(m, &e);
-            const float gsl = ldexpf(1.0f, 8 - e);
-            cr_l *= gsl; ci_l *= gsl;
-        }
-        for (int l = 0; l < n_keep; ++l) {
-            const float dnf = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, dn_l), l));
-            const float cr = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cr_l), l));
-            const float ci = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ci_l), l));
-            const unsigned s0b = (unsigned)__builtin_amdgcn_readlane(__builtin_bit_cast(int, s0_l), l);
-            const float S = __builtin_bit_cast(float, s0b ^ sgn);
-            const kv2 cs = kv2{cr * S, ci * S};
-            const float x0 = lanef - dnf;                  // d - dn in float32: exact unless dn is tiny (then 6e-8 relative)
-            float2 v[8];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const kv2 t = cs * __builtin_amdgcn_rcpf(x0 + (float)(64 * r));      // lane + 64 r is exact in float32, so is the sum
-                v[r] = make_float2(t[0], t[1]);
-            }
-            if (dnf == rintf(dnf) && dnf >= 0.f && dnf < (float)N) {                 // wave-uniform: np.sinc(0) = 1; s0 = 0, the other taps are 0
-                const int d0 = (int)dnf;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) v[r] = (lane + 64 * r == d0) ? make_float2(cr, ci) : make_float2(0.f, 0.f);
-            }
-            if constexpr (DOPPLER) {
-                const double dv = (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, dv_l), l));
-                const double da = (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, da_l), l));
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const double tau = a.ts * (double)(lane + 64 * r);
-                    const double rev = -a.fc * (dv * tau / LPF_C0 + da * (tau * tau) / (2.0 * LPF_C0));
-                    float s, c;
-                    sincos_rev(frac_rev(rev), s, c);
-                    v[r] = cmulf(v[r], make_float2(c, s));
-                }
-            }
-            // pass 1 (Ns = 1): no twiddles; element 8 lane + r
-            dft8_pk(v);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) w1[r] = v[r];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            // pass 2 (Ns = 8)
-#pragma unroll
-            for (int r = 0; r < 8; ++r) v[r] = rd[68 * r];
-#pragma unroll
-            for (int r = 1; r < 8; ++r) v[r] = cmul_pk(v[r], tw2[r]);
-            dft8_pk(v);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) w2[8 * r + (r >> 1)] = v[r];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            // pass 3 (Ns = 64): bins lane + 64 r
-#pragma unroll
-            for (int r = 0; r < 8; ++r) v[r] = rd[68 * r];
-#pragma unroll
-            for (int r = 1; r < 8; ++r) v[r] = cmul_pk(v[r], tw3[r]);
-            dft8_pk(v);
-            float2* grow = a.gtab + ((size_t)ul * ws.P + l) * a.K;
-            uint2* prow = reinterpret_cast<uint2*>(grow);
-            if constexpr (!IDENT) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");           // every lane has read its pass-3 inputs
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int r = 0; r < 8; ++r) rd[68 * r] = v[r];
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int r = 0; r < 8; ++r) v[r] = X[binreg[r]];
-            }
-            if (a.K == N) {                                                      // wave-uniform: no per-store guard
-#pragma unroll
-                for (int r = 0; r < 8; ++r) store_gain<PACK>(grow, prow, lane + 64 * r, v[r], ws.neg_one);
-            } else {
-#pragma unroll
-                for (int r = 0; r < 8; ++r)
-                    if (lane + 64 * r < a.K) store_gain<PACK>(grow, prow, lane + 64 * r, v[r], ws.neg_one);
-            }
-            if constexpr (!IDENT) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");           // the gather has read X before the next path's pass 1
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
-    }
+// x of lane src.  One path per wave: src is wave-uniform and the value lands in a scalar register
+template <int PW>
+__device__ __forceinline__ float path_value(float x, int src) {
+    if constexpr (PW == 1) return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), src));
+    else return __shfl(x, src);
 }
-
-// ---- the same scheme for N = 64, 128, 256 and 1024 ------------------------------------------------------------------
-// LP = min(64, N / 8) lanes transform one path (64 / LP paths per wave for N < 512), a lane holds the E = N / LP points
-// j + LP m (j = lane % LP) - taps in, bins out.  Every pass reads and writes that pattern: passes 1 and 2 are radix 8
-// (E / 8 butterflies per lane, butterfly t on points t + r E/8; pass 2's twiddles exp(-j 2pi (j & 7) r / 64)), pass 3
-// has radix N / 64 (2, 4: 64 / LP butterflies per lane; 16 for N = 1024: one) with twiddles exp(-j 2pi (j + LP t) r / N).
-// N = 64 ends after pass 2.  N = 512 keeps its own kernel above (one butterfly per lane and pass, nothing indexed).
 __device__ __forceinline__ void dft16_pk(float2 (&x)[16]) {                  // x[r] -> X[r], 4 x 4
     constexpr float H = 0.70710678118654752f, C1 = 0.92387953251128674f, S1 = 0.38268343236508977f;
     float2 u[4][4];
@@ -584,7 +443,7 @@ __global__ __launch_bounds__(256) void k3_lpf_fft_pow2(WsView ws, LpfArgs a, int
     constexpr int S1 = E / 8;                              // radix-8 butterflies per lane in passes 1 and 2
     constexpr int R3 = N / 64;                             // radix of pass 3 (1 = no pass 3)
     constexpr int S3 = R3 > 1 ? E / R3 : 1;                // its butterflies per lane
-    static_assert(LOG2N >= 6 && LOG2N <= 10 && LOG2N != 9, "N = 64, 128, 256, 1024");
+    static_assert(LOG2N >= 6 && LOG2N <= 10, "N = 64 ... 1024");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -619,8 +478,16 @@ __global__ __launch_bounds__(256) void k3_lpf_fft_pow2(WsView ws, LpfArgs a, int
                 tw3[t * (R3 - 1) + r - 1] = make_float2(c, s);
             }
     }
+    // LDS positions of this lane (Stockham autosort, see fft_pass): pass 1 writes elements 8 b + r (b = j + LP t), every
+    // pass reads elements j + LP m, pass 2 writes 64 (b >> 3) + (b & 7) + 8 r, whose pad is that of r = 0 plus r >> 1.
+    // One path per wave: the pad splits (j < 64, and the offsets are multiples of 64), so an element is a per-lane
+    // pointer plus a compile-time offset - the compiler does not find that split and spends 8 LDS operations and as many
+    // registers more.  Several paths per wave keep fpad() per access
+    const int e1 = 8 * j, e2 = 64 * (j >> 3) + (j & 7);
+    float2* const w1 = X + fpad(e1), * const rd = X + fpad(j), * const w2 = X + fpad(e2);
+    const auto at = [&](float2* p, int e, int off) { if constexpr (PW == 1) return p + fpad(off); else return X + fpad(e + off); };
     const float jf = (float)j;
-    const unsigned sgn = (j & 1) ? 0u : 0x80000000u;       // LP is even: (-1)^d = (-1)^j for every point of the lane
+    const unsigned sgn = (j & 1) ? 0u : 0x80000000u;       // S = (-1)^d * (-1) * s0: odd d -> +s0, even d -> -s0
     int binreg[E];
     if constexpr (!IDENT) {
 #pragma unroll
@@ -635,41 +502,39 @@ __global__ __launch_bounds__(256) void k3_lpf_fft_pow2(WsView ws, LpfArgs a, int
         const float dn_l = lok ? ws.dn[rb + lane] : 0.f;
         float cr_l = lok ? ws.c_re[rb + lane] : 0.f, ci_l = lok ? ws.c_im[rb + lane] : 0.f;
         const float dv_l = (lok && DOPPLER) ? ws.dop_v[rb + lane] : 0.f, da_l = (lok && DOPPLER) ? ws.dop_a[rb + lane] : 0.f;
+        // sin(pi dn) / pi per path, all paths in parallel (float64 sinpi: dn reaches thousands of samples)
         const float s0_l = (float)(sinpi((double)dn_l) * (1.0 / LPF_PI));
         if constexpr (PACK) {
-            float m = lane < (n_keep < 32 ? n_keep : 32) ? fmaxf(fabsf(cr_l), fabsf(ci_l)) : 0.f;
-            for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-            int e;
-            (void)frexpf(m, &e);
-            const float gsl = ldexpf(1.0f, 8 - e);
+            const float gsl = lpf_pack_scale(cr_l, ci_l, lane, n_keep);         // a power of two, so scaling c instead of G changes nothing
             cr_l *= gsl; ci_l *= gsl;
         }
         for (int l0 = 0; l0 < n_keep; l0 += PW) {
             const int l = l0 + g;                          // this lane group's path; groups past n_keep compute zeros and store nothing
-            const bool act = l < n_keep;
+            const bool act = PW == 1 || l < n_keep;
             const int ls = act ? l : 0;
-            // every shuffle outside any `act ? :` - inside, only the active groups' lanes execute it and a source lane in an
-            // idle group (the last path of a user: slot l0 + g >= the active lanes) returns 0
-            const float dnf = __shfl(dn_l, ls), crs = __shfl(cr_l, ls), cis = __shfl(ci_l, ls);
+            // PW > 1: every shuffle outside any `act ? :` - inside, only the active groups' lanes execute it and a source lane
+            // in an idle group (the last path of a user: slot l0 + g >= the active lanes) returns 0
+            const float dnf = path_value<PW>(dn_l, ls), crs = path_value<PW>(cr_l, ls), cis = path_value<PW>(ci_l, ls);
             const float cr = act ? crs : 0.f, ci = act ? cis : 0.f;
-            const float S = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, __shfl(s0_l, ls)) ^ sgn);
+            const float S = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, path_value<PW>(s0_l, ls)) ^ sgn);
             const kv2 cs = kv2{cr * S, ci * S};
-            const float x0 = jf - dnf;
+            const float x0 = jf - dnf;                     // d - dn in float32: exact unless dn is tiny (then 6e-8 relative)
             float2 v[E];
 #pragma unroll
             for (int m = 0; m < E; ++m) {
-                const kv2 t = cs * __builtin_amdgcn_rcpf(x0 + (float)(LP * m));
+                const kv2 t = cs * __builtin_amdgcn_rcpf(x0 + (float)(LP * m));      // j + LP m is exact in float32, so is the sum
                 v[m] = make_float2(t[0], t[1]);
             }
-            const bool whole = dnf == rintf(dnf) && dnf >= 0.f && dnf < (float)N;    // np.sinc(0) = 1: s0 = 0, the other taps 0
-            if (__builtin_amdgcn_ballot_w64(whole) != 0) {
+            // np.sinc(0) = 1: s0 = 0, the other taps are 0.  Wave-uniform with one path per wave, else any group's
+            const bool whole = dnf == rintf(dnf) && dnf >= 0.f && dnf < (float)N;
+            if (PW == 1 ? whole : __builtin_amdgcn_ballot_w64(whole) != 0) {
                 const int d0 = (int)dnf;
 #pragma unroll
                 for (int m = 0; m < E; ++m)
                     if (whole) v[m] = (j + LP * m == d0) ? make_float2(cr, ci) : make_float2(0.f, 0.f);
             }
             if constexpr (DOPPLER) {
-                const double dv = (double)__shfl(dv_l, ls), da = (double)__shfl(da_l, ls);
+                const double dv = (double)path_value<PW>(dv_l, ls), da = (double)path_value<PW>(da_l, ls);
 #pragma unroll
                 for (int m = 0; m < E; ++m) {
                     const double tau = a.ts * (double)(j + LP * m);
@@ -682,67 +547,49 @@ __global__ __launch_bounds__(256) void k3_lpf_fft_pow2(WsView ws, LpfArgs a, int
             // pass 1 (radix 8, no twiddles): butterfly b = j + LP t on points t + r S1 -> elements 8 b + r
 #pragma unroll
             for (int t = 0; t < S1; ++t) {
-                float2 w[8];
+                dft8_pk<S1>(v, t);
+                float2* dst = at(w1, e1, 8 * LP * t);
 #pragma unroll
-                for (int r = 0; r < 8; ++r) w[r] = v[t + r * S1];
-                dft8_pk(w);
-                float2* dst = X + fpad(8 * (j + LP * t));
-#pragma unroll
-                for (int r = 0; r < 8; ++r) dst[r] = w[r];
+                for (int r = 0; r < 8; ++r) dst[r] = v[t + r * S1];
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
             __builtin_amdgcn_wave_barrier();
             // pass 2 (radix 8, Ns = 8): elements b + r N/8 = j + LP (t + r S1) -> 64 (b >> 3) + (b & 7) + 8 r
 #pragma unroll
-            for (int m = 0; m < E; ++m) v[m] = X[fpad(j + LP * m)];
+            for (int m = 0; m < E; ++m) v[m] = *at(rd, j, LP * m);
 #pragma unroll
             for (int t = 0; t < S1; ++t) {
-                float2 w[8];
-                w[0] = v[t];
 #pragma unroll
-                for (int r = 1; r < 8; ++r) w[r] = cmul_pk(v[t + r * S1], tw2[r]);
-                dft8_pk(w);
-                const int b = j + LP * t;
-                float2* dst = X + fpad(64 * (b >> 3) + (b & 7));
+                for (int r = 1; r < 8; ++r) v[t + r * S1] = cmul_pk(v[t + r * S1], tw2[r]);
+                dft8_pk<S1>(v, t);
+                float2* dst = at(w2, e2, 8 * LP * t);
 #pragma unroll
-                for (int r = 0; r < 8; ++r) dst[8 * r + (r >> 1)] = w[r];
+                for (int r = 0; r < 8; ++r) dst[8 * r + (r >> 1)] = v[t + r * S1];
             }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            // pass 3 (radix R3, Ns = 64): elements b + 64 r = j + LP (t + r S3) -> bins b + 64 r, the same pattern.
+            // N = 64: pass 2 already wrote bins j + 8 r in order; this fetches them back into the lane pattern
+#pragma unroll
+            for (int m = 0; m < E; ++m) v[m] = *at(rd, j, LP * m);
             if constexpr (R3 > 1) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-                __builtin_amdgcn_wave_barrier();
-                // pass 3 (radix R3, Ns = 64): elements b + 64 r = j + LP (t + r S3) -> bins b + 64 r, the same pattern
 #pragma unroll
-                for (int m = 0; m < E; ++m) v[m] = X[fpad(j + LP * m)];
-                if constexpr (R3 == 16) {
-                    float2 w[16];
-                    w[0] = v[0];
+                for (int t = 0; t < S3; ++t) {
 #pragma unroll
-                    for (int r = 1; r < 16; ++r) {
-                        const float2 lo = tw3[(r & 3) - 1 < 0 ? 0 : (r & 3) - 1], hi = tw3[2 + (r >> 2)];
-                        float2 tw = (r & 3) == 0 ? hi : ((r >> 2) == 0 ? lo : cmul_pk(hi, lo));
-                        w[r] = cmul_pk(v[r], tw);
+                    for (int r = 1; r < R3; ++r) {
+                        float2 tw;
+                        if constexpr (R3 == 16) {
+                            const float2 lo = tw3[(r & 3) - 1 < 0 ? 0 : (r & 3) - 1], hi = tw3[2 + (r >> 2)];
+                            tw = (r & 3) == 0 ? hi : ((r >> 2) == 0 ? lo : cmul_pk(hi, lo));
+                        } else {
+                            tw = tw3[t * (R3 - 1) + r - 1];
+                        }
+                        v[t + r * S3] = cmul_pk(v[t + r * S3], tw);
                     }
-                    dft16_pk(w);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) v[r] = w[r];
-                } else {
-#pragma unroll
-                    for (int t = 0; t < S3; ++t) {
-                        float2 w[R3];
-                        w[0] = v[t];
-#pragma unroll
-                        for (int r = 1; r < R3; ++r) w[r] = cmul_pk(v[t + r * S3], tw3[t * (R3 - 1) + r - 1]);
-                        dft_small<R3>(w);
-#pragma unroll
-                        for (int r = 0; r < R3; ++r) v[t + r * S3] = w[r];
-                    }
+                    if constexpr (R3 == 16) dft16_pk(v);
+                    else if constexpr (R3 == 8) dft8_pk<S3>(v, t);
+                    else dft_small<R3, S3>(v, t);
                 }
-            } else {
-                // N = 64: pass 2 already wrote bins j + 8 r in order; fetch them back into the lane pattern
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int m = 0; m < E; ++m) v[m] = X[fpad(j + LP * m)];
             }
             float2* grow = a.gtab + ((size_t)ul * ws.P + ls) * a.K;
             uint2* prow = reinterpret_cast<uint2*>(grow);
@@ -750,17 +597,27 @@ __global__ __launch_bounds__(256) void k3_lpf_fft_pow2(WsView ws, LpfArgs a, int
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");           // every lane has read its inputs of the last pass
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll
-                for (int m = 0; m < E; ++m) X[fpad(j + LP * m)] = v[m];
+                for (int m = 0; m < E; ++m) *at(rd, j, LP * m) = v[m];
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll
                 for (int m = 0; m < E; ++m) v[m] = X[binreg[m]];
             }
+            if (PW == 1 && a.K == N) {                                           // wave-uniform, every lane and bin stores: no per-store guard
 #pragma unroll
-            for (int m = 0; m < E; ++m)
-                if (act && j + LP * m < a.K) store_gain<PACK>(grow, prow, j + LP * m, v[m], ws.neg_one);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");               // the buffer is free for the next path
-            __builtin_amdgcn_wave_barrier();
+                for (int m = 0; m < E; ++m) store_gain<PACK>(grow, prow, j + LP * m, v[m], ws.neg_one);
+            } else {
+#pragma unroll
+                for (int m = 0; m < E; ++m)
+                    if (act && j + LP * m < a.K) store_gain<PACK>(grow, prow, j + LP * m, v[m], ws.neg_one);
+            }
+            if constexpr (!IDENT || PW > 1) {
+                // the gather read wherever the selection pointed: keep the next path's pass 1 behind it.  With IDENT the last
+                // LDS operations were the lane's own reads of the last pass, and the in-order rule above covers them (it
+                // would for several paths per wave as well; those sizes keep the fence they were measured with)
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+                __builtin_amdgcn_wave_barrier();
+            }
         }
     }
 }
@@ -789,7 +646,7 @@ int launch_channels_fd_lpf(const dmx_params& prm, const WsView& ws, int64_t user
     return DMX_OK;
 }
 
-// the wave-per-user kernels (k3_lpf_fft512, k3_lpf_fft_pow2): persistent, four users per workgroup
+// the wave-per-user kernel (k3_lpf_fft_pow2): persistent, four users per workgroup
 using WaveFftKernel = void (*)(WsView, LpfArgs, int64_t);
 static int launch_wave_fft(WaveFftKernel kernel, const char* name, size_t smem, const WsView& ws, const LpfArgs& a, int64_t user_count,
                            hipStream_t stream) {
@@ -812,19 +669,9 @@ static int launch_channels_fd_lpf_once(const dmx_params& prm, const WsView& ws, 
         int log2n = 0;
         while ((1 << log2n) < a.N) ++log2n;
         const bool old = tuning_int("DMX_LPF_OLD_FFT", 0) == 1;       // tuning build only: the workgroup-per-user FFT
-        if (a.N == 512 && a.K <= 512 && ws.P <= 64 && !old && tuning_int("DMX_LPF_GENERIC_FFT", 0) != 1) {      // (longer selections: the generic kernel)
-            // wave per user, N fixed (k3_lpf_fft512); tuning build only: DMX_LPF_GENERIC_FFT=1 takes the generic kernel below
-            a.pack = packed = lpf_table_packed(prm, ws) && tuning_int("DMX_LPF_FLOAT_TABLE", 0) != 1;
-            const bool ident = prm.sc_stride == 1 && (prm.sc_first & 511) == 0 && a.K <= 512;   // host promise: sc[k] = k (mod N)
-            static constexpr WaveFftKernel kfns[8] = {k3_lpf_fft512<false, false, false>, k3_lpf_fft512<false, false, true>,
-                                                      k3_lpf_fft512<false, true, false>,  k3_lpf_fft512<false, true, true>,
-                                                      k3_lpf_fft512<true, false, false>,  k3_lpf_fft512<true, false, true>,
-                                                      k3_lpf_fft512<true, true, false>,   k3_lpf_fft512<true, true, true>};
-            rc = launch_wave_fft(kfns[(ident ? 4 : 0) + (packed ? 2 : 0) + (a.doppler ? 1 : 0)], "k3_lpf_fft512", 4 * lpf_buf_elems(512) * 8,
-                                 ws, a, user_count, stream);
-        } else if ((a.N == 64 || a.N == 128 || a.N == 256 || a.N == 1024) && a.K <= a.N && ws.P <= 64 && !old &&
-                   tuning_int("DMX_LPF_GENERIC_FFT", 0) != 1) {
-            // the other default sizes, same scheme (k3_lpf_fft_pow2)
+        if (pow2 && a.N >= 64 && a.N <= 1024 && a.K <= a.N && ws.P <= 64 && !old && tuning_int("DMX_LPF_GENERIC_FFT", 0) != 1) {
+            // N = 64 ... 1024: wave per user, N a template parameter (k3_lpf_fft_pow2; longer selections and more paths: the
+            // generic kernel below); tuning build only: DMX_LPF_GENERIC_FFT=1 takes the generic kernel too
             a.pack = packed = lpf_table_packed(prm, ws) && tuning_int("DMX_LPF_FLOAT_TABLE", 0) != 1;
             const bool ident = prm.sc_stride == 1 && (prm.sc_first & (a.N - 1)) == 0;          // host promise: sc[k] = k (mod N)
             const int v = (ident ? 4 : 0) + (packed ? 2 : 0) + (a.doppler ? 1 : 0);
@@ -832,11 +679,11 @@ static int launch_channels_fd_lpf_once(const dmx_params& prm, const WsView& ws, 
                               k3_lpf_fft_pow2<L2, false, true, false>,  k3_lpf_fft_pow2<L2, false, true, true>,  \
                               k3_lpf_fft_pow2<L2, true, false, false>,  k3_lpf_fft_pow2<L2, true, false, true>,  \
                               k3_lpf_fft_pow2<L2, true, true, false>,   k3_lpf_fft_pow2<L2, true, true, true>}
-            static constexpr WaveFftKernel kfns[4][8] = {DMX_FFT_POW2_ROW(6), DMX_FFT_POW2_ROW(7), DMX_FFT_POW2_ROW(8), DMX_FFT_POW2_ROW(10)};
+            static constexpr WaveFftKernel kfns[5][8] = {DMX_FFT_POW2_ROW(6), DMX_FFT_POW2_ROW(7), DMX_FFT_POW2_ROW(8), DMX_FFT_POW2_ROW(9),
+                                                         DMX_FFT_POW2_ROW(10)};
 #undef DMX_FFT_POW2_ROW
             const int pw = a.N >= 512 ? 1 : 512 / a.N;                                          // paths per wave
-            rc = launch_wave_fft(kfns[a.N == 64 ? 0 : (a.N == 128 ? 1 : (a.N == 256 ? 2 : 3))][v], "k3_lpf_fft_pow2",
-                                 (size_t)4 * pw * lpf_buf_elems(a.N) * 8, ws, a, user_count, stream);
+            rc = launch_wave_fft(kfns[log2n - 6][v], "k3_lpf_fft_pow2", (size_t)4 * pw * lpf_buf_elems(a.N) * 8, ws, a, user_count, stream);
         } else if (pow2 && a.N >= 64 && a.N <= 2048 && !old) {
             // tuning build only: DMX_LPF_FLOAT_TABLE=1 keeps the float table
             a.pack = packed = lpf_table_packed(prm, ws) && tuning_int("DMX_LPF_FLOAT_TABLE", 0) != 1;

@@ -348,7 +348,7 @@ CASES = (
     Case("fd_direct", "dmx_channels_fd_direct", ("k12_fd_direct",), _direct([8, 1], [1, 1], [0]), "dmx_fd_direct_supported"),
     # rx_filter: the gains kernel of every FFT route, then the contraction (matrix cores over the packed or the float table,
     # or the fp32 vector kernel); lpf_extra adds accumulate passes over the float table
-    Case("lpf_fft512", "dmx_channels_fd_lpf", (K1, "k3_lpf_fft512", "k2_fd_mfma"), _lpf(*MFMA_ARRAYS, 512, range(8)), R_LPF),
+    Case("lpf_fft512", "dmx_channels_fd_lpf", (K1, "k3_lpf_fft_pow2", "k2_fd_mfma"), _lpf(*MFMA_ARRAYS, 512, range(8)), R_LPF),
     Case("lpf_pow2", "dmx_channels_fd_lpf", (K1, "k3_lpf_fft_pow2", "k2_fd_valu"), _lpf(*VALU_ARRAYS, 64, range(8)), R_LPF),
     Case("lpf_wave", "dmx_channels_fd_lpf", (K1, "k3_lpf_fft_wave", "k2_fd_mfma"), _lpf(*MFMA_ARRAYS, 64, range(70)), R_LPF),
     Case("lpf_wave_2048", "dmx_channels_fd_lpf", (K1, "k3_lpf_fft_wave", "k2_fd_valu"), _lpf(*VALU_ARRAYS, 2048, range(8)), R_LPF),

@@ -1,8 +1,8 @@
 """Case table and float64 reference of tests/test_gpu_rx_filter_routes.py and tests/test_rx_filter_routes_cpu.py.
 
-rx_filter = 1 has five gain kernels behind one dispatcher (launch_channels_fd_lpf_once, k3_lpf_gains.hip).  This module
+rx_filter = 1 has four gain kernels behind one dispatcher (launch_channels_fd_lpf_once, k3_lpf_gains.hip).  This module
 restates the dispatcher in its default build (`lpf_route`; the tuning hooks stay at their defaults), the facts of the
-three kernels the fast N = 512 / 64 / 128 / 256 / 1024 kernels leave over (the radices, the gather form and the LDS of
+three kernels the fast N = 64 / 128 / 256 / 512 / 1024 kernel leaves over (the radices, the gather form and the LDS of
 k3_lpf_fft_wave; PB and the batches of k3_lpf_fft; the LDS of the direct kernel k3_lpf_gains), the table of cases that
 reach each of their branches, the rays of a case and the float64 gains of every kept path.  A plain module: no torch,
 no GPU.  tests/test_rx_filter_routes_cpu.py pins the restated conditions to the kernel file's text.
@@ -41,9 +41,7 @@ def lpf_route(N, K, P):
     if N * 16 > 64 * 1024:
         return "refused"
     pow2 = N >= 2 and (N & (N - 1)) == 0
-    if N == 512 and K <= 512 and P <= 64:
-        return "fft512"
-    if N in (64, 128, 256, 1024) and K <= N and P <= 64:
+    if pow2 and 64 <= N <= 1024 and K <= N and P <= 64:
         return "fft_pow2"
     if pow2 and 64 <= N <= 2048:
         return "fft_wave"
@@ -58,9 +56,9 @@ def mfma_preferred(M, K):
 
 
 def table_packed(N, K, P, M):
-    """whether the gains table is written as packed f16 pairs: lpf_table_packed (k2_channel_fd.hip), asked by the three
+    """whether the gains table is written as packed f16 pairs: lpf_table_packed (k2_channel_fd.hip), asked by the two
     wave FFT kernels only - k3_lpf_fft and k3_lpf_gains always write floats"""
-    return lpf_route(N, K, P) in ("fft512", "fft_pow2", "fft_wave") and mfma_preferred(M, K) and P <= 32
+    return lpf_route(N, K, P) in ("fft_pow2", "fft_wave") and mfma_preferred(M, K) and P <= 32
 
 
 def log2n(N):

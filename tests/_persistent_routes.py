@@ -19,7 +19,7 @@ LDS_PER_CU = 160 * 1024
 
 # the kernels whose workgroups or waves loop over work items (gridDim-strided loops)
 PERSISTENT_KERNELS = ("k2_fd_mfma", "k2b_beam_project_mfma", "k2_fd_fold", "k2_fd_small", "k2c_beam_power",
-                      "k3_lpf_fft_wave", "k3_lpf_fft512", "k3_lpf_fft_pow2")
+                      "k3_lpf_fft_wave", "k3_lpf_fft_pow2")
 
 
 def _cdiv(a, b):
@@ -130,10 +130,10 @@ def grid_upper_bound(route, launch, items, cu):
         if g4 > grid:
             grid = min(g4, 4 * grid)
         return min(items, grid)
-    if k == "fft_wave_per_user":                                                        # k3_lpf_gains.hip:794-797 (launch_wave_fft)
+    if k == "fft_wave_per_user":                                                        # k3_lpf_gains.hip:651-655 (launch_wave_fft)
         return min(cu * _per_cu(4, launch.lds), _cdiv(items, 4))
     if k == "fft_wave":
-        return min(cu * _per_cu(4, launch.lds), items)                                  # k3_lpf_gains.hip:845-846
+        return min(cu * _per_cu(4, launch.lds), items)                                  # k3_lpf_gains.hip:692-693
     if k == "fold":
         # k2_channel_fd_fold.hip:689 (smem >= FOLD_MIN_LDS = 160 KiB / 5 + 64: at most four per CU) and :692-694
         grid = cu * _per_cu(4, LDS_PER_CU // 5 + 64)
@@ -169,8 +169,8 @@ def _mfma(nw, mode, gsrc, rows, ipw, persistent=True):
                   persistent=persistent, gsrc=gsrc, mode=mode)
 
 
-_FFT512 = Launch("k3_lpf_fft512", "fft_wave_per_user", lds=4 * (512 + 512 // 16 + 1) * 8)          # k3_lpf_gains.hip:823
-_FFT128 = Launch("k3_lpf_fft_pow2", "fft_wave_per_user", lds=4 * 4 * (128 + 128 // 16 + 1) * 8)    # :837-839
+_FFT512 = Launch("k3_lpf_fft_pow2", "fft_wave_per_user", lds=4 * (512 + 512 // 16 + 1) * 8)        # k3_lpf_gains.hip:685-686, one path per wave
+_FFT128 = Launch("k3_lpf_fft_pow2", "fft_wave_per_user", lds=4 * 4 * (128 + 128 // 16 + 1) * 8)    # the same, four paths per wave
 _FFTW512 = Launch("k3_lpf_fft_wave", "fft_wave", lds=512 * 8 + 4 * 2 * (512 + 512 // 16 + 1) * 8)  # :263
 _FFTW2048 = Launch("k3_lpf_fft_wave", "fft_wave", lds=2048 * 8 + 4 * 2 * (2048 + 2048 // 16 + 1) * 8)
 
@@ -209,16 +209,16 @@ ROUTES = (
           kind="beam_power", n_beams=32),
     # rx_filter: the packed f16 gains table (GSRC 2) in 8-wave workgroups, K = 200 (not a multiple of 16: no DMA), and
     # the guarded-store N = 512 FFT with the Doppler term
-    Route("k", "rx_filter GSRC 2, 8 waves + k3_lpf_fft512, Doppler", (8, 4), (2, 2), 25, 512, ("range", 0, 200, 1), 16384,
+    Route("k", "rx_filter GSRC 2, 8 waves + k3_lpf_fft_pow2 (N = 512), Doppler", (8, 4), (2, 2), 25, 512, ("range", 0, 200, 1), 16384,
           (_mfma(8, 0, 2, 128, 8), _FFT512), kind="lpf", doppler=True),
     # GSRC 3: the LDS-DMA chain (the next item's first strip prefetched into the wave's slot), whole and ragged blocks
     Route("l256", "rx_filter GSRC 3 (DMA chain), 256 rows", (8, 8), (2, 2), 25, 512, ("range", 0, 256, 1), 4096,
           (_mfma(16, 0, 3, 256, 4),), kind="lpf"),
     Route("l320", "rx_filter GSRC 3 (DMA chain), 320 rows = 256 + 64", (10, 8), (2, 2), 25, 512, ("range", 0, 256, 1), 2048,
           (_mfma(16, 0, 3, 256, 4),), kind="lpf"),
-    Route("m", "rx_filter GSRC 2 small (4 waves, resident grid) + k3_lpf_fft_pow2", (4, 4), (2, 1), 25, 128,
+    Route("m", "rx_filter GSRC 2 small (4 waves, resident grid) + k3_lpf_fft_pow2 (N = 128)", (4, 4), (2, 1), 25, 128,
           ("range", 0, 64, 1), 20480, (_mfma(4, 0, 2, 32, 0), _FFT128), kind="lpf"),
-    Route("n", "k3_lpf_fft512 (float table) + the vector contraction, Doppler", (2, 1), (1, 1), 25, 512,
+    Route("n", "k3_lpf_fft_pow2 (N = 512, float table) + the vector contraction, Doppler", (2, 1), (1, 1), 25, 512,
           ("range", 0, 512, 1), 20480, (_FFT512,), kind="lpf", doppler=True),
     Route("o", "k3_lpf_fft_wave (K = 600 > N = 512)", (2, 1), (1, 1), 25, 512, ("range", 0, 600, 1), 8192,
           (_FFTW512,), kind="lpf"),
@@ -229,7 +229,7 @@ ROUTES = (
     # GSRC 1 (the float gains table with matrix cores): rx_filter with more than 32 path slots (lpf_table_packed is
     # false, k2_channel_fd.hip:308); the first 32 kept paths go through the matrix cores, the rest through the vector
     # kernel's accumulate passes
-    Route("s", "rx_filter GSRC 1 (40 paths), 8 waves + k3_lpf_fft512 float table", (4, 4), (2, 1), 40, 512,
+    Route("s", "rx_filter GSRC 1 (40 paths), 8 waves + k3_lpf_fft_pow2 (N = 512) float table", (4, 4), (2, 1), 40, 512,
           ("range", 0, 256, 1), 16384, (_mfma(8, 0, 1, 32, 8), _FFT512), kind="lpf"),
     # the folded kernel: one wave per item (8 pairs), and the shared-table form (64 pairs)
     Route("p", "k2_fd_fold, one wave per item", (8, 1), (1, 1), 25, 512, ("range", 0, 512, 1), 16384,

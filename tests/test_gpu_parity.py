@@ -640,7 +640,7 @@ def test_rx_filter_fft_and_mfma_path(N, K):
 @pytest.mark.parametrize("arrays", ["mfma", "valu", "dma256", "dma320"])
 @pytest.mark.parametrize("selection", ["all512", "first200", "random100", "offset512", "even256", "wrap600"])
 def test_rx_filter_fft512_variants(selection, arrays):
-    """Every instantiation of the N = 512 wave-per-user FFT (k3_lpf_fft512): selected subcarriers 0..K-1 stored from
+    """Every N = 512 instantiation of the wave-per-user FFT (k3_lpf_fft_pow2<9, ..>): selected subcarriers 0..K-1 stored from
     registers (K = 512 unguarded, K = 200 guarded, 512..1023 = the same bins through the stride promise) or any selection
     through the buffer; packed f16 table for the matrix-core contraction or float table for the vector kernel; Doppler on
     and off; users with 0, 1 and all paths; delays that are whole samples (np.sinc(0) = 1 taps, channel.py:166-168).
@@ -682,7 +682,7 @@ def test_rx_filter_fft512_variants(selection, arrays):
 @pytest.mark.parametrize("N,selection", [(N, s) for N in (64, 128, 256, 1024) for s in ("all", "first_half", "random", "offset")] +
                          [(1024, "wrap")])
 def test_rx_filter_fft_pow2_variants(N, selection, arrays):
-    """k3_lpf_fft_pow2: the register FFT of the other default OFDM sizes - 8, 4 and 2 paths per wave (N = 64, 128, 256:
+    """k3_lpf_fft_pow2 at the other default OFDM sizes - 8, 4 and 2 paths per wave (N = 64, 128, 256:
     the last lane group runs past a user's path count) and 16 points per lane with a radix-16 last pass (N = 1024);
     selections stored from registers or through the buffer, packed or float table, Doppler on and off, users with 0, 1, 2
     and all paths, whole-sample delays.  1024-wrap: more subcarriers than bins leave this kernel for the generic

@@ -140,8 +140,8 @@ def test_channels(route, variant, family, monkeypatch):
 @pytest.mark.parametrize("family", FAM)
 @pytest.mark.parametrize("N", [512, 1024, 100])
 def test_rx_filter(N, family):
-    """rx_filter = 1: FFT forms at N = 512 (k3_lpf_fft512; arange(-512, 0) is sc[k] = k mod 512, the `ident` store of
-    the promise) and 1024 (k3_lpf_fft_pow2), the direct kernel at N = 100 (floor-mod of a negative index)"""
+    """rx_filter = 1: FFT forms at N = 512 (k3_lpf_fft_pow2, one radix-8 butterfly per lane and pass; arange(-512, 0) is
+    sc[k] = k mod 512, the `ident` store of the promise) and 1024 (the same kernel, a last pass of radix 16), the direct kernel at N = 100 (floor-mod of a negative index)"""
     from deepmimo_amd.engine import uniform_stride
     sel = FAMILIES[family]
     if family == "centred":

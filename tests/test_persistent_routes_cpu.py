@@ -54,7 +54,7 @@ def _routed():
 
 def test_every_persistent_kernel_has_a_route():
     found = kernels_with_strided_loops(_sources())
-    assert len(found) >= 8, found                   # the scan itself works (eight such kernels when this was written)
+    assert len(found) >= 7, found                   # the scan itself works (seven such kernels; the set is pinned below)
     missing = sorted(k for k in found if k not in _routed())
     assert not missing, f"persistent kernels without a route in tests/_persistent_routes.py: {missing}"
     assert set(found) == set(R.PERSISTENT_KERNELS), (sorted(found), R.PERSISTENT_KERNELS)

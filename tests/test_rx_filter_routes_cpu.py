@@ -4,7 +4,7 @@
    fails here instead of silently sending the GPU cases to another kernel.
 2. The case table reaches what it promises, by the mirror: k3_lpf_fft_wave with a last pass of radix 8, 4 and 2, both
    gather forms, packed and float tables, more than 64 kept paths; k3_lpf_fft with PB = 16 (a full and a ragged batch)
-   and PB = 1; k3_lpf_gains with N > 256 and K > 256; nothing on the two fast kernels the suite already covers.
+   and PB = 1; k3_lpf_gains with N > 256 and K > 256; nothing on the fast kernel the suite already covers.
 3. The reference against itself: the float64 gain rows summed through the float64 array responses are the oracle's
    channel, and for power-of-two N they are np.fft.fft of the taps at the selected bins.
 4. Sensitivity, a condition on the inputs: for the equal-power user of every case a dropped path and two gain rows in
@@ -39,11 +39,11 @@ def test_route_mirror_and_the_dispatchers_text():
         r"const bool pow2 = a\.N >= 2 && \(a\.N & \(a\.N - 1\)\) == 0;",
         r"while \(\(1 << log2n\) < a\.N\) \+\+log2n;",
         r"const bool old = tuning_int\(\"DMX_LPF_OLD_FFT\", 0\) == 1;",
-        r"\n        if \(a\.N == 512 && a\.K <= 512 && ws\.P <= 64 && !old && tuning_int\(\"DMX_LPF_GENERIC_FFT\", 0\) != 1\) \{",
-        r"\"k3_lpf_fft512\", 4 \* lpf_buf_elems\(512\) \* 8,",
-        r"\n        \} else if \(\(a\.N == 64 \|\| a\.N == 128 \|\| a\.N == 256 \|\| a\.N == 1024\) && a\.K <= a\.N && ws\.P <= 64 && !old &&\n"
-        r"                   tuning_int\(\"DMX_LPF_GENERIC_FFT\", 0\) != 1\) \{",
-        r"\"k3_lpf_fft_pow2\",",
+        r"\n        if \(pow2 && a\.N >= 64 && a\.N <= 1024 && a\.K <= a\.N && ws\.P <= 64 && !old && tuning_int\(\"DMX_LPF_GENERIC_FFT\", 0\) != 1\) \{",
+        r"const bool ident = prm\.sc_stride == 1 && \(prm\.sc_first & \(a\.N - 1\)\) == 0;",
+        r"static constexpr WaveFftKernel kfns\[5\]\[8\] = \{DMX_FFT_POW2_ROW\(6\), DMX_FFT_POW2_ROW\(7\), DMX_FFT_POW2_ROW\(8\), DMX_FFT_POW2_ROW\(9\),\n"
+        r"\s*DMX_FFT_POW2_ROW\(10\)\};",
+        r"kfns\[log2n - 6\]\[v\], \"k3_lpf_fft_pow2\", \(size_t\)4 \* pw \* lpf_buf_elems\(a\.N\) \* 8,",
         r"\n        \} else if \(pow2 && a\.N >= 64 && a\.N <= 2048 && !old\) \{",
         r"a\.pack = packed = lpf_table_packed\(prm, ws\) && tuning_int\(\"DMX_LPF_FLOAT_TABLE\", 0\) != 1;\n[^\n]*\n"
         r"            const size_t smem = lpf_wave_lds_bytes\(a\.N\);",
@@ -60,7 +60,7 @@ def test_route_mirror_and_the_dispatchers_text():
         m = re.compile(pat).search(body, at)
         assert m, f"the dispatcher no longer reads: {pat}"
         at = m.end()
-    assert body.count("a.pack = packed =") == 3 and body.count("else if") == 3      # five branches, three that may pack
+    assert body.count("a.pack = packed =") == 2 and body.count("else if") == 2      # four branches, two that may pack
     # the kernels' own rules
     assert re.search(r"__host__ __device__ inline size_t lpf_buf_elems\(int N\) \{ return \(size_t\)N \+ N / 16 \+ 1; \}", k3)
     assert re.search(r"__host__ __device__ inline size_t lpf_wave_lds_bytes\(int N\) \{ return \(size_t\)N \* 8 \+ 4 \* 2 \* lpf_buf_elems\(N\) \* 8; \}", k3)
@@ -81,8 +81,8 @@ def test_route_mirror_and_the_dispatchers_text():
 
     # the mirror at the edges of every condition
     route = R.lpf_route
-    assert [route(512, K, 25) for K in (1, 512, 513)] == ["fft512", "fft512", "fft_wave"]
-    assert [route(512, 100, P) for P in (64, 65)] == ["fft512", "fft_wave"]
+    assert [route(512, K, 25) for K in (1, 512, 513)] == ["fft_pow2", "fft_pow2", "fft_wave"]
+    assert [route(512, 100, P) for P in (64, 65)] == ["fft_pow2", "fft_wave"]
     assert [route(N, N, 25) for N in (64, 128, 256, 1024)] == ["fft_pow2"] * 4
     assert [route(N, N + 1, 25) for N in (64, 128, 256, 1024)] == ["fft_wave"] * 4
     assert [route(N, 8, 65) for N in (64, 128, 256, 1024)] == ["fft_wave"] * 4
@@ -110,7 +110,7 @@ def test_the_table_reaches_what_it_promises():
     wave = [c for c in R.CASES if R.route_of(c) == "fft_wave"]
     fft = [c for c in R.CASES if R.route_of(c) == "fft"]
     gains = [c for c in R.CASES if R.route_of(c) == "gains"]
-    assert len(wave) + len(fft) + len(gains) == len(R.CASES)    # nothing on fft512 / fft_pow2, nothing refused
+    assert len(wave) + len(fft) + len(gains) == len(R.CASES)    # nothing on fft_pow2, nothing refused
     assert {c.id[0] for c in wave} == {"w"} and {c.id[0] for c in fft} == {"f"} and {c.id[0] for c in gains} == {"g"}
     # k3_lpf_fft_wave
     assert {R.wave_radices(c.N)[-1] for c in wave} == {8, 4, 2}
@@ -133,7 +133,7 @@ def test_the_table_reaches_what_it_promises():
         assert kept[c.id][R.ONE] == 1 and kept[c.id][R.NONE] == 0 and kept[c.id][R.TWO] == 2
         assert kept[c.id].max() == 70                           # slots 64 .. 69: the l >= 64 reads of two waves at least
     assert set(R.CASES_BY_ID["w256_p70"].arrays) == {"mfma", "valu"}
-    assert R.lpf_route(512, len(R.selection(R.CASES_BY_ID["w512_p70"])), 25) == "fft512"       # what P = 70 displaces
+    assert R.lpf_route(512, len(R.selection(R.CASES_BY_ID["w512_p70"])), 25) == "fft_pow2"     # what P = 70 displaces
     # k3_lpf_fft
     assert {R.fft_pb(c.N, c.L) for c in fft} == {16, 9, 1}
     for cid in ("f32_all", "f32_off"):

@@ -23,7 +23,7 @@ def main():
     ap.add_argument("--workload", default="c3_headline")
     ap.add_argument("--quick", action="store_true", help="skip the plain path and the round-1 FFT")
     ap.add_argument("--plain-only", action="store_true", help="the plain path alone")
-    ap.add_argument("--n", type=int, default=0, help="OFDM size N = K instead of the workload's (512: k3_lpf_fft512; others: the generic k3_lpf_fft_wave)")
+    ap.add_argument("--n", type=int, default=0, help="OFDM size N = K instead of the workload's (64, 128, 256, 512, 1024: k3_lpf_fft_pow2; 2048: the generic k3_lpf_fft_wave)")
     args = ap.parse_args()
     w = dict(bench.WORKLOADS[args.workload])
     w["n_ue"] = args.users
