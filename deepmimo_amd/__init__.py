@@ -17,10 +17,11 @@ from .general_utils import DotDict
 from .channel import ChannelGenParameters
 from .dataset import Dataset, MacroDataset
 from .geometry import dft_codebook, pattern_gain, steering_vec
+from .combiner import combine_rays, combiner_response
 from .core import generate, load
 from .generator_utils import get_idxs_with_limits, LinearPath
 
 __version__ = consts.VERSION
 
 __all__ = ["generate", "load", "Dataset", "MacroDataset", "ChannelGenParameters", "config", "steering_vec", "dft_codebook",
-           "pattern_gain", "get_idxs_with_limits", "LinearPath", "DotDict", "consts"]
+           "pattern_gain", "combiner_response", "combine_rays", "get_idxs_with_limits", "LinearPath", "DotDict", "consts"]

@@ -46,7 +46,11 @@ _RX_VEL, _TX_VEL = "rx_vel", "tx_vel"
 _TIMES, _N_TIMES, _N_UE_PER_TIME = "times", "n_times", "n_ue_per_time"
 _TIME_KEYS = (_TIMES, _N_TIMES, _N_UE_PER_TIME)
 _FOV_KEYS = ("bs_fov", "ue_fov")
-_NOT_PER_USER = (_TX_VEL, c.TX_POS_PARAM_NAME) + _FOV_KEYS + _TIME_KEYS      # never the user axis, whatever their length
+# UE receive combining (DESIGN.md "UE receive combining")
+_RX_COMBINER, _N_RX_BEAMS, _N_UE_PER_RX_BEAM = "rx_combiner", "n_rx_beams", "n_ue_per_rx_beam"
+_RX_KEYS = (_RX_COMBINER, _N_RX_BEAMS, _N_UE_PER_RX_BEAM)
+_NOT_PER_USER = (_TX_VEL, c.TX_POS_PARAM_NAME) + _FOV_KEYS + _TIME_KEYS + _RX_KEYS    # never the user axis, whatever their length
+_VIEW_RESULTS = ("beam_mean_amplitude", "beam_pair_mean_amplitude")         # results kept in the dict that no view carries
 # what a block of snapshots needs to run a channel call, and nothing a caller of the view might read beside it
 _BLOCK_KEYS = c.RAY_FIELDS + (c.DOPPLER_VEL_PARAM_NAME, c.DOPPLER_ACC_PARAM_NAME, c.CH_PARAMS_PARAM_NAME) + _FOV_KEYS
 
@@ -72,6 +76,13 @@ def _engine():
         from .engine import ChannelEngine
         _engines[dev] = ChannelEngine(dev)
     return _engines[dev]
+
+
+def _tile_users(value, reps: int):
+    """The per-user array `value` (NumPy or torch) `reps` times along the user axis."""
+    if isinstance(value, np.ndarray):
+        return np.tile(value, (reps,) + (1,) * (value.ndim - 1))
+    return value.repeat(reps, *([1] * (value.dim() - 1)))
 
 
 def _precoding_codebook(who: str, params, codebook):
@@ -178,6 +189,10 @@ class Dataset(DotDict):
         if params is None:
             params = ChannelGenParameters()
         params.validate(self.n_ue)
+        ue_shape = params[c.PARAMSET_ANT_UE][c.PARAMSET_ANT_SHAPE]
+        if _N_RX_BEAMS in self._data and [int(v) for v in ue_shape] != [1, 1]:
+            raise ValueError(f"this dataset is a view of with_rx_combiner: each of its users is one UE beam of a combined "
+                             f"array, a single antenna, and takes ue_antenna.shape = [1, 1] only, got {list(ue_shape)}")
         old = self._data.get(c.CH_PARAMS_PARAM_NAME)
         self.ch_params = params.deepcopy()
         if old is not None:
@@ -231,10 +246,10 @@ class Dataset(DotDict):
         if cached is not None:
             return cached
         if rot.ndim == 2 and rot.shape == (3, 2):
-            if _N_TIMES in self._data:            # a view of `at_times`: a UE keeps its orientation over the snapshots
-                rot = np.tile(np.random.uniform(rot[:, 0], rot[:, 1], (self._data[_N_UE_PER_TIME], 3)), (self._data[_N_TIMES], 1))
-            else:
-                rot = np.random.uniform(rot[:, 0], rot[:, 1], (self.n_ue, 3))
+            # a view of `at_times` or `with_rx_combiner` tiles its users: a UE keeps its orientation over the snapshots
+            # and the UE beams
+            reps = self._data.get(_N_TIMES, 1) * self._data.get(_N_RX_BEAMS, 1)
+            rot = np.tile(np.random.uniform(rot[:, 0], rot[:, 1], (self.n_ue // reps, 3)), (reps, 1))
         rot = np.ascontiguousarray(rot, dtype=np.float64).reshape(-1, 3)
         self._data[_UE_ROT_RESOLVED] = rot
         return rot
@@ -873,7 +888,7 @@ class Dataset(DotDict):
                 return value[idxs]
             import torch
             return value[torch.as_tensor(np.asarray(idxs), device=value.device)]
-        return self._with_users(len(idxs), take, self.to_dict().items(), skip=_TIME_KEYS)
+        return self._with_users(len(idxs), take, self.to_dict().items(), skip=_TIME_KEYS + _RX_KEYS)
 
     def _with_users(self, n_new: int, take, items, skip=(), fixed=()) -> "Dataset":
         """New Dataset of `n_new` users from `items`, (key, value) pairs of this one: the shared objects by reference,
@@ -975,26 +990,31 @@ class Dataset(DotDict):
         fc = self._time_carrier(who, carrier_freq)
         vel, acc = self._doppler_matrices(who)
         T, n_ue = len(t), int(self.n_ue)
-
-        def tile(value):
-            if isinstance(value, np.ndarray):
-                return np.tile(value, (T,) + (1,) * (value.ndim - 1))
-            return value.repeat(T, *([1] * (value.dim() - 1)))
-
-        cached = (set(self._computed_attributes) - {c.CH_PARAMS_PARAM_NAME}) | {"beam_mean_amplitude", c.PHASE_PARAM_NAME}
-        keys = [k for k in self._data if not k.startswith("_") and k not in cached and (only is None or k in only)]
-        view = self._with_users(T * n_ue, tile, ((k, self._host(k)) for k in keys), skip=_TIME_KEYS, fixed=_NOT_PER_USER)
+        phase = advance_phase(self[c.PHASE_PARAM_NAME], vel, acc, t, fc)
+        view = self._tiled_view(T, {c.PHASE_PARAM_NAME: phase}, only, skip=_TIME_KEYS)
         d = view._data
-        d[c.PHASE_PARAM_NAME] = advance_phase(self[c.PHASE_PARAM_NAME], vel, acc, t, fc)
+        d[_TIMES], d[_N_TIMES], d[_N_UE_PER_TIME] = t.copy(), T, n_ue
+        return view
+
+    def _tiled_view(self, reps: int, replaced, only=None, skip=()) -> "Dataset":
+        """What the views of `at_times` and `with_rx_combiner` share: a Dataset of `reps` * n_ue users, every public
+        per-user array tiled, the ray matrices in `replaced` (key -> the matrix of the view) in place of the tiled ones,
+        the stored parameters tiled (`_tiled_params`) with the rotations drawn for them, the fields of view copied, no
+        cached result.  `only`: the public keys to carry; `skip`: keys never carried."""
+        cached = (set(self._computed_attributes) - {c.CH_PARAMS_PARAM_NAME}) | set(_VIEW_RESULTS) | set(replaced)
+        keys = [k for k in self._data if not k.startswith("_") and k not in cached and (only is None or k in only)]
+        view = self._with_users(reps * int(self.n_ue), lambda v: _tile_users(v, reps), ((k, self._host(k)) for k in keys),
+                                skip=skip, fixed=_NOT_PER_USER)
+        d = view._data
+        d.update(replaced)
         if c.CH_PARAMS_PARAM_NAME in d:
-            d[c.CH_PARAMS_PARAM_NAME] = self._tiled_params(self._data[c.CH_PARAMS_PARAM_NAME], T)
-            drawn = self._data.get(_UE_ROT_RESOLVED)                       # the parent's draw: the same UEs, later
+            d[c.CH_PARAMS_PARAM_NAME] = self._tiled_params(self._data[c.CH_PARAMS_PARAM_NAME], reps)
+            drawn = self._data.get(_UE_ROT_RESOLVED)                       # the parent's draw: the same UEs
             if drawn is not None:
-                d[_UE_ROT_RESOLVED] = np.tile(drawn, (T, 1))
+                d[_UE_ROT_RESOLVED] = np.tile(drawn, (reps, 1))
         for k in _FOV_KEYS:
             if isinstance(d.get(k), np.ndarray):
                 d[k] = d[k].copy()
-        d[_TIMES], d[_N_TIMES], d[_N_UE_PER_TIME] = t.copy(), T, n_ue
         return view
 
     @staticmethod
@@ -1012,17 +1032,23 @@ class Dataset(DotDict):
         T, n = self._data.get(_N_TIMES), self._data.get(_N_UE_PER_TIME)
         if T is None:
             raise ValueError("split_times: this dataset is not a view of at_times")
+        return self._split_users("split_times", x, T, n, "n_times * n_ue")
+
+    @staticmethod
+    def _split_users(who: str, x, outer: int, inner: int, what: str):
+        """`x` - an array or tensor whose first axis holds `outer` * `inner` users (`what`), or a tuple, list or dict of
+        them - as [outer, inner, ...]: a view of the same memory, never a copy."""
         if isinstance(x, Mapping):
-            return type(x)({k: self.split_times(v) for k, v in x.items()})
+            return type(x)({k: Dataset._split_users(who, v, outer, inner, what) for k, v in x.items()})
         if isinstance(x, (tuple, list)):
-            return type(x)(self.split_times(v) for v in x)
+            return type(x)(Dataset._split_users(who, v, outer, inner, what) for v in x)
         shape = tuple(x.shape)
-        if not shape or shape[0] != T * n:
-            raise ValueError(f"split_times: the first axis must be n_times * n_ue = {T * n}, got shape {shape}")
+        if not shape or shape[0] != outer * inner:
+            raise ValueError(f"{who}: the first axis must be {what} = {outer * inner}, got shape {shape}")
         if hasattr(x, "detach"):
-            return x.view((T, n) + shape[1:])
+            return x.view((outer, inner) + shape[1:])
         y = x.view()
-        y.shape = (T, n) + shape[1:]                                        # raises where NumPy would have to copy
+        y.shape = (outer, inner) + shape[1:]                                # raises where NumPy would have to copy
         return y
 
     def _time_blocks(self, T: int):
@@ -1116,6 +1142,134 @@ class Dataset(DotDict):
                     cnt = min(step, n_ue - ub)
                     yield b + i, ub, eng.channels_to_host(prep, variant=variant, user_begin=i * n_ue + ub, user_count=cnt)
 
+    # -------------------------------------------------------------- UE receive combining (extension)
+    def with_rx_combiner(self, codebook="dft", params: Optional[ChannelGenParameters] = None) -> "Dataset":
+        """The dataset behind a UE combining codebook W [Q, M_rx] as a plain Dataset of Q * n_ue single-antenna users,
+        combiner-major: row q * n_ue + u is user u behind row q, the UE beam q (extension).  Every ``compute_*`` works on
+        it unchanged and gives what it would give for ``W[q] @ H[u]``, with no [n_ue, M_rx, ...] tensor written.
+
+        A combiner row multiplies the complex gain of each path and nothing else:
+
+            e[u, q, l]  = sum_r W[q, r] exp(j 2 pi spacing (y_r sin theta sin phi + z_r cos theta))      # r = y + Mh z
+            power[q, u, l] = power[u, l] + 10 log10(max(|e|^2, 2^-100))
+            phase[q, u, l] = wrap(phase[u, l] + degrees(arg e))
+
+        in float64, rounded to float32 once (``deepmimo_amd.combiner``); W is applied without a conjugate, as
+        ``codebook @ H`` applies a BS codebook.  theta, phi are the arrival angles stage 1 gives for ``params`` (or the stored
+        parameters): rotated by the UE rotation and filtered by the field of view.  The angles themselves stay what they
+        are, so the UE rotation, the UE radiation pattern and ``ue_fov`` act in the view as they do in the parent; a path
+        without an angle keeps its stored power and phase.  ``codebook``: ``"dft"`` (``dm.dft_codebook`` of the UE panel) or
+        a finite complex array [Q, M_rx], Q >= 1; anything else raises ValueError before any GPU work.
+
+        Every public array whose first axis is the user axis is tiled (as ``at_times`` tiles it), shared objects are held
+        by reference, cached results are not carried; rays in HBM are combined there.  The view stores ``ch_params`` as a
+        copy of the parameters with ``ue_antenna.shape = [1, 1]`` (a per-user rotation [n_ue, 3] tiled to [Q * n_ue, 3]; a
+        (3, 2) rotation range keeps the parent's draw, tiled), ``rx_combiner`` [Q, M_rx], ``n_rx_beams`` and
+        ``n_ue_per_rx_beam``; ``split_rx_beams(x)`` gives a result [Q * n_ue, ...] as [Q, n_ue, ...].  The view is bound to
+        the UE array, rotation and field of view it was built with: parameters given to one of its calls have to keep
+        them, and a UE shape other than [1, 1] raises ValueError.  It composes with ``at_times`` in either order; the
+        outer view's split applies to the first axis."""
+        from .combiner import check_rx_codebook
+        params = self._call_params(params)
+        W = check_rx_codebook("with_rx_combiner", codebook, params[c.PARAMSET_ANT_UE][c.PARAMSET_ANT_SHAPE])
+        return self._rx_view(W, *self._rx_arrival_angles())
+
+    def _rx_arrival_angles(self):
+        """(theta, phi) of `with_rx_combiner` for the stored parameters: stage 1's rotated arrival zenith and azimuth in
+        radians, float64 [n_ue, L], NaN where the field of view masks the path (what ``aoa_el_rot_fov`` / ``aoa_az_rot_fov``
+        hold), where the rays live: NumPy arrays for host rays, tensors in HBM for rays in HBM."""
+        np.random.seed(1001)
+        _, prep = self._run_prep(want_side=True)
+        theta, phi, mask = prep.side["aoa_el_rot"], prep.side["aoa_az_rot"], prep.side["fov_mask"]
+        if mask is not None:
+            theta, phi = theta.masked_fill(mask == 0, float("nan")), phi.masked_fill(mask == 0, float("nan"))
+        if not hasattr(self[c.POWER_PARAM_NAME], "detach"):
+            theta, phi = theta.cpu().numpy(), phi.cpu().numpy()
+        return theta, phi
+
+    def _rx_view(self, W: np.ndarray, theta, phi, only=None) -> "Dataset":
+        """`with_rx_combiner` for the checked complex128 `W` [Q, M_rx] and the arrival angles of the stored parameters.
+        `only`: the public keys to carry (a block of `compute_beam_pair_power` carries what the call reads and no more)."""
+        from .combiner import combine_all
+        ue = self.ch_params[c.PARAMSET_ANT_UE]
+        power, phase = combine_all(self[c.POWER_PARAM_NAME], self[c.PHASE_PARAM_NAME], W, ue[c.PARAMSET_ANT_SHAPE],
+                                   float(ue[c.PARAMSET_ANT_SPACING]), theta, phi)
+        view = self._tiled_view(len(W), {c.POWER_PARAM_NAME: power, c.PHASE_PARAM_NAME: phase}, only, skip=_RX_KEYS)
+        d = view._data
+        d[c.CH_PARAMS_PARAM_NAME][c.PARAMSET_ANT_UE][c.PARAMSET_ANT_SHAPE] = np.array([1, 1])
+        d[_RX_COMBINER], d[_N_RX_BEAMS], d[_N_UE_PER_RX_BEAM] = W.copy(), len(W), int(self.n_ue)
+        return view
+
+    def split_rx_beams(self, x):
+        """A result of a ``compute_*`` on a view of ``with_rx_combiner`` - an array or tensor [Q * n_ue, ...], or a tuple or
+        dict of them - as [Q, n_ue, ...]: a view of the same memory, never a copy."""
+        Q, n = self._data.get(_N_RX_BEAMS), self._data.get(_N_UE_PER_RX_BEAM)
+        if Q is None:
+            raise ValueError("split_rx_beams: this dataset is not a view of with_rx_combiner")
+        return self._split_users("split_rx_beams", x, Q, n, "n_rx_beams * n_ue")
+
+    def compute_beam_pair_power(self, tx_codebook, rx_codebook="dft", params: Optional[ChannelGenParameters] = None,
+                                return_best: bool = False):
+        """Received power of every pair of a UE beam and a BS beam - the two-sided beam sweep in one call, with the semantics
+        of ``compute_beam_power`` and no channel or beam-space tensor written anywhere (extension).  For a BS codebook F
+        [B, M_tx] and a UE combining codebook W [Q, M_rx] (``"dft"``: ``dm.dft_codebook`` of the UE panel):
+
+            amp[u, q, b]    = np.abs(np.einsum('qr,urtk,bt->uqbk', W, dataset.channel, F)).mean(axis=-1)  # computed on the GPU
+            recv_bf_pwr_dbm = np.around(20 * np.log10(amp) + 30, 1), NaN where dataset.los == -1
+            best_rx, best_tx = np.unravel_index(argmax over (q, b), (Q, B)), the first maximum, as float; NaN where
+                               dataset.los == -1
+
+        Returns ``recv_bf_pwr_dbm`` float64 [n_ue, Q, B] (and ``best_rx``, ``best_tx`` with ``return_best``): NumPy arrays,
+        as ``compute_beam_power`` returns them.  The raw means stay available as ``dataset['beam_pair_mean_amplitude']``
+        (float32 [n_ue, Q, B]).  W is applied without a conjugate, like F.  It runs the beam-power kernel on the
+        ``with_rx_combiner`` view, a block of UE beams at a time.  A bad codebook on either side, the time domain,
+        ``rx_filter = 1`` or a subcarrier index beyond the bound of the beam entry points raise ValueError before any GPU
+        work."""
+        import torch
+        from .combiner import check_rx_codebook
+        from .engine import check_beam_bound, check_selection
+        who = "compute_beam_pair_power"
+        params = self._call_params(params)
+        bs_shape = params[c.PARAMSET_ANT_BS][c.PARAMSET_ANT_SHAPE]
+        m_tx = int(bs_shape[0]) * int(bs_shape[1])
+        W = check_rx_codebook(who, rx_codebook, params[c.PARAMSET_ANT_UE][c.PARAMSET_ANT_SHAPE])
+        F = tx_codebook if hasattr(tx_codebook, "shape") else np.asarray(tx_codebook)
+        if len(F.shape) != 2 or F.shape[1] != m_tx or F.shape[0] < 1:
+            raise ValueError(f"{who}: the BS codebook must be an array [B, {m_tx}] with B >= 1, got shape {tuple(F.shape)}")
+        if not params[c.PARAMSET_FD_CH]:
+            raise ValueError(f"{who}: needs the frequency-domain channel (freq_domain = 1)")
+        if params[c.PARAMSET_OFDM][c.PARAMSET_OFDM_LPF]:
+            raise ValueError(f"{who}: ofdm.rx_filter = 1 is not covered")
+        check_beam_bound(check_selection(params[c.PARAMSET_OFDM][c.PARAMSET_OFDM_SC_SAMP])[1])
+        src = self._in_hbm(_BLOCK_KEYS)                                    # the rays cross PCIe once, uncombined
+        theta, phi = src._rx_arrival_angles()
+        no_paths = src[c.LOS_PARAM_NAME] == -1
+        eng = _engine()
+        F = eng._codebook(F, m_tx, min_beams=1)
+        Q, n_ue, B = len(W), int(self.n_ue), int(F.shape[0])
+        amp = torch.empty((n_ue, Q, B), dtype=torch.float32, device=eng.device)
+        for b, nb in self._time_blocks(Q):
+            view = src._rx_view(W[b:b + nb], theta, phi, only=_BLOCK_KEYS)
+            np.random.seed(1001)
+            _, prep = view._run_prep(want_side="light")
+            # the block's small [nb, n_ue, B] result into its user-major place in HBM: a strided copy of the amplitudes alone
+            amp[:, b:b + nb] = eng.beam_power(prep, F, want_best=False)[0].view(nb, n_ue, B).permute(1, 0, 2)
+        amp = amp.cpu().numpy()
+        self._data["beam_pair_mean_amplitude"] = amp
+        # compute_beam_power's np.around(20 * np.log10(amp) + 30, 1) in float32, then float64: the same operations per
+        # element, in place on the one temporary - at 100k users x 4 x 64 pairs the passes over it are the cost of the call
+        with np.errstate(divide="ignore"):
+            dbm = np.log10(amp)
+        dbm *= 20
+        dbm += 30
+        pwr = np.around(dbm, 1, out=dbm).astype(np.float64)
+        pwr[no_paths] = np.nan
+        if not return_best:
+            return pwr
+        best_rx, best_tx = (v.astype(float) for v in np.divmod(np.argmax(pwr.reshape(n_ue, Q * B), axis=1), B))
+        best_rx[no_paths] = best_tx[no_paths] = np.nan
+        return pwr, best_rx, best_tx
+
     def get_active_idxs(self) -> np.ndarray:
         """Users with at least one path (dataset.py:775-781)."""
         return np.where(self.num_paths > 0)[0]
@@ -1192,7 +1346,7 @@ class Dataset(DotDict):
 class MacroDataset:
     """List of Datasets (one per TX / RX-set pair); attribute access and method calls fan out to
     every child, a single child returns its value unwrapped (dataset.py:888-998).  Methods of its own: `compute_cell_rate`
-    reads all children in one launch, `at_times` returns a MacroDataset of the children's views."""
+    reads all children in one launch, `at_times` and `with_rx_combiner` return a MacroDataset of the children's views."""
 
     SINGLE_ACCESS_METHODS = {"info"}
     PROPAGATE_METHODS = {name for name, _ in inspect.getmembers(Dataset, predicate=inspect.isfunction)
@@ -1277,6 +1431,22 @@ class MacroDataset:
         if not self.datasets:
             raise IndexError("MacroDataset is empty")
         return self.datasets[0].split_times(x)
+
+    def with_rx_combiner(self, codebook="dft", params=None) -> "MacroDataset":
+        """A MacroDataset of the children's ``Dataset.with_rx_combiner(codebook, params)`` views - Q * n_ue single-antenna
+        users each, combiner-major - so ``compute_cell_rate`` runs per UE beam (extension).  ``params``: one
+        ``ChannelGenParameters`` for all children, or a list with one per child.  ``split_rx_beams`` gives its results as
+        [Q, n_ue, ...]."""
+        plist = list(params) if isinstance(params, (list, tuple)) else [params] * len(self.datasets)
+        if len(plist) != len(self.datasets):
+            raise ValueError(f"with_rx_combiner: {len(plist)} parameter sets for {len(self.datasets)} children")
+        return MacroDataset([d.with_rx_combiner(codebook, prm) for d, prm in zip(self.datasets, plist)])
+
+    def split_rx_beams(self, x):
+        """``Dataset.split_rx_beams`` of the first child: the children of a view share the UE beams and the users."""
+        if not self.datasets:
+            raise IndexError("MacroDataset is empty")
+        return self.datasets[0].split_rx_beams(x)
 
     def __getitem__(self, idx):
         if isinstance(idx, (int, slice)):

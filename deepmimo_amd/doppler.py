@@ -88,6 +88,20 @@ def doppler_velocity(aoa_az, aoa_el, aod_az, aod_el, rx_vel: np.ndarray, tx_vel:
     return to_f32(-(along_rx + along_tx))
 
 
+def wrap_degrees(x):
+    """The float64 degrees `x` (NumPy or torch) wrapped into [-180, 180), in place; returns `x`."""
+    xp = _xp(x)
+    # x - 360 floor((x + 180) / 360): 360 k and the difference are exact in float64 (|x| stays far below 2^53 / 360),
+    # so only the choice of k can be off, by one float64 rounding at a boundary - -180 for +180, the same angle
+    k = x + 180.0
+    k /= 360.0
+    with np.errstate(invalid="ignore"):                                                    # NaN paths stay NaN, silently
+        xp.floor(k, out=k)
+    k *= 360.0
+    x -= k
+    return x
+
+
 def advance_phase(phase, vel, acc, times: np.ndarray, carrier_freq: float):
     """The phase matrices of the snapshots at `times` (float64 [T], seconds), time-major float32 [T * n_ue, n_paths]:
 
@@ -121,14 +135,7 @@ def advance_phase(phase, vel, acc, times: np.ndarray, carrier_freq: float):
         x *= scale
         still = x == 0
         x += p64
-        # x - 360 floor((x + 180) / 360): 360 k and the difference are exact in float64 (|x| stays far below 2^53 / 360),
-        # so only the choice of k can be off, by one float64 rounding at a boundary - -180 for +180, the same angle
-        k = x + 180.0
-        k /= 360.0
-        with np.errstate(invalid="ignore"):                                                # NaN paths stay NaN, silently
-            xp.floor(k, out=k)
-        k *= 360.0
-        x -= k
+        wrap_degrees(x)
         if out is None:                                                                    # the device: all snapshots at once
             out = xp.where(still, stored, f32(x))
         else:
