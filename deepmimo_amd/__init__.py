@@ -16,12 +16,12 @@ from .config import config
 from .general_utils import DotDict
 from .channel import ChannelGenParameters
 from .dataset import Dataset, MacroDataset
-from .geometry import dft_codebook, pattern_gain, steering_vec
+from .geometry import dft_codebook, pattern_gain, steering_vec, wideband_array_response
 from .combiner import combine_rays, combiner_response
 from .core import generate, load
 from .generator_utils import get_idxs_with_limits, LinearPath
 
 __version__ = consts.VERSION
 
-__all__ = ["generate", "load", "Dataset", "MacroDataset", "ChannelGenParameters", "config", "steering_vec", "dft_codebook",
+__all__ = ["generate", "load", "Dataset", "MacroDataset", "ChannelGenParameters", "config", "steering_vec", "wideband_array_response", "dft_codebook",
            "pattern_gain", "combiner_response", "combine_rays", "get_idxs_with_limits", "LinearPath", "DotDict", "consts"]

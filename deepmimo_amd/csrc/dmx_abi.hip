@@ -1,6 +1,7 @@
 // C-ABI entry points (include/deepmimo_amd.h): argument validation, workspace carving, error
 // string.  No allocation, no synchronisation, no global state besides the thread-local message.
 #include "dmx_common.h"
+#include <cmath>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -32,7 +33,9 @@ static int check_patterns(const dmx_params* p) {
     return DMX_OK;
 }
 
-static int check_params(const dmx_params* p) {
+// `wideband_ok`: the caller is one of the two entry points that take DMX_FLAG_SPATIAL_WIDEBAND (dmx_path_prep,
+// dmx_channels_fd); every other one, and every dmx_*_supported query, refuses the flag here
+static int check_params(const dmx_params* p, bool wideband_ok = false) {
     if (!p) { set_error("params is NULL"); return DMX_ERR_ARG; }
     for (int i = 0; i < 2; ++i) {
         if (p->bs_shape[i] < 1 || p->ue_shape[i] < 1) { set_error("antenna shape entries must be >= 1"); return DMX_ERR_SHAPE; }
@@ -42,7 +45,12 @@ static int check_params(const dmx_params* p) {
     }
     if (check_patterns(p)) return DMX_ERR_ARG;
     if (p->num_paths < 0) { set_error("num_paths must be >= 0"); return DMX_ERR_ARG; }
-    if ((p->flags & ~DMX_FLAG_ADAPTIVE_TERMS) != 0 || p->reserved0 != 0) { set_error("unknown bits in dmx_params.flags / reserved0"); return DMX_ERR_ARG; }
+    if ((p->flags & ~(DMX_FLAG_ADAPTIVE_TERMS | DMX_FLAG_SPATIAL_WIDEBAND)) != 0 || p->reserved0 != 0) { set_error("unknown bits in dmx_params.flags / reserved0"); return DMX_ERR_ARG; }
+    if ((p->flags & DMX_FLAG_SPATIAL_WIDEBAND) && !wideband_ok) {
+        set_error("DMX_FLAG_SPATIAL_WIDEBAND is taken by dmx_path_prep and dmx_channels_fd only: no other kernel forms a per-subcarrier "
+                  "array response");
+        return DMX_ERR_ARG;
+    }
     if (p->freq_domain) {
         if (p->n_subcarriers < 1) { set_error("ofdm.subcarriers must be >= 1"); return DMX_ERR_ARG; }
         if (p->n_selected < 0 || (p->n_selected > 0 && !p->selected_subcarriers)) {
@@ -212,7 +220,7 @@ float dmx_decode_max_delay(uint32_t key) {
 
 int dmx_path_prep(const dmx_rays* rays, const dmx_params* prm, void* workspace, size_t workspace_bytes,
                   const dmx_side* side, void* stream) {
-    int rc = check_params(prm);
+    int rc = check_params(prm, true);
     if (rc || (rc = check_rays(rays))) return rc;
     if (rays->n_ue > 0x7fffffffLL * 4) { set_error("too many users for one call"); return DMX_ERR_SHAPE; }
     const int P = used_paths(prm, rays->n_paths);
@@ -225,8 +233,8 @@ int dmx_path_prep(const dmx_rays* rays, const dmx_params* prm, void* workspace, 
 }
 
 static int stage2_common(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
-                         int64_t user_begin, int64_t user_count, void* out, WsView* ws) {
-    int rc = check_params(prm);
+                         int64_t user_begin, int64_t user_count, void* out, WsView* ws, bool wideband_ok = false) {
+    int rc = check_params(prm, wideband_ok);
     if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
     if (user_count > 0 && (!workspace || !out)) { set_error("workspace/out is NULL"); return DMX_ERR_ARG; }
     if ((rc = check_workspace_aligned(workspace)) || (rc = check_out_aligned(out))) return rc;
@@ -237,11 +245,23 @@ static int stage2_common(const dmx_params* prm, const void* workspace, int64_t n
 int dmx_channels_fd(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                     int64_t user_begin, int64_t user_count, void* out_c64, int32_t variant, void* stream) {
     WsView ws;
-    int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_c64, &ws);
+    int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_c64, &ws, true);
     if (rc) return rc;
     if (!prm->freq_domain) { set_error("dmx_channels_fd called with freq_domain = 0"); return DMX_ERR_ARG; }
     if (prm->rx_filter) { set_error("rx_filter = 1 is handled by dmx_channels_fd_lpf"); return DMX_ERR_ARG; }
     if (variant < 0 || variant > 12) { set_error("unknown variant %d", variant); return DMX_ERR_ARG; }
+    if (prm->flags & DMX_FLAG_SPATIAL_WIDEBAND) {
+        if (!(prm->carrier_freq > 0) || !std::isfinite(prm->carrier_freq) || !std::isfinite(prm->bandwidth)) {   // bandwidth > 0: check_params
+            set_error("DMX_FLAG_SPATIAL_WIDEBAND needs carrier_freq and bandwidth finite and > 0, got carrier_freq = %g, bandwidth = %g",
+                      prm->carrier_freq, prm->bandwidth);
+            return DMX_ERR_ARG;
+        }
+        if (variant > 1) {
+            set_error("DMX_FLAG_SPATIAL_WIDEBAND: variant %d refused, only the fp32 vector kernel (variant 0 or 1) forms a "
+                      "per-subcarrier array response", variant);
+            return DMX_ERR_SHAPE;
+        }
+    }
     if (variant >= 2 && variant != 9 && (rc = check_sc_bound_f32(prm, "matrix-core / folded variant"))) return rc;
     if (prm->n_selected == 0) return DMX_OK;
     return launch_channels_fd(*prm, ws, user_begin, user_count, (float2*)out_c64, variant, (hipStream_t)stream);
@@ -252,6 +272,7 @@ int dmx_fd_kernel_choice(const dmx_params* prm, int32_t n_paths_loaded) {
     if (n_paths_loaded < 0 || prm->n_selected < 0 || prm->bs_shape[0] < 1 || prm->bs_shape[1] < 1 || prm->ue_shape[0] < 1 ||
         prm->ue_shape[1] < 1) { set_error("bad shape"); return DMX_ERR_SHAPE; }
     if (check_patterns(prm)) return DMX_ERR_ARG;
+    if (prm->flags & DMX_FLAG_SPATIAL_WIDEBAND) return 1;
     WsView ws{};
     ws.P = used_paths(prm, n_paths_loaded);
     return fd_auto_choice(*prm, ws);

@@ -19,6 +19,7 @@
 // at the fp32 ridge of the chip (25 flop/B), so this kernel is VALU-bound; the MFMA variant
 // (k2_channel_fd_mfma.hip) removes that bound.  This one stays as the exact-fp32, any-shape path.
 #include "dmx_common.h"
+#include <type_traits>
 
 namespace dmx {
 
@@ -35,6 +36,11 @@ struct FdArgs {
     int l0;               // first path slot of this pass (users with more than 32 kept paths take several passes)
     int accumulate;       // 1: add to what earlier passes wrote
 };
+// the arguments of the spatial-wideband instantiations: the others keep FdArgs, and with it their kernel-argument layout
+struct FdArgsWb : FdArgs {
+    double sq;            // bandwidth / (carrier_freq * N): the squint of subcarrier k is sq * sc_k
+};
+template <bool WB> using FdArgsFor = std::conditional_t<WB, FdArgsWb, FdArgs>;
 
 // Everything one workgroup does for one user with LPA (multiple of 4) path slots; slots beyond the
 // user's n_act paths hold zero table entries, so the unrolled loops need no guards.
@@ -50,9 +56,108 @@ __device__ __forceinline__ void user_sync() {
     }
 }
 
-template <int LPA, int RB, bool GLOAD, int WPU>
-__device__ __forceinline__ void fd_user(const WsView& ws, const FdArgs& a, float2* __restrict__ o, int64_t u,
+// Spatial-wideband body (DMX_FLAG_SPATIAL_WIDEBAND): the array phase of every element is taken at the subcarrier's own
+// frequency, psi * s_k with s_k = 1 + sq * sc_k, so the array phasors differ per lane and no LDS table can hold them.
+//   out[r, t, k] = sum_l c_l exp(j 2pi ((psi_rx[r,l] + psi_tx[t,l]) s_k - q_l sc_k))
+// A lane keeps, per path, the running product p_l (all of the summand at the current transmit element) and the step rotor
+// w_l = exp(j 2pi tx_y[l] s_k): walking the panel along y is p_l *= w_l and the output is the sum of the p_l - a packed
+// multiply, a packed FMA and a packed add per (output, path) against the narrowband body's 2 packed FMAs.  p_l is seeded
+// from one float64 phase (receive element, z row, first y, delay: one frac_rev / sincos_rev) at the start of every z row
+// and every WB_RESEED steps along it, which bounds what the fp32 rotations add: per step the rotor's own phase error (the
+// float32 rounding of its reduced phase, 2pi * 3e-8, and 1.25e-7 of v_sin / v_cos) and the rounding of the product
+// (1.2e-7), so at most 15 * 5e-7 = 7e-6 of a path's amplitude in the worst case, all steps adding up, against the 5e-5
+// criterion.
+// LDS per user: q, tx_y, tx_z [LPA] and psi_rx [m_rx][LPA] in float64 (unreduced: the squint needs the whole revolutions),
+// c [LPA] as float2; slots beyond n_act hold c = 0 and zero phases.  No transmit table, so no tile loop over M_tx.
+constexpr int WB_RESEED = 16;
+
+template <int LPA, int WPU>
+__device__ __forceinline__ void fd_user_wideband(const WsView& ws, const FdArgsWb& a, float2* __restrict__ o, int64_t u,
+                                                 int n_act, unsigned char* smem) {
+    constexpr int NTU = WPU * 64;
+    double* q = reinterpret_cast<double*>(smem);                 // [LPA]  dn_l / N
+    double* ty = q + LPA;                                        // [LPA]  revolutions per y step of the BS panel
+    double* tz = ty + LPA;                                       // [LPA]
+    double* prx = tz + LPA;                                      // [m_rx][LPA]  psi_rx, revolutions
+    float2* cl = reinterpret_cast<float2*>(prx + (size_t)a.m_rx * LPA);   // [LPA]  path coefficient
+    const int tid = threadIdx.x % NTU, lane = tid & 63, wave = tid >> 6;
+    const size_t rb = (size_t)u * ws.P + a.l0;
+
+    for (int l = tid; l < LPA; l += NTU) {
+        const bool on = l < n_act;
+        q[l] = on ? (double)ws.dn[rb + l] * a.inv_n : 0.0;
+        ty[l] = on ? ws.tx_y[rb + l] : 0.0;
+        tz[l] = on ? ws.tx_z[rb + l] : 0.0;
+        cl[l] = on ? make_float2(ws.c_re[rb + l], ws.c_im[rb + l]) : make_float2(0.f, 0.f);
+    }
+    for (int i = tid; i < a.m_rx * LPA; i += NTU) {
+        const int r = i / LPA, l = i - r * LPA;
+        const int y = r % a.ue_mh, z = r / a.ue_mh;
+        prx[i] = l < n_act ? (double)y * ws.rx_y[rb + l] + (double)z * ws.rx_z[rb + l] : 0.0;
+    }
+    user_sync<WPU>();
+
+    const int nchunks = (a.K + 63) >> 6, bs_mv = a.m_tx / a.bs_mh;
+    for (int ch = wave; ch < nchunks; ch += WPU) {
+        const int kidx = (ch << 6) + lane;
+        const bool kok = kidx < a.K;
+        const double kk = (double)(kok ? a.sc[kidx] : 0);
+        const double sk = 1.0 + a.sq * kk;                       // f_k / f_c
+        v2f w[LPA];                                              // step rotor along y, (re, im)
+#pragma unroll
+        for (int l = 0; l < LPA; ++l) {
+            float s, c;
+            sincos_rev(frac_rev(ty[l] * sk), s, c);
+            w[l] = v2f{c, s};
+            __builtin_amdgcn_sched_barrier(0);                   // one phasor at a time: keeps live temporaries low
+        }
+        for (int r = 0; r < a.m_rx; ++r) {
+            const double* prow = prx + (size_t)r * LPA;
+            for (int z = 0; z < bs_mv; ++z) {
+                for (int y0 = 0; y0 < a.bs_mh; y0 += WB_RESEED) {
+                    const int y1 = (a.bs_mh - y0) < WB_RESEED ? a.bs_mh : y0 + WB_RESEED;
+                    const double zz = (double)z, yy = (double)y0;
+                    v2f p[LPA];
+                    // The table reads are wave-uniform and loop-invariant: hoisted out of the panel loops they would take
+                    // 10 registers per path and push p and w to scratch.  An offset the compiler cannot see through keeps
+                    // them where they are used, one path at a time (LDS broadcast reads, as in the narrowband body).
+                    int t0 = 0;
+                    asm volatile("" : "+s"(t0));
+#pragma unroll
+                    for (int l = 0; l < LPA; ++l) {
+                        float s, c;
+                        sincos_rev(frac_rev((prow[t0 + l] + zz * tz[t0 + l] + yy * ty[t0 + l]) * sk - q[t0 + l] * kk), s, c);
+                        const float2 cc = cl[t0 + l];
+                        p[l] = v2f{cc.x * c - cc.y * s, cc.x * s + cc.y * c};
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    int y = y0;                                 // y0 < y1: a loop the compiler knows to run, so that the seed
+                    do {                                        // is computed above it, path by path, and not sunk below its test
+                        if (y != y0) {
+#pragma unroll
+                            for (int l = 0; l < LPA; ++l)
+                                p[l] = __builtin_elementwise_fma(v2f{-p[l].y, p[l].x}, v2f{w[l].y, w[l].y}, p[l] * v2f{w[l].x, w[l].x});
+                        }
+                        v2f accA = v2f{0.f, 0.f}, accB = v2f{0.f, 0.f};
+#pragma unroll
+                        for (int l = 0; l < LPA; l += 2) { accA += p[l]; accB += p[l + 1]; }
+                        if (kok) {
+                            float2* dst = o + ((size_t)r * a.m_tx + ((size_t)z * a.bs_mh + y)) * a.K + kidx;
+                            float2 v = make_float2(accA.x + accB.x, accA.y + accB.y);
+                            if (a.accumulate) { const float2 prev = *dst; v.x += prev.x; v.y += prev.y; }
+                            *dst = v;
+                        }
+                    } while (++y < y1);
+                }
+            }
+        }
+    }
+}
+
+template <int LPA, int RB, bool GLOAD, int WPU, bool WB>
+__device__ __forceinline__ void fd_user(const WsView& ws, const FdArgsFor<WB>& a, float2* __restrict__ o, int64_t u,
                                         int64_t u_local, int n_act, unsigned char* smem) {
+    if constexpr (WB) { fd_user_wideband<LPA, WPU>(ws, a, o, u, n_act, smem); return; }
     constexpr int NTU = WPU * 64;                               // threads working on this user
     double* q = reinterpret_cast<double*>(smem);                 // [LPA]  dn_l / N
     float* brx = reinterpret_cast<float*>(q + LPA);             // [m_rx][2*LPA]
@@ -166,8 +271,9 @@ __device__ __forceinline__ void fd_user(const WsView& ws, const FdArgs& a, float
 // WPU = waves per user: 4 (one user per 256-thread workgroup) or 1 (four users per workgroup, one wave each,
 // no workgroup barrier) for shapes whose subcarriers fit one 64-lane chunk - there three of four waves would
 // idle and the per-workgroup fixed costs (launch, table build, barriers) dominate the tiny per-user work.
-template <int LPMAX, int RB, bool GLOAD, int WPU>
-__global__ __launch_bounds__(256, 2) void k2_fd_valu(WsView ws, FdArgs a, float2* __restrict__ out, int64_t user_count,
+// WB: the spatial-wideband body above in place of the narrowband one (its own instantiations: the others compile as before).
+template <int LPMAX, int RB, bool GLOAD, int WPU, bool WB = false>
+__global__ __launch_bounds__(256, 2) void k2_fd_valu(WsView ws, FdArgsFor<WB> a, float2* __restrict__ out, int64_t user_count,
                                                      int smem_per_user) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
     constexpr int UPW = 4 / WPU, NTU = WPU * 64;
@@ -186,14 +292,14 @@ __global__ __launch_bounds__(256, 2) void k2_fd_valu(WsView ws, FdArgs a, float2
         return;
     }
     const int n4 = (n_act + 3) >> 2;
-    if constexpr (LPMAX >= 32) { if (n4 == 8) { fd_user<32, RB, GLOAD, WPU>(ws, a, o, u, ul, n_act, smem); return; } }
-    if constexpr (LPMAX >= 28) { if (n4 == 7) { fd_user<28, RB, GLOAD, WPU>(ws, a, o, u, ul, n_act, smem); return; } }
-    if constexpr (LPMAX >= 24) { if (n4 == 6) { fd_user<24, RB, GLOAD, WPU>(ws, a, o, u, ul, n_act, smem); return; } }
-    if constexpr (LPMAX >= 20) { if (n4 == 5) { fd_user<20, RB, GLOAD, WPU>(ws, a, o, u, ul, n_act, smem); return; } }
-    if constexpr (LPMAX >= 16) { if (n4 == 4) { fd_user<16, RB, GLOAD, WPU>(ws, a, o, u, ul, n_act, smem); return; } }
-    if constexpr (LPMAX >= 12) { if (n4 == 3) { fd_user<12, RB, GLOAD, WPU>(ws, a, o, u, ul, n_act, smem); return; } }
-    if constexpr (LPMAX >= 8) { if (n4 == 2) { fd_user<8, RB, GLOAD, WPU>(ws, a, o, u, ul, n_act, smem); return; } }
-    fd_user<4, RB, GLOAD, WPU>(ws, a, o, u, ul, n_act, smem);
+    if constexpr (LPMAX >= 32) { if (n4 == 8) { fd_user<32, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem); return; } }
+    if constexpr (LPMAX >= 28) { if (n4 == 7) { fd_user<28, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem); return; } }
+    if constexpr (LPMAX >= 24) { if (n4 == 6) { fd_user<24, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem); return; } }
+    if constexpr (LPMAX >= 20) { if (n4 == 5) { fd_user<20, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem); return; } }
+    if constexpr (LPMAX >= 16) { if (n4 == 4) { fd_user<16, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem); return; } }
+    if constexpr (LPMAX >= 12) { if (n4 == 3) { fd_user<12, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem); return; } }
+    if constexpr (LPMAX >= 8) { if (n4 == 2) { fd_user<8, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem); return; } }
+    fd_user<4, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem);
 }
 
 template <int LP, int RB, bool GLOAD, int WPU>
@@ -227,6 +333,26 @@ static int launch_valu(const WsView& ws, const FdArgs& a, int64_t user_count, fl
     return launch_valu_w<LP, RB, GLOAD, 4>(ws, a, user_count, out, stream);
 }
 
+// the spatial-wideband body: RB = 1, no transmit table; one wave per user by the rule of launch_valu
+template <int LP, int WPU>
+static int launch_valu_wb_w(const WsView& ws, const FdArgsWb& a, int64_t user_count, float2* out, hipStream_t stream) {
+    constexpr int UPW = 4 / WPU;
+    const size_t per_user = align_up((size_t)LP * 8 * (4 + (size_t)a.m_rx), 16);
+    if (per_user * UPW > 64 * 1024) {
+        set_error("UE array of %d elements does not fit the LDS tables of the spatial-wideband body (max %d)", a.m_rx, (64 * 1024) / (8 * LP) - 4);
+        return DMX_ERR_SHAPE;
+    }
+    const int64_t blocks = (user_count + UPW - 1) / UPW;
+    return launch_dyn_lds(k2_fd_valu<LP, 1, false, WPU, true>, "k2_fd_valu", dim3((unsigned)blocks), dim3(256), per_user * UPW, LDS_NO_RAISE,
+                          stream, ws, a, out, user_count, (int)per_user);
+}
+
+template <int LP>
+static int launch_valu_wb(const WsView& ws, const FdArgsWb& a, int64_t user_count, float2* out, hipStream_t stream) {
+    if (a.m_rx * a.m_tx <= 8) return launch_valu_wb_w<LP, 1>(ws, a, user_count, out, stream);   // at most 3 KB of tables per user
+    return launch_valu_wb_w<LP, 4>(ws, a, user_count, out, stream);
+}
+
 static int launch_fd_valu_any(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
                               const float2* gtab, float2* out, hipStream_t stream, int l0 = 0, int accumulate = 0) {
     FdArgs a;
@@ -242,6 +368,15 @@ static int launch_fd_valu_any(const dmx_params& prm, const WsView& ws, int64_t u
     a.txt = 0;
     a.gtab = gtab;
     const int P = (ws.P - l0) < 32 ? (ws.P - l0) : 32;       // path slots of this pass
+    if (prm.flags & DMX_FLAG_SPATIAL_WIDEBAND) {               // never with a gains table: dmx_channels_fd_lpf refuses the flag
+        FdArgsWb w;
+        static_cast<FdArgs&>(w) = a;
+        w.sq = prm.bandwidth / prm.carrier_freq / (double)prm.n_subcarriers;
+        if (P <= 8) return launch_valu_wb<8>(ws, w, user_count, out, stream);
+        if (P <= 16) return launch_valu_wb<16>(ws, w, user_count, out, stream);
+        if (P <= 28) return launch_valu_wb<28>(ws, w, user_count, out, stream);
+        return launch_valu_wb<32>(ws, w, user_count, out, stream);
+    }
     // RB = receive elements sharing one a_tx row read.  2 halves the LDS traffic but doubles the t
     // registers; beyond 16 path slots that would spill, so the long-path bodies use RB = 1.
     const bool rb2 = a.m_rx >= 2;
@@ -274,8 +409,9 @@ static int launch_extra_path_passes(const dmx_params& prm, const WsView& ws, int
 
 // what variant 0 runs for this shape: 9 small-output kernel, 12 folded matrix-core kernel (few antenna pairs, uniformly
 // spaced subcarriers), 2 matrix cores, 1 fp32 vector kernel.  Indices at or beyond DMX_SC_ABS_MAX_F32: only the
-// float64-phase kernels, 9 and 1
+// float64-phase kernels, 9 and 1.  DMX_FLAG_SPATIAL_WIDEBAND: 1, whatever the shape
 int fd_auto_choice(const dmx_params& prm, const WsView& ws) {
+    if (prm.flags & DMX_FLAG_SPATIAL_WIDEBAND) return 1;       // only the vector kernel forms a per-subcarrier array response
     if (sc_beyond_f32(prm)) return fd_small_preferred(prm, ws) ? 9 : 1;
     if (fd_fold_preferred(prm, ws)) return 12;
     if (fd_small_preferred(prm, ws)) return 9;
@@ -286,6 +422,7 @@ int fd_auto_choice(const dmx_params& prm, const WsView& ws) {
 int launch_channels_fd(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
                        float2* out, int variant, hipStream_t stream) {
     if (user_count == 0) return DMX_OK;
+    if (prm.flags & DMX_FLAG_SPATIAL_WIDEBAND) variant = 1;    // dmx_channels_fd has refused every explicit variant but 1
     if (variant >= 2 && variant != 9 && variant != 12 && !fd_mfma_supported(prm, ws)) {
         set_error("MFMA variant does not support this shape");
         return DMX_ERR_SHAPE;

@@ -278,15 +278,27 @@ class Dataset(DotDict):
         self._data[_PATTERNS_IN_EFFECT] = pats
         return params
 
-    def _prep_inputs(self):
-        """(engine, parameters stage 1 runs with, uploaded rays, prepare keywords) of a GPU pass on this dataset."""
+    def _prep_inputs(self, wideband_fc=None):
+        """(engine, parameters stage 1 runs with, uploaded rays, prepare keywords) of a GPU pass on this dataset.
+        `wideband_fc`: the carrier frequency of a spatial-wideband call (`_wideband_carrier`), None for every other call."""
         eng = _engine()
         params = self._params_for_prep()
         rays = eng.upload_rays(self)
         kw = dict(bs_fov=self._data.get("bs_fov"), ue_fov=self._data.get("ue_fov"),
                   ue_rotation_per_user=self._resolved_ue_rotation(), carrier_freq=self._carrier_freq(),
                   adaptive_terms=bool(config.get("adaptive_precision", False)))
+        if wideband_fc is not None:
+            kw.update(carrier_freq=wideband_fc, spatial_wideband=True)
         return eng, params, rays, kw
+
+    def _wideband_carrier(self, params, spatial_wideband, carrier_freq):
+        """The checks of a channel call with ``spatial_wideband`` before any GPU work (engine.check_wideband_call): the
+        carrier frequency in Hz - `carrier_freq`, else rt_params.frequency - or None when the keyword is off."""
+        if not spatial_wideband:
+            return None
+        from .engine import check_wideband_call
+        fc = self._carrier_freq() if carrier_freq is None else carrier_freq
+        return check_wideband_call(params, fc, config.get("fd_kernel_variant", 0))
 
     def _run_prep(self, want_side=True, inputs=None, structs=None):
         """Stage 1 on the GPU; refreshes every per-path side product in the cache.  want_side="light" computes LoS,
@@ -308,7 +320,7 @@ class Dataset(DotDict):
         eng, params, rays, kw = inputs
         cfg = (config.get("single_pass", "auto"), config.get("fd_kernel_variant", 0), config.get("adaptive_precision", False))
         # what needs no struct first: a call that cannot be routed pays nothing for the question
-        if not params[c.PARAMSET_FD_CH] or not single_pass_route(*cfg, True, 9, True):
+        if not params[c.PARAMSET_FD_CH] or not single_pass_route(*cfg, True, 9, True, spatial_wideband=kw.get("spatial_wideband", False)):
             return None, None
         structs = eng._call_structs(rays, params, **kw)
         p = structs[0]
@@ -392,22 +404,31 @@ class Dataset(DotDict):
     def __setstate__(self, state):
         object.__setattr__(self, "_data", state["_data"])
 
-    def compute_channels(self, params: Optional[ChannelGenParameters] = None, *, times=None, carrier_freq=None):
+    def compute_channels(self, params: Optional[ChannelGenParameters] = None, *, spatial_wideband: bool = False,
+                         carrier_freq=None, times=None):
         """dataset.py:224-268.  Returns complex64 [n_ue, M_rx, M_tx, K] (freq_domain) or
         [n_ue, M_rx, M_tx, num_paths]: a NumPy array by default, the HBM-resident torch tensor when
         ``config('channel_output') == 'torch'``.  Cached as ``dataset.channel``.
 
         ``times`` (keyword, extension): a 1-D array of T seconds gives the snapshots of ``at_times(times, carrier_freq)``
         as [T, n_ue, M_rx, M_tx, K], time-major - ``out[t]`` has the layout of one call - and a scalar the one snapshot
-        without the leading axis; nothing is cached then.  A per-user [n_ue, 3] UE rotation holds for every snapshot."""
+        without the leading axis; nothing is cached then.  A per-user [n_ue, 3] UE rotation holds for every snapshot.
+
+        ``spatial_wideband`` (keyword, extension): the array response of every element is taken at the subcarrier's own
+        frequency ``f_c + sc_k B / N`` instead of at the carrier (beam squint; include/deepmimo_amd.h
+        DMX_FLAG_SPATIAL_WIDEBAND).  ``f_c``: ``carrier_freq``, else ``rt_params.frequency`` - it is then the carrier of the
+        Doppler term too.  Frequency domain without rx_filter, ``config('fd_kernel_variant')`` 0 or 1 (the fp32 vector
+        kernel runs either way); anything else, or no carrier frequency, raises ValueError before any GPU work.  It composes
+        with ``times``, the views of ``at_times`` / ``with_rx_combiner``, ``enable_doppler`` and ``adaptive_precision``."""
         if times is not None:
-            return self._channels_over_time(params, times, carrier_freq)
+            return self._channels_over_time(params, times, carrier_freq, spatial_wideband)
         params = self._call_params(params)
+        wideband_fc = self._wideband_carrier(params, spatial_wideband, carrier_freq)
         np.random.seed(1001)                                                   # dataset.py:250
         to_host = config.get("channel_output", "numpy") != "torch"
         if to_host:                                                            # before any GPU work is spent on it
             self._guard_host_copy(8 * int(np.prod(self._channel_shape(params))))
-        out, max_delay = self._channels_once(params, to_host)
+        out, max_delay = self._channels_once(params, to_host, wideband_fc=wideband_fc)
         ofdm = params[c.PARAMSET_OFDM]
         if params[c.PARAMSET_FD_CH]:
             self._warn_symbol_duration(max_delay, ofdm)
@@ -420,11 +441,11 @@ class Dataset(DotDict):
         last = len(np.atleast_1d(ofdm_[c.PARAMSET_OFDM_SC_SAMP])) if params[c.PARAMSET_FD_CH] else int(params[c.PARAMSET_NUM_PATHS])
         return int(self.n_ue), n_ant[1], n_ant[0], last
 
-    def _channels_once(self, params, to_host: bool, out=None):
+    def _channels_once(self, params, to_host: bool, out=None, wideband_fc=None):
         """The GPU part of `compute_channels` for the stored parameters `params`: the single pass where it applies, else
         stage 1 and stage 2.  Returns (channels, the delay maximum or None in the time domain).  `out`: the resident
-        tensor to write into (not with `to_host`)."""
-        inputs = self._prep_inputs()
+        tensor to write into (not with `to_host`).  `wideband_fc`: as for `_prep_inputs`."""
+        inputs = self._prep_inputs(wideband_fc)
         direct, structs = self._run_single_pass(inputs, to_host, out)
         if direct is not None:
             return direct
@@ -433,21 +454,23 @@ class Dataset(DotDict):
         H = eng.channels_to_host(prep, variant=variant) if to_host else eng.channels(prep, out=out, variant=variant)
         return H, (eng.max_delay(prep) if params[c.PARAMSET_FD_CH] else None)
 
-    def iter_channels(self, params: Optional[ChannelGenParameters] = None, chunk_users: int = 4096, *, times=None,
-                      carrier_freq=None):
+    def iter_channels(self, params: Optional[ChannelGenParameters] = None, chunk_users: int = 4096, *,
+                      spatial_wideband: bool = False, carrier_freq=None, times=None):
         """Generate channels in user chunks (extension): yields ``(user_begin, H_chunk)`` with ``H_chunk`` a
         NumPy complex64 array [<= chunk_users, M_rx, M_tx, K].  For scenarios whose full tensor (1 MB per user at
         64x4 antennas x 512 subcarriers) fits neither host memory nor one NumPy array; stage 1 runs once, stage 2
         per chunk through the C-ABI's user_begin / user_count range.  Nothing is cached as ``channel``.
 
         With ``times`` (keyword; as in ``compute_channels``) it yields ``(t_index, user_begin, H_chunk)``, the snapshots
-        in order and the users of a snapshot in order; stage 1 runs once per block of snapshots."""
+        in order and the users of a snapshot in order; stage 1 runs once per block of snapshots.  ``spatial_wideband``: as
+        in ``compute_channels``."""
         if times is not None:
-            yield from self._iter_channels_over_time(params, chunk_users, times, carrier_freq)
+            yield from self._iter_channels_over_time(params, chunk_users, times, carrier_freq, spatial_wideband)
             return
         params = self._call_params(params)
+        wideband_fc = self._wideband_carrier(params, spatial_wideband, carrier_freq)
         np.random.seed(1001)
-        eng, prep = self._run_prep(want_side="light")
+        eng, prep = self._run_prep(want_side="light", inputs=self._prep_inputs(wideband_fc))
         n = prep.n_ue
         variant = int(config.get("fd_kernel_variant", 0))
         for b in range(0, n, max(1, int(chunk_users))):
@@ -1093,10 +1116,11 @@ class Dataset(DotDict):
         view._call_params(self._tiled_params(params, len(t)))
         return view
 
-    def _channels_over_time(self, params, times, carrier_freq):
+    def _channels_over_time(self, params, times, carrier_freq, spatial_wideband=False):
         """`compute_channels(times=...)`: one stage 1 and one stage 2 (or one single pass) per block of snapshots, written
         time-major where they are returned from - no channel-sized tensor is ever transposed."""
         params, t, scalar, fc = self._time_call("compute_channels", params, times, carrier_freq)
+        wideband_fc = self._wideband_carrier(params, spatial_wideband, fc)
         to_host = config.get("channel_output", "numpy") != "torch"
         shape = self._channel_shape(params)
         if not params[c.PARAMSET_FD_CH]:
@@ -1116,7 +1140,7 @@ class Dataset(DotDict):
                     out = torch.empty((T,) + shape, dtype=torch.complex64, device=_engine().device)
                 dst = out[b:b + nb].view((nb * n_ue,) + shape[1:])
             np.random.seed(1001)
-            H, max_delay = view._channels_once(view.ch_params, to_host, out=dst)
+            H, max_delay = view._channels_once(view.ch_params, to_host, out=dst, wideband_fc=wideband_fc)
             if b == 0 and params[c.PARAMSET_FD_CH]:                            # the delays are those of every snapshot
                 self._warn_symbol_duration(max_delay, params[c.PARAMSET_OFDM])
             if len(blocks) == 1:
@@ -1127,16 +1151,17 @@ class Dataset(DotDict):
                 out[b:b + nb] = H.reshape((nb,) + shape)
         return out[0] if scalar else out
 
-    def _iter_channels_over_time(self, params, chunk_users, times, carrier_freq):
+    def _iter_channels_over_time(self, params, chunk_users, times, carrier_freq, spatial_wideband=False):
         """`iter_channels(times=...)`: stage 1 once per block of snapshots, stage 2 per snapshot and user chunk."""
         params, t, _, fc = self._time_call("iter_channels", params, times, carrier_freq)
+        wideband_fc = self._wideband_carrier(params, spatial_wideband, fc)
         n_ue, step = int(self.n_ue), max(1, int(chunk_users))
         variant = int(config.get("fd_kernel_variant", 0))
         src = self._in_hbm(_BLOCK_KEYS)
         for b, nb in self._time_blocks(len(t)):
             view = src._block_view("iter_channels", params, t[b:b + nb], fc)
             np.random.seed(1001)
-            eng, prep = view._run_prep(want_side="light")
+            eng, prep = view._run_prep(want_side="light", inputs=view._prep_inputs(wideband_fc))
             for i in range(nb):
                 for ub in range(0, n_ue, step):
                     cnt = min(step, n_ue - ub)

@@ -136,15 +136,16 @@ def single_pass_preferred(table_rows: int, loaded_paths: int, n_selected: int) -
 
 
 def single_pass_route(single_pass, fd_kernel_variant, adaptive_precision, direct_supported, auto_choice, one_piece,
-                      preferred=True) -> bool:
+                      preferred=True, spatial_wideband=False) -> bool:
     """Whether ``Dataset.compute_channels`` takes the single-pass kernel (dmx_channels_fd_direct) instead of stage 1 +
     stage 2.  All of: ``config('single_pass')`` is not False; the kernel variant is the automatic one (0) and adaptive
     precision is off; the library takes the shape (dmx_fd_direct_supported == 1); variant 0 would run the small-output
     kernel there (dmx_fd_kernel_choice == 9), so the arithmetic - and every output bit - is the one the two calls give;
     the tensor leaves in one piece (resident, or a host copy `channels_to_host` would not chunk); and, for 'auto', the
     shape is on the winning side of the measured crossover (`single_pass_preferred`).  ``single_pass = True`` takes the
-    route wherever it is possible, whatever the crossover says."""
-    if single_pass is False or single_pass is None or single_pass in (0, "off", "false", "False"):
+    route wherever it is possible, whatever the crossover says.  Never with ``spatial_wideband``: the single-pass kernel
+    has no per-subcarrier array response."""
+    if spatial_wideband or single_pass is False or single_pass is None or single_pass in (0, "off", "false", "False"):
         return False
     if int(fd_kernel_variant) != 0 or bool(adaptive_precision):
         return False
@@ -171,6 +172,34 @@ def check_beam_bound(sc_abs_max: int):
     if sc_abs_max >= SC_ABS_MAX_F32:
         raise ValueError(f"beam-space channels / beam power need every selected subcarrier |index| below {SC_ABS_MAX_F32} "
                          f"(DMX_SC_ABS_MAX_F32); the selection reaches {sc_abs_max}")
+
+
+WIDEBAND_VARIANTS = (0, 1)
+
+
+def check_wideband_call(params, carrier_freq, fd_kernel_variant=0) -> float:
+    """Everything a spatial-wideband channel call (DMX_FLAG_SPATIAL_WIDEBAND, include/deepmimo_amd.h) can refuse without a
+    GPU, as ValueError: time domain, rx_filter = 1, a carrier frequency that is missing or not finite and > 0, a bandwidth
+    that is not finite and > 0, and a kernel variant other than 0 or 1 (only the fp32 vector kernel forms a per-subcarrier
+    array response).  `params`: validated ChannelGenParameters.  Returns the carrier frequency in Hz."""
+    ofdm = params[c.PARAMSET_OFDM]
+    if not params[c.PARAMSET_FD_CH]:
+        raise ValueError("spatial_wideband: needs the frequency-domain channel (freq_domain = 1)")
+    if ofdm[c.PARAMSET_OFDM_LPF]:
+        raise ValueError("spatial_wideband: ofdm.rx_filter = 1 is not covered")
+    try:
+        fc = float(carrier_freq)
+    except (TypeError, ValueError):
+        fc = float("nan")
+    if not (math.isfinite(fc) and fc > 0):
+        raise ValueError("spatial_wideband: no carrier frequency: pass carrier_freq (Hz, finite and > 0) or set rt_params.frequency")
+    bw = float(ofdm[c.PARAMSET_OFDM_BANDWIDTH])
+    if not (math.isfinite(bw) and bw > 0):
+        raise ValueError(f"spatial_wideband: ofdm.bandwidth must be finite and > 0, got {bw!r}")
+    if int(fd_kernel_variant) not in WIDEBAND_VARIANTS:
+        raise ValueError(f"spatial_wideband: fd_kernel_variant {int(fd_kernel_variant)} is refused, only the fp32 vector kernel "
+                         f"(variant 0 or 1) forms a per-subcarrier array response")
+    return fc
 
 
 def covariance_side(side) -> int:
@@ -489,10 +518,12 @@ class ChannelEngine:
         return side, s
 
     def _call_structs(self, rays: DeviceRays, params, bs_fov=None, ue_fov=None, ue_rotation_per_user=None,
-                      carrier_freq: float = 0.0, adaptive_terms: bool = False):
+                      carrier_freq: float = 0.0, adaptive_terms: bool = False, spatial_wideband: bool = False):
         """The dmx_params / dmx_rays of a call on `rays` (shared by `prepare` and `channels_direct`): checks the
         selection, uploads it and the per-user rotation.  Returns (params struct, rays struct, tensors to keep alive,
-        largest |selected index|)."""
+        largest |selected index|).  spatial_wideband: DMX_FLAG_SPATIAL_WIDEBAND, after `check_wideband_call`."""
+        if spatial_wideband:
+            check_wideband_call(params, carrier_freq)
         dev = self.device
         n, L = rays.n_ue, rays.n_paths
         ofdm = params[c.PARAMSET_OFDM]
@@ -511,7 +542,7 @@ class ChannelEngine:
         have_dop = rays.doppler_vel is not None and rays.doppler_acc is not None
         p = self._params_struct(params, bs_fov, ue_fov, rot_dev, sel_dev, carrier_freq, have_dop,
                                 sc_hint=uniform_stride(sel))
-        p.flags = nat.FLAG_ADAPTIVE_TERMS if adaptive_terms else 0
+        p.flags = (nat.FLAG_ADAPTIVE_TERMS if adaptive_terms else 0) | (nat.FLAG_SPATIAL_WIDEBAND if spatial_wideband else 0)
 
         r = nat.DmxRays()
         r.n_ue, r.n_paths, r.ld = n, L, L
@@ -523,15 +554,18 @@ class ChannelEngine:
 
     # ------------------------------------------------------------------ stage 1
     def prepare(self, rays: DeviceRays, params, bs_fov=None, ue_fov=None, ue_rotation_per_user=None,
-                carrier_freq: float = 0.0, want_side=True, adaptive_terms: bool = False, structs=None) -> PrepResult:
+                carrier_freq: float = 0.0, want_side=True, adaptive_terms: bool = False, structs=None,
+                spatial_wideband: bool = False) -> PrepResult:
         """Run dmx_path_prep.  ue_rotation_per_user: optional [N, 3] degrees (numpy/torch).  want_side: True = every
         side product, "light" = LoS / path counts / FoV mask only, False = none.  adaptive_terms: opt into
         DMX_FLAG_ADAPTIVE_TERMS (include/deepmimo_amd.h: weak last path groups in one product term); the flag travels in
         the parameter block of the preparation, so every stage-2 call on it runs in the same mode.  structs: what
-        `_call_structs` returned for the same arguments, when the caller has built them already."""
+        `_call_structs` returned for the same arguments, when the caller has built them already.  spatial_wideband: opt
+        into DMX_FLAG_SPATIAL_WIDEBAND (the per-subcarrier array response; `carrier_freq` is then required): it travels in
+        the parameter block too, the records are the same, and `channels` on the preparation runs the wideband body."""
         n, L = rays.n_ue, rays.n_paths
         p, r, keep, sc_abs_max = structs or self._call_structs(rays, params, bs_fov, ue_fov, ue_rotation_per_user,
-                                                               carrier_freq, adaptive_terms)
+                                                               carrier_freq, adaptive_terms, spatial_wideband)
         keep = list(keep)
 
         nbytes = int(self.lib.dmx_workspace_bytes(C.byref(p), n, L))
@@ -547,8 +581,9 @@ class ChannelEngine:
 
     def fd_variant(self, prep: PrepResult, variant: int = 0) -> int:
         """The variant stage 2 runs for `variant` (bounded_fd_variant).  Beyond the bound without a spacing promise the
-        library cannot see the indices, so variant 0 is resolved here."""
-        if prep.sc_abs_max < SC_ABS_MAX_F32:
+        library cannot see the indices, so variant 0 is resolved here.  A spatial-wideband preparation runs the fp32 vector
+        kernel for variant 0 and 1 at any index; the library refuses every other variant."""
+        if prep.sc_abs_max < SC_ABS_MAX_F32 or prep.params_struct.flags & nat.FLAG_SPATIAL_WIDEBAND:
             return variant
         return bounded_fd_variant(int(variant), prep.sc_abs_max, self._small_preferred(prep.params_struct, prep.n_paths_loaded))
 

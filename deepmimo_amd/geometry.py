@@ -31,6 +31,27 @@ def steering_vec(array, phi: float = 0, theta: float = 0, spacing: float = 0.5) 
     return resp / np.linalg.norm(resp)
 
 
+def wideband_array_response(shape, spacing: float = 0.5, theta: float = 0, phi: float = 0, freq_ratio=1.0) -> np.ndarray:
+    """``steering_vec(shape, phi, theta, spacing)`` at another frequency (extension): the same expression with the element
+    spacing measured in wavelengths of ``freq_ratio * f_c``, i.e. ``spacing * freq_ratio``.  ``freq_ratio`` is
+    ``s_k = 1 + (bandwidth / carrier_freq) * sc_k / N`` for subcarrier ``sc_k`` of a spatial-wideband channel
+    (``compute_channels(spatial_wideband=True)``): a beam steered with ``steering_vec`` at the carrier meets this response
+    at the band edges, which is beam squint.  A scalar gives [M, 1] - with ``freq_ratio = 1`` exactly ``steering_vec`` - and
+    a 1-D array of K ratios [M, K], every column normalised."""
+    idx = _ant_indices(shape)
+    zen, az = phi * np.pi / 180, theta * np.pi / 180 + np.pi / 2
+    ratios = np.asarray(freq_ratio, dtype=np.float64)
+    if ratios.ndim > 1 or not np.all(np.isfinite(ratios)):
+        raise ValueError("wideband_array_response: freq_ratio must be a finite scalar or 1-D array")
+    cols = []
+    for f in ratios.reshape(-1):
+        kd = 2 * np.pi * (spacing * float(f))
+        gamma = 1j * kd * np.array([np.sin(zen) * np.cos(az), np.sin(zen) * np.sin(az), np.cos(zen)])
+        resp = np.exp(idx @ gamma).reshape(-1, 1)
+        cols.append(resp / np.linalg.norm(resp))
+    return np.concatenate(cols, axis=1) if cols else np.zeros((len(idx), 0), dtype=np.complex128)
+
+
 def pattern_gain(name: str, theta, phi=None):
     """Linear power gain of one antenna element with the radiation pattern `name`, as stage 1 applies it to a path
     (``power_linear_ant_gain = power_linear * g_tx * g_rx``): NumPy float64, angles in RADIANS in the panel's own frame

@@ -112,6 +112,29 @@ typedef struct dmx_params {
 
 #define DMX_FLAG_ADAPTIVE_TERMS 1u
 
+/* Spatial-wideband channel (beam squint): the array response of every element is taken at the subcarrier's own frequency
+ * f_c + sc_k B / N instead of at the carrier.  With c_l, dn_l as in dmx_channels_fd, psi_rx[r,l] = y_r rx_y[l] + z_r rx_z[l]
+ * and psi_tx[t,l] alike the element's steering phase in unreduced revolutions (spacing sin(th) sin(ph) per y step,
+ * spacing cos(th) per z step: what stage 1 writes), beta = bandwidth / carrier_freq and s_k = 1 + beta sc_k / N:
+ *   H_wb[u, r, t, k] = sum_l c_l exp(j 2pi (psi_rx[r,l] + psi_tx[t,l]) s_k) exp(-j 2pi dn_l sc_k / N)
+ * Equivalently element (r, t) sees path l with its own true delay tau_l - (psi_rx + psi_tx) / f_c: delays are referred to
+ * element 0 of each array, where the narrowband array response has zero phase.  sc_k = 0, or carrier_freq -> infinity,
+ * gives the narrowband channel.  Everything that acts per path is decided on the centre delay tau_l as without the flag:
+ * the clip at dn >= N, the field of view and the patterns, the Doppler term inside c_l, num_paths, compaction, LoS.
+ * The flag (value 4; 2 stays an unknown bit):
+ *   dmx_path_prep         accepts it; the records are the same bits as without it.
+ *   dmx_channels_fd       needs carrier_freq and bandwidth finite and > 0 (else DMX_ERR_ARG) and runs the fp32 vector
+ *                         kernel's per-subcarrier body for variant 0 and 1, the accumulate passes beyond 32 path slots
+ *                         included; any other explicit variant is DMX_ERR_SHAPE (the matrix-core, folded and small-output
+ *                         kernels rest on the separable form H = A G, which the squint removes).  Phases are reduced in
+ *                         float64: any int32 subcarrier index is valid.  May be combined with DMX_FLAG_ADAPTIVE_TERMS,
+ *                         which changes the order of a user's records only.
+ *   dmx_fd_kernel_choice  answers 1.
+ *   every other entry point that takes dmx_params (dmx_channels_fd_lpf, dmx_channels_td, dmx_channels_fd_beams,
+ *   dmx_beam_power, dmx_channels_fd_direct, every consumer) and every dmx_*_supported query: DMX_ERR_ARG, with the flag
+ *   named in dmx_last_error().  Not covered either: frequency-dependent element patterns and path gains, near field. */
+#define DMX_FLAG_SPATIAL_WIDEBAND 4u
+
 /* Subcarrier index bound of the float32-phase kernels.  The matrix-core and folded kernels (variants 2-5, 8, 10-12, the
  * beam entry points) reduce the phase dn k / N in float32 as qh (k mod 4096) + ql k, whose error grows linearly with
  * |k|: they meet the error claim above (~2e-6 of a user's peak) only while every selected |k| is below this bound.  The
