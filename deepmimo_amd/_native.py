@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("DMX_LIB_PATH") or os.path.join(os.path.dirname(os.pat
 ABI_VERSION = 3
 FLAG_ADAPTIVE_TERMS = 1
 FLAG_SPATIAL_WIDEBAND = 4                 # DMX_FLAG_SPATIAL_WIDEBAND: per-subcarrier array response (beam squint)
+FLAG_NEAR_FIELD = 16                      # DMX_FLAG_NEAR_FIELD: spherical-wavefront array response per path
 
 EXPORTED_SYMBOLS = ("dmx_version", "dmx_last_error", "dmx_workspace_bytes", "dmx_decode_max_delay",
                     "dmx_path_prep", "dmx_channels_fd", "dmx_channels_td", "dmx_channels_fd_lpf",

@@ -33,9 +33,9 @@ static int check_patterns(const dmx_params* p) {
     return DMX_OK;
 }
 
-// `wideband_ok`: the caller is one of the two entry points that take DMX_FLAG_SPATIAL_WIDEBAND (dmx_path_prep,
-// dmx_channels_fd); every other one, and every dmx_*_supported query, refuses the flag here
-static int check_params(const dmx_params* p, bool wideband_ok = false) {
+// `takes`: which of DMX_FLAG_SPATIAL_WIDEBAND (dmx_path_prep and dmx_channels_fd only) and DMX_FLAG_NEAR_FIELD (those two, the
+// consumers, dmx_beam_power and their dmx_*_supported queries) the caller takes; a flag it does not take is refused here
+static int check_params(const dmx_params* p, uint32_t takes = 0) {
     if (!p) { set_error("params is NULL"); return DMX_ERR_ARG; }
     for (int i = 0; i < 2; ++i) {
         if (p->bs_shape[i] < 1 || p->ue_shape[i] < 1) { set_error("antenna shape entries must be >= 1"); return DMX_ERR_SHAPE; }
@@ -45,8 +45,27 @@ static int check_params(const dmx_params* p, bool wideband_ok = false) {
     }
     if (check_patterns(p)) return DMX_ERR_ARG;
     if (p->num_paths < 0) { set_error("num_paths must be >= 0"); return DMX_ERR_ARG; }
-    if ((p->flags & ~(DMX_FLAG_ADAPTIVE_TERMS | DMX_FLAG_SPATIAL_WIDEBAND)) != 0 || p->reserved0 != 0) { set_error("unknown bits in dmx_params.flags / reserved0"); return DMX_ERR_ARG; }
-    if ((p->flags & DMX_FLAG_SPATIAL_WIDEBAND) && !wideband_ok) {
+    if ((p->flags & ~(DMX_FLAG_ADAPTIVE_TERMS | DMX_FLAG_SPATIAL_WIDEBAND | DMX_FLAG_NEAR_FIELD)) != 0 || p->reserved0 != 0) { set_error("unknown bits in dmx_params.flags / reserved0"); return DMX_ERR_ARG; }
+    if ((p->flags & DMX_FLAG_NEAR_FIELD) && (p->flags & DMX_FLAG_SPATIAL_WIDEBAND)) {
+        set_error("DMX_FLAG_NEAR_FIELD | DMX_FLAG_SPATIAL_WIDEBAND: the two are not covered together");
+        return DMX_ERR_ARG;
+    }
+    if (p->flags & DMX_FLAG_NEAR_FIELD) {
+        if (!(takes & DMX_FLAG_NEAR_FIELD)) {
+            set_error("DMX_FLAG_NEAR_FIELD is not taken here: the rx_filter, time-domain, beam-space channel and single-pass kernels "
+                      "build plane-wave array responses only");
+            return DMX_ERR_ARG;
+        }
+        if (!(p->carrier_freq > 0) || !std::isfinite(p->carrier_freq)) {
+            set_error("DMX_FLAG_NEAR_FIELD needs carrier_freq finite and > 0, got carrier_freq = %g", p->carrier_freq);
+            return DMX_ERR_ARG;
+        }
+        if (!(p->bandwidth > 0) || !std::isfinite(p->bandwidth)) {
+            set_error("DMX_FLAG_NEAR_FIELD needs bandwidth finite and > 0, got bandwidth = %g", p->bandwidth);
+            return DMX_ERR_ARG;
+        }
+    }
+    if ((p->flags & DMX_FLAG_SPATIAL_WIDEBAND) && !(takes & DMX_FLAG_SPATIAL_WIDEBAND)) {
         set_error("DMX_FLAG_SPATIAL_WIDEBAND is taken by dmx_path_prep and dmx_channels_fd only: no other kernel forms a per-subcarrier "
                   "array response");
         return DMX_ERR_ARG;
@@ -135,7 +154,7 @@ static dmx_side side_or_none(const dmx_side* side) {
 // domain under the entry point's name `fn`.
 static int consumer_args(const char* fn, const dmx_params* prm, const void* workspace, int64_t n_ue, int64_t user_begin,
                          int64_t user_count, const char* missing, const char* misaligned) {
-    int rc = check_params(prm);
+    int rc = check_params(prm, DMX_FLAG_NEAR_FIELD);
     if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
     if (user_count > 0 && missing) { set_error("%s", missing); return DMX_ERR_ARG; }
     if ((rc = check_workspace_aligned(workspace))) return rc;
@@ -160,7 +179,7 @@ static int shape_status(int shape) { return shape < 0 ? shape : shape == 0 ? DMX
 // a dmx_*_supported query: the parameter block, then the shape rule
 template <class Shape>
 static int supported(const dmx_params* prm, Shape shape) {
-    const int rc = check_params(prm);
+    const int rc = check_params(prm, DMX_FLAG_NEAR_FIELD);
     return rc ? rc : shape();
 }
 
@@ -220,7 +239,7 @@ float dmx_decode_max_delay(uint32_t key) {
 
 int dmx_path_prep(const dmx_rays* rays, const dmx_params* prm, void* workspace, size_t workspace_bytes,
                   const dmx_side* side, void* stream) {
-    int rc = check_params(prm, true);
+    int rc = check_params(prm, DMX_FLAG_SPATIAL_WIDEBAND | DMX_FLAG_NEAR_FIELD);
     if (rc || (rc = check_rays(rays))) return rc;
     if (rays->n_ue > 0x7fffffffLL * 4) { set_error("too many users for one call"); return DMX_ERR_SHAPE; }
     const int P = used_paths(prm, rays->n_paths);
@@ -233,8 +252,8 @@ int dmx_path_prep(const dmx_rays* rays, const dmx_params* prm, void* workspace, 
 }
 
 static int stage2_common(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
-                         int64_t user_begin, int64_t user_count, void* out, WsView* ws, bool wideband_ok = false) {
-    int rc = check_params(prm, wideband_ok);
+                         int64_t user_begin, int64_t user_count, void* out, WsView* ws, uint32_t takes = 0) {
+    int rc = check_params(prm, takes);
     if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
     if (user_count > 0 && (!workspace || !out)) { set_error("workspace/out is NULL"); return DMX_ERR_ARG; }
     if ((rc = check_workspace_aligned(workspace)) || (rc = check_out_aligned(out))) return rc;
@@ -245,7 +264,8 @@ static int stage2_common(const dmx_params* prm, const void* workspace, int64_t n
 int dmx_channels_fd(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                     int64_t user_begin, int64_t user_count, void* out_c64, int32_t variant, void* stream) {
     WsView ws;
-    int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_c64, &ws, true);
+    int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_c64, &ws,
+                           DMX_FLAG_SPATIAL_WIDEBAND | DMX_FLAG_NEAR_FIELD);
     if (rc) return rc;
     if (!prm->freq_domain) { set_error("dmx_channels_fd called with freq_domain = 0"); return DMX_ERR_ARG; }
     if (prm->rx_filter) { set_error("rx_filter = 1 is handled by dmx_channels_fd_lpf"); return DMX_ERR_ARG; }
@@ -262,6 +282,11 @@ int dmx_channels_fd(const dmx_params* prm, const void* workspace, int64_t n_ue, 
             return DMX_ERR_SHAPE;
         }
     }
+    if ((prm->flags & DMX_FLAG_NEAR_FIELD) && variant > 1) {
+        set_error("DMX_FLAG_NEAR_FIELD: variant %d refused, only the fp32 vector kernel (variant 0 or 1) builds spherical-wavefront "
+                  "array tables", variant);
+        return DMX_ERR_SHAPE;
+    }
     if (variant >= 2 && variant != 9 && (rc = check_sc_bound_f32(prm, "matrix-core / folded variant"))) return rc;
     if (prm->n_selected == 0) return DMX_OK;
     return launch_channels_fd(*prm, ws, user_begin, user_count, (float2*)out_c64, variant, (hipStream_t)stream);
@@ -272,7 +297,7 @@ int dmx_fd_kernel_choice(const dmx_params* prm, int32_t n_paths_loaded) {
     if (n_paths_loaded < 0 || prm->n_selected < 0 || prm->bs_shape[0] < 1 || prm->bs_shape[1] < 1 || prm->ue_shape[0] < 1 ||
         prm->ue_shape[1] < 1) { set_error("bad shape"); return DMX_ERR_SHAPE; }
     if (check_patterns(prm)) return DMX_ERR_ARG;
-    if (prm->flags & DMX_FLAG_SPATIAL_WIDEBAND) return 1;
+    if (prm->flags & (DMX_FLAG_SPATIAL_WIDEBAND | DMX_FLAG_NEAR_FIELD)) return 1;
     WsView ws{};
     ws.P = used_paths(prm, n_paths_loaded);
     return fd_auto_choice(*prm, ws);
@@ -351,7 +376,7 @@ int dmx_beam_power(const dmx_params* prm, const void* workspace, int64_t n_ue, i
                    void* beam_workspace, size_t beam_workspace_bytes_, float* out_mean_amp, int32_t* out_best_beam,
                    void* stream) {
     WsView ws;
-    int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_mean_amp, &ws);
+    int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_mean_amp, &ws, DMX_FLAG_NEAR_FIELD);
     if (rc) return rc;
     if ((rc = check_beam_call(prm, "dmx_beam_power", codebook_c64, n_beams, 1))) return rc;
     if (prm->n_selected < 1) { set_error("dmx_beam_power needs at least one selected subcarrier"); return DMX_ERR_ARG; }
@@ -483,7 +508,7 @@ static int links_in_range(int32_t n_links) { return n_links >= 1 && n_links <= D
 static int check_link_params(const dmx_link* links, int32_t n_links) {
     if (!links) { set_error("links is NULL"); return DMX_ERR_ARG; }
     for (int b = 0; b < links_in_range(n_links); ++b) {
-        if (int rc = check_params(links[b].prm)) return rc;
+        if (int rc = check_params(links[b].prm, DMX_FLAG_NEAR_FIELD)) return rc;
     }
     return DMX_OK;
 }
@@ -496,7 +521,7 @@ static int cell_rate_shape(const dmx_link* links, int32_t n_links) {
         return 0;
     }
     for (int b = 0; b < n_links; ++b) {
-        if (int rc = check_params(links[b].prm)) return rc;
+        if (int rc = check_params(links[b].prm, DMX_FLAG_NEAR_FIELD)) return rc;
         if (links[b].n_paths_loaded < 0) { set_error("link %d: n_paths_loaded must be >= 0", b); return DMX_ERR_ARG; }
     }
     const dmx_params* p0 = links[0].prm;

@@ -66,6 +66,7 @@ struct CbArgs {
     float inv_k;
     const float2* ftab;      // [user_count, C L, P] from k2b_beam_project
     int ld;                  // table row stride in path slots (= P)
+    NearField nf;            // DMX_FLAG_NEAR_FIELD (array_phase.h): the UE table here, the BS side inside ftab's rows
 };
 
 struct SbArgs {              // the subband form only
@@ -130,7 +131,7 @@ __device__ __forceinline__ void codebook_rate_body(const WsView& ws, const CbArg
         }
         return;
     }
-    const WsRecords rec{ws, (size_t)u * ws.P};
+    const WsRecords rec{ws, (size_t)u * ws.P, a.nf};
 
     // 1  the a_rx table
     fill_array_table(as, rec, true, 0, M, a.ue_mh, n, ld, lane);
@@ -351,6 +352,7 @@ static int launch_cb(const dmx_params& prm, const WsView& ws, int64_t user_begin
     CbArgs a;
     a.user_begin = user_begin; a.user_count = user_count;
     a.ue_mh = prm.ue_shape[0];
+    a.nf = near_field_of(prm);
     a.C = n_codewords; a.cpc = CB_ROWS / n_layers;
     a.K = prm.n_selected; a.kc = a.K < 64 ? a.K : 64;
     if (sb) {

@@ -19,6 +19,7 @@
 // at the fp32 ridge of the chip (25 flop/B), so this kernel is VALU-bound; the MFMA variant
 // (k2_channel_fd_mfma.hip) removes that bound.  This one stays as the exact-fp32, any-shape path.
 #include "dmx_common.h"
+#include "array_phase.h"
 #include <type_traits>
 
 namespace dmx {
@@ -40,7 +41,20 @@ struct FdArgs {
 struct FdArgsWb : FdArgs {
     double sq;            // bandwidth / (carrier_freq * N): the squint of subcarrier k is sq * sc_k
 };
-template <bool WB> using FdArgsFor = std::conditional_t<WB, FdArgsWb, FdArgs>;
+// ... of the near-field instantiations (DMX_FLAG_NEAR_FIELD): the narrowband body with spherical-wavefront table fills
+struct FdArgsNf : FdArgs {
+    NearField nf;
+};
+// MODE of k2_fd_valu: the narrowband body, the spatial-wideband body, the narrowband body with near-field tables
+constexpr int FD_FAR = 0, FD_WIDEBAND = 1, FD_NEAR = 2;
+template <int MODE> using FdArgsFor = std::conditional_t<MODE == FD_WIDEBAND, FdArgsWb, std::conditional_t<MODE == FD_NEAR, FdArgsNf, FdArgs>>;
+// the near-field block of one end: a compile-time "off" for every mode but FD_NEAR, so that array_phase folds to the
+// plane-wave expression there
+template <int MODE>
+__device__ __forceinline__ NearFieldEnd fd_near_field(const FdArgsFor<MODE>& a, const bool rx) {
+    if constexpr (MODE == FD_NEAR) return a.nf.end(rx);
+    else return NearFieldEnd{0, 0.0, 0.0};
+}
 
 // Everything one workgroup does for one user with LPA (multiple of 4) path slots; slots beyond the
 // user's n_act paths hold zero table entries, so the unrolled loops need no guards.
@@ -154,10 +168,11 @@ __device__ __forceinline__ void fd_user_wideband(const WsView& ws, const FdArgsW
     }
 }
 
-template <int LPA, int RB, bool GLOAD, int WPU, bool WB>
-__device__ __forceinline__ void fd_user(const WsView& ws, const FdArgsFor<WB>& a, float2* __restrict__ o, int64_t u,
+template <int LPA, int RB, bool GLOAD, int WPU, int MODE>
+__device__ __forceinline__ void fd_user(const WsView& ws, const FdArgsFor<MODE>& a, float2* __restrict__ o, int64_t u,
                                         int64_t u_local, int n_act, unsigned char* smem) {
-    if constexpr (WB) { fd_user_wideband<LPA, WPU>(ws, a, o, u, n_act, smem); return; }
+    if constexpr (MODE == FD_WIDEBAND) { fd_user_wideband<LPA, WPU>(ws, a, o, u, n_act, smem); return; }
+    const NearFieldEnd nf_rx = fd_near_field<MODE>(a, true), nf_tx = fd_near_field<MODE>(a, false);
     constexpr int NTU = WPU * 64;                               // threads working on this user
     double* q = reinterpret_cast<double*>(smem);                 // [LPA]  dn_l / N
     float* brx = reinterpret_cast<float*>(q + LPA);             // [m_rx][2*LPA]
@@ -172,7 +187,7 @@ __device__ __forceinline__ void fd_user(const WsView& ws, const FdArgsFor<WB>& a
         if (l < n_act) {
             const int y = r % a.ue_mh, z = r / a.ue_mh;
             float s, c;
-            sincos_rev(frac_rev((double)y * ws.rx_y[rb + l] + (double)z * ws.rx_z[rb + l]), s, c);
+            sincos_rev(frac_rev(array_phase<false>(y, z, ws.rx_y[rb + l], ws.rx_z[rb + l], MODE == FD_NEAR ? ws.dn[rb + l] : 0.f, nf_rx)), s, c);
             // with precomputed gains the path coefficient c_l is already inside g
             const float cr = GLOAD ? 1.0f : ws.c_re[rb + l], ci = GLOAD ? 0.0f : ws.c_im[rb + l];
             re = cr * c - ci * s;
@@ -191,7 +206,7 @@ __device__ __forceinline__ void fd_user(const WsView& ws, const FdArgsFor<WB>& a
             float s = 0.f, c = 0.f;
             if (l < n_act) {
                 const int m = tx0 + t, y = m % a.bs_mh, z = m / a.bs_mh;
-                sincos_rev(frac_rev((double)y * ws.tx_y[rb + l] + (double)z * ws.tx_z[rb + l]), s, c);
+                sincos_rev(frac_rev(array_phase<false>(y, z, ws.tx_y[rb + l], ws.tx_z[rb + l], MODE == FD_NEAR ? ws.dn[rb + l] : 0.f, nf_tx)), s, c);
             }
             atx[(size_t)t * 2 * LPA + 2 * l] = c;
             atx[(size_t)t * 2 * LPA + 2 * l + 1] = s;
@@ -271,9 +286,10 @@ __device__ __forceinline__ void fd_user(const WsView& ws, const FdArgsFor<WB>& a
 // WPU = waves per user: 4 (one user per 256-thread workgroup) or 1 (four users per workgroup, one wave each,
 // no workgroup barrier) for shapes whose subcarriers fit one 64-lane chunk - there three of four waves would
 // idle and the per-workgroup fixed costs (launch, table build, barriers) dominate the tiny per-user work.
-// WB: the spatial-wideband body above in place of the narrowband one (its own instantiations: the others compile as before).
-template <int LPMAX, int RB, bool GLOAD, int WPU, bool WB = false>
-__global__ __launch_bounds__(256, 2) void k2_fd_valu(WsView ws, FdArgsFor<WB> a, float2* __restrict__ out, int64_t user_count,
+// MODE: FD_WIDEBAND takes the spatial-wideband body above in place of the narrowband one, FD_NEAR the narrowband body with
+// near-field table fills (their own instantiations: the others compile as before).
+template <int LPMAX, int RB, bool GLOAD, int WPU, int MODE = FD_FAR>
+__global__ __launch_bounds__(256, 2) void k2_fd_valu(WsView ws, FdArgsFor<MODE> a, float2* __restrict__ out, int64_t user_count,
                                                      int smem_per_user) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
     constexpr int UPW = 4 / WPU, NTU = WPU * 64;
@@ -292,18 +308,18 @@ __global__ __launch_bounds__(256, 2) void k2_fd_valu(WsView ws, FdArgsFor<WB> a,
         return;
     }
     const int n4 = (n_act + 3) >> 2;
-    if constexpr (LPMAX >= 32) { if (n4 == 8) { fd_user<32, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem); return; } }
-    if constexpr (LPMAX >= 28) { if (n4 == 7) { fd_user<28, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem); return; } }
-    if constexpr (LPMAX >= 24) { if (n4 == 6) { fd_user<24, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem); return; } }
-    if constexpr (LPMAX >= 20) { if (n4 == 5) { fd_user<20, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem); return; } }
-    if constexpr (LPMAX >= 16) { if (n4 == 4) { fd_user<16, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem); return; } }
-    if constexpr (LPMAX >= 12) { if (n4 == 3) { fd_user<12, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem); return; } }
-    if constexpr (LPMAX >= 8) { if (n4 == 2) { fd_user<8, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem); return; } }
-    fd_user<4, RB, GLOAD, WPU, WB>(ws, a, o, u, ul, n_act, smem);
+    if constexpr (LPMAX >= 32) { if (n4 == 8) { fd_user<32, RB, GLOAD, WPU, MODE>(ws, a, o, u, ul, n_act, smem); return; } }
+    if constexpr (LPMAX >= 28) { if (n4 == 7) { fd_user<28, RB, GLOAD, WPU, MODE>(ws, a, o, u, ul, n_act, smem); return; } }
+    if constexpr (LPMAX >= 24) { if (n4 == 6) { fd_user<24, RB, GLOAD, WPU, MODE>(ws, a, o, u, ul, n_act, smem); return; } }
+    if constexpr (LPMAX >= 20) { if (n4 == 5) { fd_user<20, RB, GLOAD, WPU, MODE>(ws, a, o, u, ul, n_act, smem); return; } }
+    if constexpr (LPMAX >= 16) { if (n4 == 4) { fd_user<16, RB, GLOAD, WPU, MODE>(ws, a, o, u, ul, n_act, smem); return; } }
+    if constexpr (LPMAX >= 12) { if (n4 == 3) { fd_user<12, RB, GLOAD, WPU, MODE>(ws, a, o, u, ul, n_act, smem); return; } }
+    if constexpr (LPMAX >= 8) { if (n4 == 2) { fd_user<8, RB, GLOAD, WPU, MODE>(ws, a, o, u, ul, n_act, smem); return; } }
+    fd_user<4, RB, GLOAD, WPU, MODE>(ws, a, o, u, ul, n_act, smem);
 }
 
-template <int LP, int RB, bool GLOAD, int WPU>
-static int launch_valu_w(const WsView& ws, FdArgs a, int64_t user_count, float2* out, hipStream_t stream) {
+template <int LP, int RB, bool GLOAD, int WPU, int MODE = FD_FAR>
+static int launch_valu_w(const WsView& ws, FdArgsFor<MODE> a, int64_t user_count, float2* out, hipStream_t stream) {
     constexpr int UPW = 4 / WPU;
     const size_t fixed = (size_t)LP * 8 + (size_t)a.m_rx * 2 * LP * 4;
     const size_t budget = (64 * 1024) / UPW;                     // LDS share of one user
@@ -316,12 +332,12 @@ static int launch_valu_w(const WsView& ws, FdArgs a, int64_t user_count, float2*
     a.txt = txt;
     const size_t per_user = align_up(fixed + (size_t)txt * 2 * LP * 4, 16);
     const int64_t blocks = (user_count + UPW - 1) / UPW;
-    return launch_dyn_lds(k2_fd_valu<LP, RB, GLOAD, WPU>, "k2_fd_valu", dim3((unsigned)blocks), dim3(256), per_user * UPW, LDS_NO_RAISE,
+    return launch_dyn_lds(k2_fd_valu<LP, RB, GLOAD, WPU, MODE>, "k2_fd_valu", dim3((unsigned)blocks), dim3(256), per_user * UPW, LDS_NO_RAISE,
                           stream, ws, a, out, user_count, (int)per_user);
 }
 
-template <int LP, int RB, bool GLOAD = false>
-static int launch_valu(const WsView& ws, const FdArgs& a, int64_t user_count, float2* out, hipStream_t stream) {
+template <int LP, int RB, bool GLOAD = false, int MODE = FD_FAR>
+static int launch_valu(const WsView& ws, const FdArgsFor<MODE>& a, int64_t user_count, float2* out, hipStream_t stream) {
     // one wave per user (four users per workgroup, no workgroup barrier) for tiny panels, whatever the subcarrier
     // count: measured, 200k users x 25 paths, 8 pairs: K=64 1.89 -> 1.33 ms, K=128 4.07 -> 2.14, K=256 4.79 -> 3.71,
     // K=512 8.39 -> 6.95; 4 pairs x 256 3.36 -> 2.42.  From 9 pairs on the four-wave form (or the matrix cores) wins.
@@ -329,8 +345,8 @@ static int launch_valu(const WsView& ws, const FdArgs& a, int64_t user_count, fl
     // sin/cos was tried here: the kernel already spills at 256 VGPRs and the extra live state made it 2.4x slower.)
     const size_t need = (size_t)LP * 8 + (size_t)(a.m_rx + a.m_tx) * 2 * LP * 4;
     if (a.m_rx * a.m_tx <= 8 && need <= 16 * 1024 - 16)
-        return launch_valu_w<LP, RB, GLOAD, 1>(ws, a, user_count, out, stream);
-    return launch_valu_w<LP, RB, GLOAD, 4>(ws, a, user_count, out, stream);
+        return launch_valu_w<LP, RB, GLOAD, 1, MODE>(ws, a, user_count, out, stream);
+    return launch_valu_w<LP, RB, GLOAD, 4, MODE>(ws, a, user_count, out, stream);
 }
 
 // the spatial-wideband body: RB = 1, no transmit table; one wave per user by the rule of launch_valu
@@ -343,7 +359,7 @@ static int launch_valu_wb_w(const WsView& ws, const FdArgsWb& a, int64_t user_co
         return DMX_ERR_SHAPE;
     }
     const int64_t blocks = (user_count + UPW - 1) / UPW;
-    return launch_dyn_lds(k2_fd_valu<LP, 1, false, WPU, true>, "k2_fd_valu", dim3((unsigned)blocks), dim3(256), per_user * UPW, LDS_NO_RAISE,
+    return launch_dyn_lds(k2_fd_valu<LP, 1, false, WPU, FD_WIDEBAND>, "k2_fd_valu", dim3((unsigned)blocks), dim3(256), per_user * UPW, LDS_NO_RAISE,
                           stream, ws, a, out, user_count, (int)per_user);
 }
 
@@ -380,6 +396,15 @@ static int launch_fd_valu_any(const dmx_params& prm, const WsView& ws, int64_t u
     // RB = receive elements sharing one a_tx row read.  2 halves the LDS traffic but doubles the t
     // registers; beyond 16 path slots that would spill, so the long-path bodies use RB = 1.
     const bool rb2 = a.m_rx >= 2;
+    if (prm.flags & DMX_FLAG_NEAR_FIELD) {                     // never with a gains table either; the launch rules of the far field
+        FdArgsNf f;
+        static_cast<FdArgs&>(f) = a;
+        f.nf = near_field_of(prm);
+        if (P <= 8) return rb2 ? launch_valu<8, 2, false, FD_NEAR>(ws, f, user_count, out, stream) : launch_valu<8, 1, false, FD_NEAR>(ws, f, user_count, out, stream);
+        if (P <= 16) return rb2 ? launch_valu<16, 2, false, FD_NEAR>(ws, f, user_count, out, stream) : launch_valu<16, 1, false, FD_NEAR>(ws, f, user_count, out, stream);
+        if (P <= 28) return launch_valu<28, 1, false, FD_NEAR>(ws, f, user_count, out, stream);
+        return launch_valu<32, 1, false, FD_NEAR>(ws, f, user_count, out, stream);
+    }
     if (gtab) {
         if (P <= 8) return launch_valu<8, 1, true>(ws, a, user_count, out, stream);
         if (P <= 16) return launch_valu<16, 1, true>(ws, a, user_count, out, stream);
@@ -409,9 +434,10 @@ static int launch_extra_path_passes(const dmx_params& prm, const WsView& ws, int
 
 // what variant 0 runs for this shape: 9 small-output kernel, 12 folded matrix-core kernel (few antenna pairs, uniformly
 // spaced subcarriers), 2 matrix cores, 1 fp32 vector kernel.  Indices at or beyond DMX_SC_ABS_MAX_F32: only the
-// float64-phase kernels, 9 and 1.  DMX_FLAG_SPATIAL_WIDEBAND: 1, whatever the shape
+// float64-phase kernels, 9 and 1.  DMX_FLAG_SPATIAL_WIDEBAND, DMX_FLAG_NEAR_FIELD: 1, whatever the shape
 int fd_auto_choice(const dmx_params& prm, const WsView& ws) {
     if (prm.flags & DMX_FLAG_SPATIAL_WIDEBAND) return 1;       // only the vector kernel forms a per-subcarrier array response
+    if (prm.flags & DMX_FLAG_NEAR_FIELD) return 1;             // ... and, of the channel kernels, spherical-wavefront tables
     if (sc_beyond_f32(prm)) return fd_small_preferred(prm, ws) ? 9 : 1;
     if (fd_fold_preferred(prm, ws)) return 12;
     if (fd_small_preferred(prm, ws)) return 9;
@@ -422,7 +448,7 @@ int fd_auto_choice(const dmx_params& prm, const WsView& ws) {
 int launch_channels_fd(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
                        float2* out, int variant, hipStream_t stream) {
     if (user_count == 0) return DMX_OK;
-    if (prm.flags & DMX_FLAG_SPATIAL_WIDEBAND) variant = 1;    // dmx_channels_fd has refused every explicit variant but 1
+    if (prm.flags & (DMX_FLAG_SPATIAL_WIDEBAND | DMX_FLAG_NEAR_FIELD)) variant = 1;    // dmx_channels_fd has refused every explicit variant but 1
     if (variant >= 2 && variant != 9 && variant != 12 && !fd_mfma_supported(prm, ws)) {
         set_error("MFMA variant does not support this shape");
         return DMX_ERR_SHAPE;

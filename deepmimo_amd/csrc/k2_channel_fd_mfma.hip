@@ -29,6 +29,7 @@
 //            a scalar offset of the buffer instruction, so the epilogue is 1 VALU op per store.
 // HBM traffic = the 8*M*K output bytes (written once) + ~1 KB of path records per user.
 #include "k2_mfma_frag.h"
+#include "array_phase.h"
 #include "dmx_tuning.h"
 #include <stdlib.h>
 
@@ -660,8 +661,12 @@ struct BeamArgs {
     float2* ftab;            // [user_count, n_beams, P]
     int32_t* fexp;           // [user_count]
 };
+// the scalar form's arguments: the matrix-core form keeps BeamArgs, and with it its kernel-argument layout
+struct BeamArgsNf : BeamArgs {
+    NearField nf;            // DMX_FLAG_NEAR_FIELD (array_phase.h): the scalar form alone builds spherical-wavefront tables
+};
 
-__global__ __launch_bounds__(256) void k2b_beam_project(WsView ws, BeamArgs a) {
+__global__ __launch_bounds__(256) void k2b_beam_project(WsView ws, BeamArgsNf a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float2* atx = reinterpret_cast<float2*>(smem);                       // [m_tx][P]
     __shared__ float wmax[4];
@@ -671,12 +676,13 @@ __global__ __launch_bounds__(256) void k2b_beam_project(WsView ws, BeamArgs a) {
     int n_act = ws.n_keep[u];
     n_act = n_act < LPAD ? n_act : LPAD;
     const size_t rb = (size_t)u * P;
+    const NearFieldEnd nf = a.nf.tx();
     for (int i = tid; i < a.m_tx * P; i += 256) {
         const int t = i / P, l = i - t * P;
         float s = 0.f, c = 0.f;
         if (l < n_act) {
             const int y = t % a.bs_mh, z = t / a.bs_mh;
-            sincos_rev(frac_rev((double)y * ws.tx_y[rb + l] + (double)z * ws.tx_z[rb + l]), s, c);
+            sincos_rev(frac_rev(array_phase<false>(y, z, ws.tx_y[rb + l], ws.tx_z[rb + l], nf.on ? ws.dn[rb + l] : 0.f, nf)), s, c);
         }
         atx[i] = make_float2(c, s);
     }
@@ -898,7 +904,8 @@ size_t beam_workspace_bytes(int64_t user_count, int n_beams, int P) {
 // two arrays inside it that the contraction kernels read
 int launch_beam_project(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count,
                         const float2* codebook, int n_beams, void* beam_ws, hipStream_t stream, BeamTabs* tabs) {
-    BeamArgs b;
+    BeamArgsNf b;
+    b.nf = near_field_of(prm);
     b.user_begin = user_begin;
     b.m_tx = prm.bs_shape[0] * prm.bs_shape[1];
     b.bs_mh = prm.bs_shape[0];
@@ -914,12 +921,15 @@ int launch_beam_project(const dmx_params& prm, const WsView& ws, int64_t user_be
     const int fstride = kkpad * 2 + 16;
     const int nbt = (n_beams + 31) / 32;
     const size_t smem_m = (size_t)2 * (nbt <= 1 ? 1 : (nbt <= 2 ? 2 : 4)) * 32 * fstride;
+    // (near field: the scalar kernel for every panel - the matrix-core form generates plane-wave fragments)
     if (nbt <= 4 && smem_m <= 64 * 1024) {
-        int64_t grid = (user_count + 3) / 4;
-        if (grid > 2048) grid = 2048;                      // persistent: the codebook is staged once per workgroup
-        const auto kernel = nbt <= 1 ? k2b_beam_project_mfma<1> : (nbt <= 2 ? k2b_beam_project_mfma<2> : k2b_beam_project_mfma<4>);
-        return launch_dyn_lds(kernel, "k2b_beam_project", dim3((unsigned)grid), dim3(256), smem_m, LDS_NO_RAISE, stream, ws, b, user_count,
-                              kkpad, fstride);
+        if (!b.nf.on) {
+            int64_t grid = (user_count + 3) / 4;
+            if (grid > 2048) grid = 2048;                      // persistent: the codebook is staged once per workgroup
+            const auto kernel = nbt <= 1 ? k2b_beam_project_mfma<1> : (nbt <= 2 ? k2b_beam_project_mfma<2> : k2b_beam_project_mfma<4>);
+            return launch_dyn_lds(kernel, "k2b_beam_project", dim3((unsigned)grid), dim3(256), smem_m, LDS_NO_RAISE, stream, ws,
+                                  static_cast<const BeamArgs&>(b), user_count, kkpad, fstride);
+        }
     }
     const size_t smem = (size_t)b.m_tx * (ws.P > 0 ? ws.P : 1) * 8;
     if (smem > 64 * 1024) { set_error("BS panel of %d elements x %d paths does not fit the beam-projection table", b.m_tx, ws.P); return DMX_ERR_SHAPE; }

@@ -8,6 +8,7 @@
 // the body switches it off and every fused operation is an explicit fma ("Bit identity", has the forms).
 #pragma once
 #include "dmx_common.h"
+#include "array_phase.h"
 
 namespace dmx {
 
@@ -41,6 +42,8 @@ __host__ inline size_t small_table_bytes(const dmx_params& prm, int ld) {
 struct WsRecords {
     const WsView& ws;
     size_t rb;                                                               // first record of the user's row
+    NearField nf{};                                                          // how the array phases of these records are read
+                                                                             // (array_phase.h): off unless the kernel sets it
     __device__ float c_re(int l) const { return ws.c_re[rb + l]; }
     __device__ float c_im(int l) const { return ws.c_im[rb + l]; }
     __device__ float dn(int l) const { return ws.dn[rb + l]; }

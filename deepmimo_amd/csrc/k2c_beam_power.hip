@@ -20,6 +20,7 @@
 // K-step of one wide strip of chunk c + 1, then runs its tile against chunk c - one barrier per chunk; with fewer than
 // eight row tiles the waves split the chunk's wide strips among themselves.
 #include "k2_mfma_frag.h"
+#include "array_phase.h"
 #include "dmx_tuning.h"
 #include <stdlib.h>
 
@@ -44,6 +45,7 @@ struct BeamPowArgs {
     float* out;              // [user_count, n_beams] mean amplitude
     int32_t* best;           // [user_count] argmax_b (first maximum), -1 without paths; may be nullptr
     int adaptive;            // 1 = a weak last K-step may take one product term
+    NearFieldEnd nf;         // DMX_FLAG_NEAR_FIELD, the UE end (array_phase.h); the BS end is inside ftab
 };
 
 __host__ __device__ inline size_t beam_pow_lds_bytes(int M, int NW) {
@@ -51,7 +53,9 @@ __host__ __device__ inline size_t beam_pow_lds_bytes(int M, int NW) {
     return (size_t)BP_BUFS * (NW / 4) * BP_SLOT + LPAD * (8 + 4 + 4) + 16 + nblk * NW * 32 * 4;
 }
 
-template <int NW>
+// NF: the receive-side phase of the A' fill is the near-field one (DMX_FLAG_NEAR_FIELD); its own instantiations, the
+// far-field ones compile as before (the kernel sits at its register cap)
+template <int NW, bool NF = false>
 __global__ __launch_bounds__(NW * 64, 4) void k2c_beam_power(WsView ws, BeamPowArgs a, int64_t user_count) {
     constexpr int BP_WAVES = NW, BP_CHUNK = NW / 4, MAX_ROWS = 32 * NW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -126,7 +130,7 @@ __global__ __launch_bounds__(NW * 64, 4) void k2c_beam_power(WsView ws, BeamPowA
                 const int r = row0 + (tile << 5) + col;
                 const bool pok = r < M;
                 const int rx = pok ? r / B : 0, bm = pok ? r - rx * B : 0;
-                const double yr = (double)(rx % a.ue_mh), zr = (double)(rx / a.ue_mh);
+                const int yr = rx % a.ue_mh, zr = rx / a.ue_mh;
                 const float2* frow = a.ftab + ((size_t)ul * B + bm) * P;
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
@@ -137,7 +141,8 @@ __global__ __launch_bounds__(NW * 64, 4) void k2c_beam_power(WsView ws, BeamPowA
                             h2 vh = {(_Float16)0.f, (_Float16)0.f}, vl = vh;
                             if (pok && pl < n_act) {
                                 float sn, cs;
-                                sincos_rev(frac_rev(yr * ws.rx_y[rb + pl] + zr * ws.rx_z[rb + pl]), sn, cs);
+                                sincos_rev(frac_rev(array_phase<false>(yr, zr, ws.rx_y[rb + pl], ws.rx_z[rb + pl], NF ? ws.dn[rb + pl] : 0.f,
+                                                                       NF ? a.nf : NearFieldEnd{0, 0.0, 0.0})), sn, cs);
                                 const float2 f = frow[pl];
                                 split2_f16((cs * f.x - sn * f.y) * ascale, (cs * f.y + sn * f.x) * ascale, vh, vl, ws.neg_one);
                             }
@@ -286,7 +291,9 @@ int launch_beam_power(const dmx_params& prm, const WsView& ws, int64_t user_begi
     a.out = out_amp;
     a.best = out_best;
     a.adaptive = (prm.flags & DMX_FLAG_ADAPTIVE_TERMS) ? 1 : 0;     // default: three product terms everywhere
-    const auto kernel = nw == 4 ? k2c_beam_power<4> : k2c_beam_power<8>;
+    a.nf = near_field_of(prm).rx();
+    const auto kernel = a.nf.on ? (nw == 4 ? k2c_beam_power<4, true> : k2c_beam_power<8, true>)
+                                : (nw == 4 ? k2c_beam_power<4> : k2c_beam_power<8>);
     int64_t grid = resident_workgroups(kernel, nw * 64, smem);
     // a few users per workgroup let the dispatcher balance the tail (k2_channel_fd_mfma.hip: ITEMS_PER_WG)
     const int64_t g4 = user_count / 4;

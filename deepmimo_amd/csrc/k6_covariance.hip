@@ -16,6 +16,7 @@
 // launch.  LDS of one wave: (M_out + M_avg + M_out + P + kc) * P * 8 bytes (ao, aa, T, Q, g chunk), P = min(num_paths,
 // loaded paths) <= 32; cov_waves_per_block has the rule.  Bound: VALU / LDS issue of phases 2 and 4, far below HBM.
 #include "dmx_common.h"
+#include "array_phase.h"
 #include "k2_small_body.h"
 
 namespace dmx {
@@ -29,6 +30,7 @@ struct CovArgs {
     double inv_n;
     float scale;         // 1 / (m_avg * K)
     int ld;              // table row stride in path slots (= P)
+    NearField nf;        // DMX_FLAG_NEAR_FIELD (array_phase.h)
 };
 
 // Pair (i <= j) number e of an n x n upper triangle, rows i and n - 1 - i folded into one row of n + 1 entries
@@ -74,14 +76,14 @@ __global__ __launch_bounds__(256) void k6_covariance(WsView ws, CovArgs a, float
         const int t = i / n, l = i - t * n;
         const double sy = SIDE == DMX_COV_TX ? rec.tx_y(l) : rec.rx_y(l), sz = SIDE == DMX_COV_TX ? rec.tx_z(l) : rec.rx_z(l);
         float s, c;
-        sincos_rev(frac_rev(__builtin_fma((double)(t % a.out_mh), sy, (double)(t / a.out_mh) * sz)), s, c);
+        sincos_rev(frac_rev(array_phase(t % a.out_mh, t / a.out_mh, sy, sz, a.nf.on ? rec.dn(l) : 0.f, a.nf.end(SIDE != DMX_COV_TX))), s, c);
         ao[t * ld + l] = make_float2(c, s);
     }
     for (int i = lane; i < a.m_avg * n; i += 64) {
         const int t = i / n, l = i - t * n;
         const double sy = SIDE == DMX_COV_TX ? rec.rx_y(l) : rec.tx_y(l), sz = SIDE == DMX_COV_TX ? rec.rx_z(l) : rec.tx_z(l);
         float s, c;
-        sincos_rev(frac_rev(__builtin_fma((double)(t % a.avg_mh), sy, (double)(t / a.avg_mh) * sz)), s, c);
+        sincos_rev(frac_rev(array_phase(t % a.avg_mh, t / a.avg_mh, sy, sz, a.nf.on ? rec.dn(l) : 0.f, a.nf.end(SIDE == DMX_COV_TX))), s, c);
         aa[t * ld + l] = make_float2(c, s);
     }
     for (int i = lane; i < n * ld; i += 64) Q[i] = make_float2(0.f, 0.f);
@@ -190,6 +192,7 @@ int launch_covariance(const dmx_params& prm, const WsView& ws, int64_t user_begi
     a.inv_n = 1.0 / (double)prm.n_subcarriers;
     a.scale = (float)(1.0 / ((double)a.m_avg * (double)a.K));
     a.ld = ws.P;
+    a.nf = near_field_of(prm);
     const size_t smem = (size_t)wpb * (size_t)(2 * a.m_out + a.m_avg + a.ld + a.kc) * a.ld * sizeof(float2);
     const dim3 g((unsigned)((user_count + wpb - 1) / wpb)), b(64 * wpb);    // flat: one wave per user
     if (tx) return launch_dyn_lds(k6_covariance<DMX_COV_TX>, "k6_covariance", g, b, smem, WAVE_LDS_MAX, stream, ws, a, out);

@@ -71,6 +71,7 @@ struct RateArgs {
     float scale;         // sqrt(snr / M_tx), or sqrt(snr) for the spectrum
     float inv_k;
     int ld;              // table row stride in path slots (= P)
+    NearField nf;        // DMX_FLAG_NEAR_FIELD (array_phase.h)
 };
 
 // 2 .. 4  the w chunk, rows_pair of phase 3, epilogue_logdet and the kept-path count: k7_rate_body.h, shared with the other
@@ -255,14 +256,18 @@ __global__ __launch_bounds__(256) void k7_rate(WsView ws, RateArgs a, float* __r
         const int t = i / n, l = i - t * n;
         const double sy = a.small_is_rx ? rec.rx_y(l) : rec.tx_y(l), sz = a.small_is_rx ? rec.rx_z(l) : rec.tx_z(l);
         float s, c;
-        sincos_rev(frac_rev(__builtin_fma((double)(t % a.small_mh), sy, (double)(t / a.small_mh) * sz)), s, c);
+        if (a.nf.on) near_field_sincos(t % a.small_mh, t / a.small_mh, sy, sz, rec.dn(l), a.nf.end(a.small_is_rx), s, c);
+        else
+            sincos_rev(frac_rev(__builtin_fma((double)(t % a.small_mh), sy, (double)(t / a.small_mh) * sz)), s, c);
         as[t * ld + l] = make_float2(c, s);
     }
     for (int i = lane; i < Mb * n; i += 64) {
         const int t = i / n, l = i - t * n;
         const double sy = a.small_is_rx ? rec.tx_y(l) : rec.rx_y(l), sz = a.small_is_rx ? rec.tx_z(l) : rec.rx_z(l);
         float s, c;
-        sincos_rev(frac_rev(__builtin_fma((double)(t % a.big_mh), sy, (double)(t / a.big_mh) * sz)), s, c);
+        if (a.nf.on) near_field_sincos(t % a.big_mh, t / a.big_mh, sy, sz, rec.dn(l), a.nf.end(!a.small_is_rx), s, c);
+        else
+            sincos_rev(frac_rev(__builtin_fma((double)(t % a.big_mh), sy, (double)(t / a.big_mh) * sz)), s, c);
         ab[t * ld + l] = make_float2(c, s);
     }
 
@@ -451,6 +456,7 @@ static int launch_rate_epi(const dmx_params& prm, const WsView& ws, int64_t user
     a.m_big = rx_small ? m_tx : m_rx;
     a.big_mh = rx_small ? prm.bs_shape[0] : prm.ue_shape[0];
     a.small_mh = rx_small ? prm.ue_shape[0] : prm.bs_shape[0];
+    a.nf = near_field_of(prm);
     a.small_is_rx = rx_small ? 1 : 0;
     a.K = prm.n_selected; a.kc = a.K < 64 ? a.K : 64;
     a.log2_S = gram_slices_log2(a.K, a.m_big);

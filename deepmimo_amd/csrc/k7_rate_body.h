@@ -16,6 +16,7 @@
 // fill and the reads of it; nothing here does.
 #pragma once
 #include "dmx_common.h"
+#include "array_phase.h"
 #include "k2_small_body.h"
 #include <hip/hip_runtime.h>
 
@@ -35,14 +36,18 @@ __device__ __forceinline__ int kept_paths(const WsView& ws, const int64_t u) {
 }
 
 // 1  rows row0 .. row0 + rows of the steering table of the UE (rx) or the BS array, first panel dimension mh, for the first
-//    n paths: tab[t][l], t from 0.  float64 phase, reduced to a revolution before the float32 sincos.
+//    n paths: tab[t][l], t from 0.  float64 phase - the plane wave, or with rec.nf.on the spherical one of array_phase.h -
+//    reduced to a revolution before the float32 sincos.
 __device__ __forceinline__ void fill_array_table(float2* tab, const WsRecords& rec, const bool rx, const int row0, const int rows,
                                                  const int mh, const int n, const int ld, const int lane) {
+    const NearFieldEnd nf = rec.nf.end(rx);
     for (int i = lane; i < rows * n; i += 64) {
         const int t = i / n, l = i - t * n, e = row0 + t;
         const double sy = rx ? rec.rx_y(l) : rec.tx_y(l), sz = rx ? rec.rx_z(l) : rec.tx_z(l);
         float s, c;
-        sincos_rev(frac_rev(__builtin_fma((double)(e % mh), sy, (double)(e / mh) * sz)), s, c);
+        if (nf.on) near_field_sincos(e % mh, e / mh, sy, sz, rec.dn(l), nf, s, c);
+        else
+            sincos_rev(frac_rev(__builtin_fma((double)(e % mh), sy, (double)(e / mh) * sz)), s, c);
         tab[t * ld + l] = make_float2(c, s);
     }
 }

@@ -38,6 +38,7 @@ struct CellLink {
     int S, log2_S;       // slices of the BS array per subcarrier (1 unless K < 64)
     float scale;         // sqrt(snr_b / M_tx,b)
     double snr;
+    NearField nf;        // DMX_FLAG_NEAR_FIELD of this link's parameters (array_phase.h)
 };
 
 struct CellArgs {
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(256) void k8_cell_rate(CellArgs a, const int32_t* _
             const int ld = lk.ws.P, Mb = lk.m_tx;
             const int n = kept_paths(lk.ws, u);
             if (n <= 0) continue;                                            // this link does not reach the user
-            const WsRecords rec{lk.ws, (size_t)u * ld};
+            const WsRecords rec{lk.ws, (size_t)u * ld, lk.nf};
             float2* ab = as + (size_t)M * ld;                                // [Mb][ld]
             float2* w = ab + (size_t)Mb * ld;                                // [ld][kc]
             wave_lds_fence();                                                // the last link's reads before this link's writes
@@ -262,6 +263,7 @@ int launch_cell_rate(const dmx_link* links, int n_links, int64_t n_ue, int64_t u
         lk.S = 1 << lk.log2_S;
         lk.scale = (float)sqrt(src.snr_linear / (double)lk.m_tx);
         lk.snr = src.snr_linear;
+        lk.nf = near_field_of(prm);
     }
     const int m_rx = p0.ue_shape[0] * p0.ue_shape[1];
     const size_t smem = (size_t)wpb * bytes;

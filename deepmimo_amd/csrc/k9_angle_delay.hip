@@ -45,6 +45,7 @@ struct AdArgs {
     double inv_n, inv_nfft;
     const float2* ftab;      // [user_count, R, P] from k2b_beam_project, or nullptr: rows are the BS elements
     int ld;                  // table row stride in path slots (= P)
+    NearField nf;            // DMX_FLAG_NEAR_FIELD (array_phase.h); with ftab the BS side of it is inside the rows
 };
 
 struct cd { double x, y; };                                                  // float64 complex: cos, sin
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(256) void k9_angle_delay(WsView ws, AdArgs a, float
         for (size_t i = lane; i < (size_t)M * R * T; i += 64) o[i] = make_float2(0.f, 0.f);
         return;
     }
-    const WsRecords rec{ws, (size_t)u * ws.P};
+    const WsRecords rec{ws, (size_t)u * ws.P, a.nf};
 
     // 1  the a_rx table
     fill_array_table(as, rec, true, 0, M, a.ue_mh, n, ld, lane);
@@ -195,6 +196,7 @@ int launch_angle_delay(const dmx_params& prm, const WsView& ws, int64_t user_beg
     }
     a.user_begin = user_begin; a.user_count = user_count;
     a.ue_mh = prm.ue_shape[0]; a.bs_mh = prm.bs_shape[0];
+    a.nf = near_field_of(prm);
     a.R = n_rows;
     a.n_taps = n_taps; a.tc = n_taps < 64 ? n_taps : 64;
     a.log2_tcp = 0;

@@ -51,8 +51,10 @@ _RX_COMBINER, _N_RX_BEAMS, _N_UE_PER_RX_BEAM = "rx_combiner", "n_rx_beams", "n_u
 _RX_KEYS = (_RX_COMBINER, _N_RX_BEAMS, _N_UE_PER_RX_BEAM)
 _NOT_PER_USER = (_TX_VEL, c.TX_POS_PARAM_NAME) + _FOV_KEYS + _TIME_KEYS + _RX_KEYS    # never the user axis, whatever their length
 _VIEW_RESULTS = ("beam_mean_amplitude", "beam_pair_mean_amplitude")         # results kept in the dict that no view carries
+# near field (DESIGN.md "Near field"): the one entry a view of `near_field` carries, its carrier frequency in Hz
+_NEAR_FIELD = "near_field_carrier"
 # what a block of snapshots needs to run a channel call, and nothing a caller of the view might read beside it
-_BLOCK_KEYS = c.RAY_FIELDS + (c.DOPPLER_VEL_PARAM_NAME, c.DOPPLER_ACC_PARAM_NAME, c.CH_PARAMS_PARAM_NAME) + _FOV_KEYS
+_BLOCK_KEYS = c.RAY_FIELDS + (c.DOPPLER_VEL_PARAM_NAME, c.DOPPLER_ACC_PARAM_NAME, c.CH_PARAMS_PARAM_NAME) + _FOV_KEYS + (_NEAR_FIELD,)
 
 _engines: Dict[int, Any] = {}
 
@@ -278,9 +280,13 @@ class Dataset(DotDict):
         self._data[_PATTERNS_IN_EFFECT] = pats
         return params
 
-    def _prep_inputs(self, wideband_fc=None):
+    def _prep_inputs(self, wideband_fc=None, fd_variant=None):
         """(engine, parameters stage 1 runs with, uploaded rays, prepare keywords) of a GPU pass on this dataset.
-        `wideband_fc`: the carrier frequency of a spatial-wideband call (`_wideband_carrier`), None for every other call."""
+        `wideband_fc`: the carrier frequency of a spatial-wideband call (`_wideband_carrier`), None for every other call.
+        On a view of `near_field` the pass runs with ``near_field=True`` and the view's carrier, after the checks of
+        `engine.check_near_field_call` - before any GPU work; `fd_variant`: the kernel variant of a channel call, which
+        is part of those checks."""
+        near_fc = self._near_field_checked(self.ch_params, wideband_fc is not None, fd_variant)
         eng = _engine()
         params = self._params_for_prep()
         rays = eng.upload_rays(self)
@@ -289,7 +295,21 @@ class Dataset(DotDict):
                   adaptive_terms=bool(config.get("adaptive_precision", False)))
         if wideband_fc is not None:
             kw.update(carrier_freq=wideband_fc, spatial_wideband=True)
+        if near_fc is not None:
+            kw.update(carrier_freq=near_fc, near_field=True)
         return eng, params, rays, kw
+
+    def _near_field_checked(self, params, spatial_wideband=False, fd_variant=None):
+        """None on a dataset that is no view of `near_field`; on a view, its carrier frequency in Hz after the checks a call
+        on it makes before any GPU work (engine.check_near_field_call)."""
+        if _NEAR_FIELD not in self._data:
+            return None
+        from .engine import check_near_field_call
+        return check_near_field_call(params, self._data[_NEAR_FIELD], fd_variant, spatial_wideband)
+
+    def _refuse_on_near_field(self, who: str, why: str) -> None:
+        if _NEAR_FIELD in self._data:
+            raise ValueError(f"{who}: not covered on a near-field view ({why})")
 
     def _wideband_carrier(self, params, spatial_wideband, carrier_freq):
         """The checks of a channel call with ``spatial_wideband`` before any GPU work (engine.check_wideband_call): the
@@ -320,7 +340,8 @@ class Dataset(DotDict):
         eng, params, rays, kw = inputs
         cfg = (config.get("single_pass", "auto"), config.get("fd_kernel_variant", 0), config.get("adaptive_precision", False))
         # what needs no struct first: a call that cannot be routed pays nothing for the question
-        if not params[c.PARAMSET_FD_CH] or not single_pass_route(*cfg, True, 9, True, spatial_wideband=kw.get("spatial_wideband", False)):
+        if not params[c.PARAMSET_FD_CH] or not single_pass_route(*cfg, True, 9, True, spatial_wideband=kw.get("spatial_wideband", False),
+                                                                  near_field=kw.get("near_field", False)):
             return None, None
         structs = eng._call_structs(rays, params, **kw)
         p = structs[0]
@@ -445,7 +466,7 @@ class Dataset(DotDict):
         """The GPU part of `compute_channels` for the stored parameters `params`: the single pass where it applies, else
         stage 1 and stage 2.  Returns (channels, the delay maximum or None in the time domain).  `out`: the resident
         tensor to write into (not with `to_host`).  `wideband_fc`: as for `_prep_inputs`."""
-        inputs = self._prep_inputs(wideband_fc)
+        inputs = self._prep_inputs(wideband_fc, fd_variant=config.get("fd_kernel_variant", 0))
         direct, structs = self._run_single_pass(inputs, to_host, out)
         if direct is not None:
             return direct
@@ -470,7 +491,7 @@ class Dataset(DotDict):
         params = self._call_params(params)
         wideband_fc = self._wideband_carrier(params, spatial_wideband, carrier_freq)
         np.random.seed(1001)
-        eng, prep = self._run_prep(want_side="light", inputs=self._prep_inputs(wideband_fc))
+        eng, prep = self._run_prep(want_side="light", inputs=self._prep_inputs(wideband_fc, config.get("fd_kernel_variant", 0)))
         n = prep.n_ue
         variant = int(config.get("fd_kernel_variant", 0))
         for b in range(0, n, max(1, int(chunk_users))):
@@ -481,6 +502,7 @@ class Dataset(DotDict):
         """Beam-space channels ``codebook @ H`` for a TX codebook [n_beams, M_tx] (rows e.g. from
         ``dm.steering_vec``), complex64 [n_ue, M_rx, n_beams, K] - what docs/manual.ipynb cell 105 computes
         as ``F1 @ dataset.channel`` - without materialising H (extension).  Not cached."""
+        self._refuse_on_near_field("compute_beam_channels", "the beam-space channel kernel builds plane-wave responses only")
         self._call_params(params)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
@@ -1121,6 +1143,7 @@ class Dataset(DotDict):
         time-major where they are returned from - no channel-sized tensor is ever transposed."""
         params, t, scalar, fc = self._time_call("compute_channels", params, times, carrier_freq)
         wideband_fc = self._wideband_carrier(params, spatial_wideband, fc)
+        self._near_field_checked(params, spatial_wideband, config.get("fd_kernel_variant", 0))     # before the rays move
         to_host = config.get("channel_output", "numpy") != "torch"
         shape = self._channel_shape(params)
         if not params[c.PARAMSET_FD_CH]:
@@ -1155,17 +1178,54 @@ class Dataset(DotDict):
         """`iter_channels(times=...)`: stage 1 once per block of snapshots, stage 2 per snapshot and user chunk."""
         params, t, _, fc = self._time_call("iter_channels", params, times, carrier_freq)
         wideband_fc = self._wideband_carrier(params, spatial_wideband, fc)
+        self._near_field_checked(params, spatial_wideband, config.get("fd_kernel_variant", 0))
         n_ue, step = int(self.n_ue), max(1, int(chunk_users))
         variant = int(config.get("fd_kernel_variant", 0))
         src = self._in_hbm(_BLOCK_KEYS)
         for b, nb in self._time_blocks(len(t)):
             view = src._block_view("iter_channels", params, t[b:b + nb], fc)
             np.random.seed(1001)
-            eng, prep = view._run_prep(want_side="light", inputs=view._prep_inputs(wideband_fc))
+            eng, prep = view._run_prep(want_side="light", inputs=view._prep_inputs(wideband_fc, config.get("fd_kernel_variant", 0)))
             for i in range(nb):
                 for ub in range(0, n_ue, step):
                     cnt = min(step, n_ue - ub)
                     yield b + i, ub, eng.channels_to_host(prep, variant=variant, user_begin=i * n_ue + ub, user_count=cnt)
+
+    # -------------------------------------------------------------- near field (extension; DESIGN.md)
+    def near_field(self, carrier_freq=None) -> "Dataset":
+        """The dataset with spherical-wavefront array responses, as a plain Dataset of the same users that shares this one's
+        arrays (extension).  Every ``compute_*`` that builds its array tables from the path records works on it unchanged
+        and sees each path as a spherical wave from a point ``R = delay * f_c`` wavelengths away along the path's direction
+        (the total path length), seen from element 0 of each array, in place of the plane wave:
+
+            psi[e, l] = R_l - sqrt(R_l^2 - 2 R_l q[e, l] + d^2 (y_e^2 + z_e^2))           # revolutions
+            q[e, l]   = d (y_e sin theta_l sin phi_l + z_e cos theta_l)                   # the plane-wave phase, R -> inf
+
+        (include/deepmimo_amd.h, DMX_FLAG_NEAR_FIELD; ``dm.near_field_response``).  ``f_c``: ``carrier_freq`` in Hz, else
+        ``rt_params.frequency``; it is kept as ``near_field_carrier`` and is the carrier of the Doppler term too.  The
+        amplitude stays uniform over the aperture, the radius is exact for LoS and specular chains and too large for
+        diffracted or scattered paths, and the two ends are curved independently.
+
+        ``subset`` and ``at_times`` of the view are near-field views.  ValueError before any GPU work: a carrier frequency
+        that is missing or not finite and > 0; in a call on the view the time domain, ``rx_filter = 1``,
+        ``spatial_wideband=True``, ``config('fd_kernel_variant')`` other than 0 or 1 (channel calls run the fp32 vector
+        kernel; the single pass is not taken), ``compute_beam_channels``, ``with_rx_combiner`` and
+        ``compute_beam_pair_power`` (the combiner's response is still plane-wave)."""
+        if _N_RX_BEAMS in self._data:
+            raise ValueError("near_field: not covered on a view of with_rx_combiner (the combiner's response to a path is the "
+                             "plane-wave one)")
+        fc = self._time_carrier("near_field", carrier_freq)
+        view = self._with_users(int(self.n_ue), lambda v: v,
+                                ((k, self._host(k)) for k in list(self._data) if k not in self._computed_attributes
+                                 or k == c.CH_PARAMS_PARAM_NAME), skip=_VIEW_RESULTS)
+        d = view._data
+        if c.CH_PARAMS_PARAM_NAME in d:
+            d[c.CH_PARAMS_PARAM_NAME] = d[c.CH_PARAMS_PARAM_NAME].deepcopy()
+            drawn = self._data.get(_UE_ROT_RESOLVED)
+            if drawn is not None:
+                d[_UE_ROT_RESOLVED] = drawn
+        d[_NEAR_FIELD] = fc
+        return view
 
     # -------------------------------------------------------------- UE receive combining (extension; DESIGN.md)
     def with_rx_combiner(self, codebook="dft", params: Optional[ChannelGenParameters] = None) -> "Dataset":
@@ -1195,6 +1255,7 @@ class Dataset(DotDict):
         them, and a UE shape other than [1, 1] raises ValueError.  It composes with ``at_times`` in either order; the
         outer view's split applies to the first axis."""
         from .combiner import check_rx_codebook
+        self._refuse_on_near_field("with_rx_combiner", "the combiner's response to a path is the plane-wave one")
         params = self._call_params(params)
         W = check_rx_codebook("with_rx_combiner", codebook, params[c.PARAMSET_ANT_UE][c.PARAMSET_ANT_SHAPE])
         return self._rx_view(W, *self._rx_arrival_angles())
@@ -1254,6 +1315,7 @@ class Dataset(DotDict):
         from .combiner import check_rx_codebook
         from .engine import check_beam_bound, check_selection
         who = "compute_beam_pair_power"
+        self._refuse_on_near_field(who, "the combiner's response to a path is the plane-wave one")
         params = self._call_params(params)
         bs_shape = params[c.PARAMSET_ANT_BS][c.PARAMSET_ANT_SHAPE]
         m_tx = int(bs_shape[0]) * int(bs_shape[1])
@@ -1450,6 +1512,11 @@ class MacroDataset:
         """A MacroDataset of the children's ``Dataset.at_times(times, carrier_freq)`` views - T * n_ue users each, time-major
         - so ``compute_cell_rate`` runs over time (extension).  ``split_times`` gives its results as [T, n_ue, ...]."""
         return MacroDataset([d.at_times(times, carrier_freq) for d in self.datasets])
+
+    def near_field(self, carrier_freq=None) -> "MacroDataset":
+        """A MacroDataset of the children's ``Dataset.near_field(carrier_freq)`` views, so ``compute_cell_rate`` runs with
+        spherical wavefronts (extension).  A MacroDataset built from views and plain children mixes the two per link."""
+        return MacroDataset([d.near_field(carrier_freq) for d in self.datasets])
 
     def split_times(self, x):
         """``Dataset.split_times`` of the first child: the children of a view share the times and the users."""

@@ -188,6 +188,8 @@ def compute_channels_sharded(data, params, bs_fov=None, ue_fov=None, group=None,
     ChannelGenParameters (validated by the caller).  A per-user UE rotation [N, 3] is sliced like
     the rays; the random-range form (3, 2) must be resolved by the caller so that all ranks agree."""
     from .engine import ChannelEngine
+    if hasattr(data, "keys") and "near_field_carrier" in data.keys():
+        raise ValueError("compute_channels_sharded: a near-field view (Dataset.near_field) is not covered")
     rank, world = _world(group)
     if device_index is None:
         device_index = torch.cuda.current_device()

@@ -136,16 +136,16 @@ def single_pass_preferred(table_rows: int, loaded_paths: int, n_selected: int) -
 
 
 def single_pass_route(single_pass, fd_kernel_variant, adaptive_precision, direct_supported, auto_choice, one_piece,
-                      preferred=True, spatial_wideband=False) -> bool:
+                      preferred=True, spatial_wideband=False, near_field=False) -> bool:
     """Whether ``Dataset.compute_channels`` takes the single-pass kernel (dmx_channels_fd_direct) instead of stage 1 +
     stage 2.  All of: ``config('single_pass')`` is not False; the kernel variant is the automatic one (0) and adaptive
     precision is off; the library takes the shape (dmx_fd_direct_supported == 1); variant 0 would run the small-output
     kernel there (dmx_fd_kernel_choice == 9), so the arithmetic - and every output bit - is the one the two calls give;
     the tensor leaves in one piece (resident, or a host copy `channels_to_host` would not chunk); and, for 'auto', the
     shape is on the winning side of the measured crossover (`single_pass_preferred`).  ``single_pass = True`` takes the
-    route wherever it is possible, whatever the crossover says.  Never with ``spatial_wideband``: the single-pass kernel
-    has no per-subcarrier array response."""
-    if spatial_wideband or single_pass is False or single_pass is None or single_pass in (0, "off", "false", "False"):
+    route wherever it is possible, whatever the crossover says.  Never with ``spatial_wideband`` or ``near_field``: the
+    single-pass kernel has no per-subcarrier array response and builds plane-wave tables only."""
+    if spatial_wideband or near_field or single_pass is False or single_pass is None or single_pass in (0, "off", "false", "False"):
         return False
     if int(fd_kernel_variant) != 0 or bool(adaptive_precision):
         return False
@@ -199,6 +199,37 @@ def check_wideband_call(params, carrier_freq, fd_kernel_variant=0) -> float:
     if int(fd_kernel_variant) not in WIDEBAND_VARIANTS:
         raise ValueError(f"spatial_wideband: fd_kernel_variant {int(fd_kernel_variant)} is refused, only the fp32 vector kernel "
                          f"(variant 0 or 1) forms a per-subcarrier array response")
+    return fc
+
+
+NEAR_FIELD_VARIANTS = (0, 1)
+
+
+def check_near_field_call(params, carrier_freq, fd_kernel_variant=None, spatial_wideband=False) -> float:
+    """Everything a call on a near-field view (DMX_FLAG_NEAR_FIELD, include/deepmimo_amd.h) can refuse without a GPU, as
+    ValueError: time domain, rx_filter = 1, ``spatial_wideband`` on top, a carrier frequency that is missing or not finite
+    and > 0, a bandwidth that is not finite and > 0 and, for a channel call (`fd_kernel_variant` given), a kernel variant
+    other than 0 or 1 (of the channel kernels only the fp32 vector kernel builds spherical-wavefront tables).  `params`:
+    validated ChannelGenParameters.  Returns the carrier frequency in Hz."""
+    ofdm = params[c.PARAMSET_OFDM]
+    if not params[c.PARAMSET_FD_CH]:
+        raise ValueError("near_field: needs the frequency-domain channel (freq_domain = 1)")
+    if ofdm[c.PARAMSET_OFDM_LPF]:
+        raise ValueError("near_field: ofdm.rx_filter = 1 is not covered")
+    if spatial_wideband:
+        raise ValueError("near_field: spatial_wideband=True is not covered on a near-field view")
+    try:
+        fc = float(carrier_freq)
+    except (TypeError, ValueError):
+        fc = float("nan")
+    if not (math.isfinite(fc) and fc > 0):
+        raise ValueError("near_field: no carrier frequency: pass carrier_freq (Hz, finite and > 0) or set rt_params.frequency")
+    bw = float(ofdm[c.PARAMSET_OFDM_BANDWIDTH])
+    if not (math.isfinite(bw) and bw > 0):
+        raise ValueError(f"near_field: ofdm.bandwidth must be finite and > 0, got {bw!r}")
+    if fd_kernel_variant is not None and int(fd_kernel_variant) not in NEAR_FIELD_VARIANTS:
+        raise ValueError(f"near_field: fd_kernel_variant {int(fd_kernel_variant)} is refused, only the fp32 vector kernel "
+                         f"(variant 0 or 1) builds spherical-wavefront array tables")
     return fc
 
 
@@ -518,10 +549,14 @@ class ChannelEngine:
         return side, s
 
     def _call_structs(self, rays: DeviceRays, params, bs_fov=None, ue_fov=None, ue_rotation_per_user=None,
-                      carrier_freq: float = 0.0, adaptive_terms: bool = False, spatial_wideband: bool = False):
+                      carrier_freq: float = 0.0, adaptive_terms: bool = False, spatial_wideband: bool = False,
+                      near_field: bool = False):
         """The dmx_params / dmx_rays of a call on `rays` (shared by `prepare` and `channels_direct`): checks the
         selection, uploads it and the per-user rotation.  Returns (params struct, rays struct, tensors to keep alive,
-        largest |selected index|).  spatial_wideband: DMX_FLAG_SPATIAL_WIDEBAND, after `check_wideband_call`."""
+        largest |selected index|).  spatial_wideband: DMX_FLAG_SPATIAL_WIDEBAND, after `check_wideband_call`; near_field:
+        DMX_FLAG_NEAR_FIELD, after `check_near_field_call`."""
+        if near_field:
+            check_near_field_call(params, carrier_freq, spatial_wideband=spatial_wideband)
         if spatial_wideband:
             check_wideband_call(params, carrier_freq)
         dev = self.device
@@ -542,7 +577,8 @@ class ChannelEngine:
         have_dop = rays.doppler_vel is not None and rays.doppler_acc is not None
         p = self._params_struct(params, bs_fov, ue_fov, rot_dev, sel_dev, carrier_freq, have_dop,
                                 sc_hint=uniform_stride(sel))
-        p.flags = (nat.FLAG_ADAPTIVE_TERMS if adaptive_terms else 0) | (nat.FLAG_SPATIAL_WIDEBAND if spatial_wideband else 0)
+        p.flags = ((nat.FLAG_ADAPTIVE_TERMS if adaptive_terms else 0) | (nat.FLAG_SPATIAL_WIDEBAND if spatial_wideband else 0) |
+                   (nat.FLAG_NEAR_FIELD if near_field else 0))
 
         r = nat.DmxRays()
         r.n_ue, r.n_paths, r.ld = n, L, L
@@ -555,17 +591,19 @@ class ChannelEngine:
     # ------------------------------------------------------------------ stage 1
     def prepare(self, rays: DeviceRays, params, bs_fov=None, ue_fov=None, ue_rotation_per_user=None,
                 carrier_freq: float = 0.0, want_side=True, adaptive_terms: bool = False, structs=None,
-                spatial_wideband: bool = False) -> PrepResult:
+                spatial_wideband: bool = False, near_field: bool = False) -> PrepResult:
         """Run dmx_path_prep.  ue_rotation_per_user: optional [N, 3] degrees (numpy/torch).  want_side: True = every
         side product, "light" = LoS / path counts / FoV mask only, False = none.  adaptive_terms: opt into
         DMX_FLAG_ADAPTIVE_TERMS (include/deepmimo_amd.h: weak last path groups in one product term); the flag travels in
         the parameter block of the preparation, so every stage-2 call on it runs in the same mode.  structs: what
         `_call_structs` returned for the same arguments, when the caller has built them already.  spatial_wideband: opt
         into DMX_FLAG_SPATIAL_WIDEBAND (the per-subcarrier array response; `carrier_freq` is then required): it travels in
-        the parameter block too, the records are the same, and `channels` on the preparation runs the wideband body."""
+        the parameter block too, the records are the same, and `channels` on the preparation runs the wideband body.
+        near_field: opt into DMX_FLAG_NEAR_FIELD (spherical-wavefront array tables from the path delay; `carrier_freq` is
+        required): it travels the same way, and every call on the preparation that takes the flag runs with it."""
         n, L = rays.n_ue, rays.n_paths
         p, r, keep, sc_abs_max = structs or self._call_structs(rays, params, bs_fov, ue_fov, ue_rotation_per_user,
-                                                               carrier_freq, adaptive_terms, spatial_wideband)
+                                                               carrier_freq, adaptive_terms, spatial_wideband, near_field)
         keep = list(keep)
 
         nbytes = int(self.lib.dmx_workspace_bytes(C.byref(p), n, L))
@@ -583,7 +621,7 @@ class ChannelEngine:
         """The variant stage 2 runs for `variant` (bounded_fd_variant).  Beyond the bound without a spacing promise the
         library cannot see the indices, so variant 0 is resolved here.  A spatial-wideband preparation runs the fp32 vector
         kernel for variant 0 and 1 at any index; the library refuses every other variant."""
-        if prep.sc_abs_max < SC_ABS_MAX_F32 or prep.params_struct.flags & nat.FLAG_SPATIAL_WIDEBAND:
+        if prep.sc_abs_max < SC_ABS_MAX_F32 or prep.params_struct.flags & (nat.FLAG_SPATIAL_WIDEBAND | nat.FLAG_NEAR_FIELD):
             return variant
         return bounded_fd_variant(int(variant), prep.sc_abs_max, self._small_preferred(prep.params_struct, prep.n_paths_loaded))
 

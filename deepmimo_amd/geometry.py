@@ -52,6 +52,62 @@ def wideband_array_response(shape, spacing: float = 0.5, theta: float = 0, phi: 
     return np.concatenate(cols, axis=1) if cols else np.zeros((len(idx), 0), dtype=np.complex128)
 
 
+def near_field_phase(shape, spacing, theta, phi, distance) -> np.ndarray:
+    """The phase of every element of an [Mh, Mv] panel for a spherical wave, in revolutions (extension): NumPy float64
+    [..., M] over the broadcast shape of ``theta`` (zenith), ``phi`` (azimuth) - radians, in the panel's own frame, what
+    stage 1's rotated angles are - and ``distance`` (wavelengths, >= 0, ``np.inf`` allowed).  Element e = (y, z) sits at
+    ``spacing * (0, y, z)`` wavelengths and the source ``distance`` wavelengths from element 0 along (theta, phi):
+
+        q   = spacing * (y sin(theta) sin(phi) + z cos(theta))                    # the plane-wave phase
+        s   = spacing^2 (y^2 + z^2)
+        psi = R - sqrt(R^2 - 2 R q + s) = (2 R q - s) / (R + sqrt(R^2 - 2 R q + s)),   0 where 2 R q = s
+
+    the definition of DMX_FLAG_NEAR_FIELD (include/deepmimo_amd.h), evaluated in its second form; R = inf gives q."""
+    idx = _ant_indices(shape).astype(np.float64)
+    y, z = idx[:, 1], idx[:, 2]
+    theta, phi, R = np.broadcast_arrays(np.asarray(theta, np.float64), np.asarray(phi, np.float64), np.asarray(distance, np.float64))
+    if np.any(np.isnan(R)) or np.any(R < 0):
+        raise ValueError("near_field_phase: distance must be >= 0 wavelengths (np.inf for the plane wave)")
+    theta, phi, R = theta[..., None], phi[..., None], R[..., None]
+    d = float(spacing)
+    q = d * (y * np.sin(theta) * np.sin(phi) + z * np.cos(theta))
+    s = d * d * (y * y + z * z)
+    far = np.isinf(R)
+    Rf = np.where(far, 0.0, R)
+    num = 2.0 * Rf * q - s
+    arg = np.maximum(Rf * Rf - num, 0.0)
+    den = Rf + np.sqrt(arg)
+    psi = np.where(num == 0.0, 0.0, num / np.where(den == 0.0, 1.0, den))
+    return np.where(far, q, psi)
+
+
+def near_field_response(shape, spacing: float = 0.5, theta=np.pi / 2, phi=0.0, distance=np.inf) -> np.ndarray:
+    """``exp(j 2 pi psi)`` of ``near_field_phase``: the array response of an [Mh, Mv] panel to a spherical wave from
+    ``distance`` wavelengths along zenith ``theta`` / azimuth ``phi`` (radians, the panel's frame), complex128 [..., M],
+    not normalised (extension).  ``distance = np.inf`` is the phase law of ``steering_vec``: ``sqrt(M) *
+    steering_vec(shape, phi=degrees(theta), theta=degrees(phi) - 90, spacing)[:, 0]``.  The amplitude is uniform over the
+    aperture (no 1/r taper), as in the kernels."""
+    return np.exp(2j * np.pi * near_field_phase(shape, spacing, theta, phi, distance))
+
+
+def focus_codebook(shape, spacing: float = 0.5, theta=np.pi / 2, phi=0.0, distance=np.inf) -> np.ndarray:
+    """A polar-domain (beam-focusing) codebook (extension): for arrays of B focal points - ``theta``, ``phi`` in radians,
+    ``distance`` in wavelengths, broadcast against each other - the rows ``conj(near_field_response) / sqrt(M)``,
+    complex128 [B, M], each of unit norm.  Usable as the ``codebook`` of every call that takes one (it is applied without a
+    conjugate): on a near-field view the row at a LoS user's own (theta, phi, R) collects ``sqrt(M) * sum |c|``, which the
+    plane-wave row ``distance = np.inf`` at the same angle no longer does inside the Fraunhofer distance."""
+    resp = near_field_response(shape, spacing, theta, phi, distance)
+    resp = resp.reshape(-1, resp.shape[-1])
+    return np.conj(resp) / np.sqrt(resp.shape[-1])
+
+
+def fraunhofer_distance(shape, spacing: float = 0.5) -> float:
+    """``2 D^2`` in wavelengths, ``D = spacing * sqrt((Mh - 1)^2 + (Mv - 1)^2)`` the panel diagonal (extension): beyond it
+    a spherical wavefront deviates from the plane wave by less than 1/16 wavelength over the aperture."""
+    mh, mv = int(shape[0]), int(shape[1])
+    return 2.0 * float(spacing) ** 2 * float((mh - 1) ** 2 + (mv - 1) ** 2)
+
+
 def pattern_gain(name: str, theta, phi=None):
     """Linear power gain of one antenna element with the radiation pattern `name`, as stage 1 applies it to a path
     (``power_linear_ant_gain = power_linear * g_tx * g_rx``): NumPy float64, angles in RADIANS in the panel's own frame

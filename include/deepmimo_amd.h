@@ -132,8 +132,42 @@ typedef struct dmx_params {
  *   dmx_fd_kernel_choice  answers 1.
  *   every other entry point that takes dmx_params (dmx_channels_fd_lpf, dmx_channels_td, dmx_channels_fd_beams,
  *   dmx_beam_power, dmx_channels_fd_direct, every consumer) and every dmx_*_supported query: DMX_ERR_ARG, with the flag
- *   named in dmx_last_error().  Not covered either: frequency-dependent element patterns and path gains, near field. */
+ *   named in dmx_last_error().  Not covered either: frequency-dependent element patterns and path gains, the squint together
+ *   with the near field (DMX_FLAG_NEAR_FIELD below is refused beside this flag). */
 #define DMX_FLAG_SPATIAL_WIDEBAND 4u
+
+/* Near field: a spherical-wavefront array response per path, in place of the plane wave.  An array is a panel in its local
+ * y-z plane, element e = (y, z) at d (0, y, z) wavelengths, d the spacing; stage 1 writes sy = d sin(th) sin(ph) and
+ * sz = d cos(th), revolutions per step, per path l and end, on the rotated, FoV-filtered angles.  With the flag the path is
+ * a spherical wave from a point at distance R_l wavelengths along its direction, seen from element 0:
+ *   R_l     = dn_l carrier_freq / bandwidth     (= tau_l f_c, the path length in wavelengths, from the record's float32 dn)
+ *   q_e     = y sy_l + z sz_l                   (the plane-wave phase)
+ *   s_e     = d^2 (y^2 + z^2)
+ *   psi_e,l = R_l - sqrt(R_l^2 - 2 R_l q_e + s_e)  revolutions
+ *           = (2 R_l q_e - s_e) / (R_l + sqrt(R_l^2 - 2 R_l q_e + s_e))    (evaluated this way)
+ *           = 0 where the numerator is 0        (element 0 always, where R_l = 0 would make it 0 / 0)
+ *   H_nf[u, r, t, k] = sum_l c_l exp(j 2pi (psi_rx[r,l] + psi_tx[t,l])) exp(-j 2pi dn_l sc_k / N)
+ * psi is float64, reduced to a revolution before the float32 sin / cos as every array table is; the argument of the root
+ * is a squared distance and never negative; R -> infinity gives q_e, the response without the flag; a 1 x 1 array has
+ * psi = 0.  The sum stays separable (H = A G), only the array tables change.  Limits of the model: the amplitude is
+ * uniform over the aperture (no 1/r taper); the radius is the TOTAL path length - exact for LoS and for chains of specular
+ * reflections (the image source), too large for a path through a diffraction or scattering point, which comes out less
+ * curved than it is; the two ends are curved independently, so the cross term between two large arrays (LoS MIMO rank
+ * from sphericity) is not covered.  Everything else per path - the clip at dn >= N, FoV, patterns, Doppler, num_paths,
+ * compaction, LoS - is unchanged, and c_l and dn_l are the same bits as without the flag.
+ * The flag (value 16; 2 and 8 stay unknown bits) needs carrier_freq and bandwidth finite and > 0 wherever it is taken
+ * (else DMX_ERR_ARG, naming the flag and the field), combines with DMX_FLAG_ADAPTIVE_TERMS and is DMX_ERR_ARG together
+ * with DMX_FLAG_SPATIAL_WIDEBAND everywhere:
+ *   dmx_path_prep         accepts it; the records are the same bits.
+ *   dmx_channels_fd       variants 0 and 1 run the fp32 vector kernel with near-field tables; any other explicit variant is
+ *                         DMX_ERR_SHAPE.  dmx_fd_kernel_choice answers 1.
+ *   dmx_channel_covariance, dmx_channel_rate, dmx_channel_spectrum, dmx_channel_precoders, dmx_channels_angle_delay,
+ *   dmx_codebook_rate, dmx_codebook_rate_subbands, dmx_beam_power (scalar projection for every panel) and their
+ *   dmx_*_supported queries accept it with the shape limits of the far field; dmx_cell_rate accepts it per link (links may
+ *   differ in flag and carrier).
+ *   dmx_channels_fd_lpf, dmx_channels_td, dmx_channels_fd_beams, dmx_channels_fd_direct, dmx_fd_direct_supported:
+ *   DMX_ERR_ARG / not taken, with DMX_FLAG_NEAR_FIELD in dmx_last_error(). */
+#define DMX_FLAG_NEAR_FIELD 16u
 
 /* Subcarrier index bound of the float32-phase kernels.  The matrix-core and folded kernels (variants 2-5, 8, 10-12, the
  * beam entry points) reduce the phase dn k / N in float32 as qh (k mod 4096) + ql k, whose error grows linearly with
