@@ -6,9 +6,8 @@ For each shape, on the same uploaded rays, stage 1 included in both:
   (a) fused   dmx_path_prep + dmx_channels_angle_delay                        (no [n, M_rx, R, K] tensor)
   (b) twin    dmx_path_prep + per user chunk: dmx_channels_fd_beams (dmx_channels_fd without a codebook) into a resident
               tensor, torch.fft.ifft(..., n=n_fft, dim=-1)[..., :n_taps] copied into the result
-Device events around back-to-back launches of one route, the routes alternating `--rounds` times after a warm-up; the whole
-A/B runs twice (`pass` 0 and 1) and the difference between the two passes of the SAME route is the spread a difference
-between the routes has to exceed.  One JSON line per shape: mean, minimum and spread of both routes, their ratio, the largest
+Timed by the protocol of `tools/ab_protocol.py` (device events, a warm-up of 1).  One JSON line per shape: the protocol's
+fields per route, their ratio, the largest
 deviation between the two results per user peak (and in units of the 5e-5 bound of the tests), the output bytes per second
 of the fused route against the HBM peak (8 TB/s), and its algorithmic flops (complex product 6, complex multiply-add 8:
 n R n_taps P (6 + 8 M_rx)) as a share of the fp32 vector peak (256 CUs x 4 SIMDs x 64 flop per clock at 2.4 GHz) - both
@@ -24,6 +23,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ab_protocol as ab  # noqa: E402
 import deepmimo_amd as dm  # noqa: E402
 from deepmimo_amd.engine import ChannelEngine  # noqa: E402
 from deepmimo_amd import _native as nat  # noqa: E402
@@ -40,17 +40,7 @@ HBM_PEAK = 8.0e12
 TOL_REL = 5e-5
 
 
-def timed(fn, launches):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(launches):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / launches
-
-
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--paths", type=int, default=25)
     ap.add_argument("--launches", type=int, default=3, help="back-to-back launches of a route per timing")
@@ -58,7 +48,7 @@ def main():
     ap.add_argument("--shapes", default=",".join(s[0] for s in SHAPES))
     ap.add_argument("--scale", type=float, default=1.0, help="multiply every user count (rehearsals)")
     ap.add_argument("--out", default="")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     eng = ChannelEngine(0)
     lib, L = eng.lib, args.paths
     stream = eng._stream_ptr()
@@ -74,7 +64,7 @@ def main():
         p.ofdm.selected_subcarriers = np.arange(K)
         p.validate(n)
         prep = eng.prepare(rays, p, want_side="light")
-        ps, rs, ss = prep.params_struct, prep.rays_struct, prep.side_struct
+        ps, stage1 = prep.params_struct, ab.stage1(eng, prep)
         m_tx, m_rx = int(np.prod(bs)), int(np.prod(ue))
         cb = eng._codebook(dm.dft_codebook(bs)[:rows], m_tx, min_beams=1) if rows else None
         R = rows if rows else m_tx
@@ -89,13 +79,13 @@ def main():
         x_twin = torch.empty((n, m_rx, R, taps), dtype=torch.complex64, device=eng.device)
 
         def fused():
-            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            stage1()
             nat.check(lib.dmx_channels_angle_delay(C.byref(ps), wsp, n, L, 0, n, cbp, R,
                                                    C.c_void_p(bws_full.data_ptr()) if rows else None, nb_full, K, taps,
                                                    C.c_void_p(x_fused.data_ptr()), stream), "dmx_channels_angle_delay")
 
         def twin():
-            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            stage1()
             for b in range(0, n, chunk):
                 cnt = min(chunk, n - b)
                 if rows:
@@ -105,25 +95,12 @@ def main():
                     nat.check(lib.dmx_channels_fd(C.byref(ps), wsp, n, L, b, cnt, C.c_void_p(Y.data_ptr()), 0, stream), "dmx_channels_fd")
                 x_twin[b:b + cnt] = torch.fft.ifft(Y[:cnt], n=K, dim=-1)[..., :taps]
 
-        routes = (("fused", fused), ("twin", twin))
+        routes = [(rn, fn, ab.device(args.launches), ab.device(1)) for rn, fn in (("fused", fused), ("twin", twin))]
         out_bytes = n * m_rx * R * taps * 8
         rec = dict(shape=name, bs=bs, ue=ue, K=K, n_fft=K, n_taps=taps, rows=R, codebook=bool(rows), users=n, paths=L,
                    chunk_users=chunk, out_bytes=out_bytes, twin_tensor_bytes=n * m_rx * R * K * 8,
                    launches_per_route=2 * args.rounds * args.launches, fused_flops=n * R * taps * L * (6 + 8 * m_rx))
-        for ab in range(2):
-            for _, fn in routes:                                         # warm-up
-                timed(fn, 1)
-            ts = {rn: [] for rn, _ in routes}
-            for _ in range(args.rounds):
-                for rn, fn in routes:
-                    ts[rn].append(timed(fn, args.launches))
-            for rn, v in ts.items():
-                rec[f"{rn}_avg_ms_pass{ab}"] = round(float(np.mean(v)), 5)
-                rec[f"{rn}_min_ms_pass{ab}"] = round(float(np.min(v)), 5)
-        for rn, _ in routes:
-            a0, a1 = rec[f"{rn}_avg_ms_pass0"], rec[f"{rn}_avg_ms_pass1"]
-            rec[f"{rn}_avg_ms"] = round((a0 + a1) / 2, 5)
-            rec[f"{rn}_spread_ms"] = round(abs(a0 - a1), 5)
+        rec.update(ab.summaries(ab.alternate(routes, args.rounds)))
         rec["speedup"] = round(rec["twin_avg_ms"] / rec["fused_avg_ms"], 3)
         rec["faster_by_more_than_the_spread"] = bool(rec["twin_avg_ms"] - rec["fused_avg_ms"] > rec["twin_spread_ms"] + rec["fused_spread_ms"])
         peak = x_twin.abs().reshape(n, -1).amax(dim=1).clamp_min(1e-38)
@@ -139,9 +116,7 @@ def main():
         del Y, x_fused, x_twin, prep, rays, bws_full, bws_chunk
         torch.cuda.empty_cache()
     if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        ab.write_lines(args.out, lines, "w")
 
 
 if __name__ == "__main__":

@@ -12,34 +12,22 @@ the 4-beam DFT codebook of the UE, the ray matrices in HBM (torch), `channel_out
   (c) one-sided ds.compute_beam_power(F, p) on the untouched users        [n, B]: no UE combining, mean over the UE elements
                 of |F H|.  It is (a)'s floor: the same kernel on n users of M_rx elements instead of Q * n of one.
 (a) and (c) return NumPy arrays whatever `channel_output` says, and their device-to-host copy and the dBm conversion on the
-host are part of their time; (b) stops at the amplitudes in HBM.  A timing is wall-clock time around the call and the
-release of its result, with a device synchronisation on both sides.  The routes alternate `--rounds` times after a warm-up;
-the whole A/B runs twice (`pass` 0 and 1) and the difference between the two passes of the SAME route is the spread a
-difference between the routes has to exceed.  One JSON line: mean, minimum and spread of every route (and every single
-timing), the times per user, (a)/(b) and (a)/(c) per user, and how far (a) and (b) differ per user.  Without a GPU the tool
-fails."""
+host are part of their time; (b) stops at the amplitudes in HBM.  So the protocol of `tools/ab_protocol.py` runs with its
+host timer, warm-up included.  One JSON line: the protocol's fields per route with every single timing, the times per user,
+(a)/(b) and (a)/(c) per user, and how far (a) and (b) differ per user.  Without a GPU the tool fails."""
 import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ab_protocol as ab  # noqa: E402
 import deepmimo_amd as dm  # noqa: E402
 from deepmimo_amd import dataset as dsm  # noqa: E402
 from oracle import oracle_np as onp  # noqa: E402
-
-
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    res = fn()
-    del res
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3
 
 
 def unfused(ds, p, F, W, chunk):
@@ -57,7 +45,7 @@ def unfused(ds, p, F, W, chunk):
     return out
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--users", type=int, default=100_000)
     ap.add_argument("--paths", type=int, default=25)
@@ -67,7 +55,7 @@ def main():
     ap.add_argument("--unfused-chunk", type=int, default=2048, help="users per beam-space tensor of route (b)")
     ap.add_argument("--rounds", type=int, default=5, help="timings per route and pass")
     ap.add_argument("--out", default="")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         sys.exit("beam_pair_bench: no GPU")
     n, L, K, B = args.users, args.paths, args.subcarriers, args.beams
@@ -97,21 +85,9 @@ def main():
     rec["pair_vs_unfused_worst_rel_err"] = float((np.abs(amp_a - amp_b).reshape(n_b, -1).max(axis=1) / peak).max())
     del amp_a, amp_b
     torch.cuda.empty_cache()
-    for ab in range(2):
-        for _, _, fn in routes:                                         # warm-up
-            timed(fn)
-        ts = {rn: [] for rn, _, _ in routes}
-        for _ in range(args.rounds):
-            for rn, _, fn in routes:
-                ts[rn].append(timed(fn))
-        for rn, v in ts.items():
-            rec[f"{rn}_ms_pass{ab}"] = [round(float(x), 4) for x in v]
-            rec[f"{rn}_avg_ms_pass{ab}"] = round(float(np.mean(v)), 4)
-            rec[f"{rn}_min_ms_pass{ab}"] = round(float(np.min(v)), 4)
+    ts = ab.alternate([(rn, fn, ab.host_timed, ab.host_timed) for rn, _, fn in routes], args.rounds)
+    rec.update(ab.summaries(ts, digits=4, raw=True))
     for rn, users, _ in routes:
-        a0, a1 = rec[f"{rn}_avg_ms_pass0"], rec[f"{rn}_avg_ms_pass1"]
-        rec[f"{rn}_avg_ms"] = round((a0 + a1) / 2, 4)
-        rec[f"{rn}_spread_ms"] = round(abs(a0 - a1), 4)
         rec[f"{rn}_us_per_user"] = round(1e3 * rec[f"{rn}_avg_ms"] / users, 5)
         rec[f"{rn}_spread_us_per_user"] = round(1e3 * rec[f"{rn}_spread_ms"] / users, 5)
     rec["unfused_extrapolated_ms"] = round(rec["unfused_us_per_user"] * n / 1e3, 3)
@@ -123,9 +99,7 @@ def main():
     print(line, flush=True)
     dm.config("channel_output", "numpy")
     if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+        ab.write_lines(args.out, [line], "w")
 
 
 if __name__ == "__main__":

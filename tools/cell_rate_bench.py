@@ -13,9 +13,8 @@ including the B stage-1 passes:
                link's Gram (the serving index is (a)'s), two torch.linalg.slogdet, the mean over the subcarriers.  At the
                headline shape a chunk of H is 4 MB per user, so this route runs on the first `--twin-users` users only, one
                launch per timing; its time is reported for that count and `twin_over_fused_per_user` compares time per user.
-Device events around back-to-back launches of one route, the routes alternating `--rounds` times after a warm-up; the
-whole A/B runs twice (`pass` 0 and 1) and the difference between the two passes of the SAME route is the spread a
-difference between the routes has to exceed.  One JSON line per shape: mean, minimum and spread of every route, (a)/(b),
+Timed by the protocol of `tools/ab_protocol.py` (device events, a warm-up of 1).  One JSON line per shape: the protocol's
+fields per route and the minimum over both passes, (a)/(b),
 (c)/(a) per user, and the largest deviation between (a) and (c) in bit.  Without a GPU the tool fails.
 """
 import argparse
@@ -29,6 +28,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ab_protocol as ab  # noqa: E402
 import deepmimo_amd as dm  # noqa: E402
 from deepmimo_amd.engine import ChannelEngine  # noqa: E402
 from deepmimo_amd import _native as nat  # noqa: E402
@@ -39,17 +39,7 @@ from oracle import oracle_np as onp  # noqa: E402
 SHAPES = [("headline_K512", [64, 4], [2, 2], 512, 100_000, 5_000, 2_500), ("defaults_K1", [8, 1], [1, 1], 1, 200_000, 200_000, 200_000)]
 
 
-def timed(fn, launches):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(launches):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / launches
-
-
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--links", type=int, default=3)
     ap.add_argument("--paths", type=int, default=25)
@@ -62,7 +52,7 @@ def main():
     ap.add_argument("--twin-users", type=int, default=0, help="users of route (c); 0: the shape's own count")
     ap.add_argument("--routes", default="fused,single,twin")
     ap.add_argument("--out", default="")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     eng = ChannelEngine(0)
     lib, L, B = eng.lib, args.paths, args.links
     stream = eng._stream_ptr()
@@ -90,10 +80,11 @@ def main():
         H = torch.empty((chunk, m_rx, m_tx, K), dtype=torch.complex64, device=eng.device) if "twin" in want else None
         eye = torch.eye(m_rx, dtype=torch.complex64, device=eng.device)
 
+        stage1s = [ab.stage1(eng, q) for q in preps]
+
         def prep_all():
-            for q in preps:
-                nat.check(lib.dmx_path_prep(C.byref(q.rays_struct), C.byref(q.params_struct), C.c_void_p(q.workspace.data_ptr()),
-                                            q.workspace_bytes, C.byref(q.side_struct), stream), "dmx_path_prep")
+            for stage1 in stage1s:
+                stage1()
 
         def fused():
             prep_all()
@@ -124,26 +115,13 @@ def main():
                 rk = (torch.linalg.slogdet(N + Gs)[1] - torch.linalg.slogdet(N)[1]) / math.log(2.0)
                 r_twin[u0:u0 + cnt] = torch.where(serving >= 0, rk.mean(dim=1), 0)
 
-        routes = [r for r in (("fused", fused), ("single", single), ("twin", twin)) if r[0] in want]
+        routes = [(rn, fn, ab.device(1 if rn == "twin" and n_twin < n else args.launches), ab.device(1))
+                  for rn, fn in (("fused", fused), ("single", single), ("twin", twin)) if rn in want]
         rec = dict(shape=name, links=B, bs=bs, ue=ue, K=K, users=n, paths=L, snr_db=[args.snr_db] + [args.inr_db] * (B - 1),
                    H_bytes_per_link=n * m_rx * m_tx * K * 8, launches_per_route=2 * args.rounds * args.launches)
-        timed(fused, 1)                                                  # the twin reads the serving index of a fused launch
-        for ab in range(2):
-            for _, fn in routes:                                         # warm-up
-                timed(fn, 1)
-            ts = {rn: [] for rn, _ in routes}
-            for _ in range(args.rounds):
-                for rn, fn in routes:
-                    ts[rn].append(timed(fn, 1 if rn == "twin" and n_twin < n else args.launches))
-            for rn, v in ts.items():
-                rec[f"{rn}_avg_ms_pass{ab}"] = round(float(np.mean(v)), 5)
-                rec[f"{rn}_min_ms_pass{ab}"] = round(float(np.min(v)), 5)
-        for rn, _ in routes:
-            a0, a1 = rec[f"{rn}_avg_ms_pass0"], rec[f"{rn}_avg_ms_pass1"]
-            rec[f"{rn}_avg_ms"] = round((a0 + a1) / 2, 5)
-            rec[f"{rn}_min_ms"] = min(rec[f"{rn}_min_ms_pass0"], rec[f"{rn}_min_ms_pass1"])
-            rec[f"{rn}_spread_ms"] = round(abs(a0 - a1), 5)
-        have = {rn for rn, _ in routes}
+        ab.device_timed(fused, 1)                                        # the twin reads the serving index of a fused launch
+        rec.update(ab.summaries(ab.alternate(routes, args.rounds), overall_min=True))
+        have = {r[0] for r in routes}
         if "fused" in have:
             rec["mean_rate"] = float(r_fused.double().mean())
             rec["served_by_link"] = [int((s_fused == b).sum()) for b in range(B)]
@@ -162,9 +140,7 @@ def main():
         del H, preps, links
         torch.cuda.empty_cache()
     if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        ab.write_lines(args.out, lines, "w")
 
 
 if __name__ == "__main__":

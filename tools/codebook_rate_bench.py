@@ -10,15 +10,13 @@ For each shape, on the same uploaded rays:
               torch.linalg.slogdet of I + s G, the mean over the subcarriers, max and argmax over the codewords.  1 MB per user
               at 64 rows x 4 x 512, so the twin runs on the first `twin users` of the shape only; `speedup_per_user` compares
               time per user - an extrapolation where the counts differ, not a like-for-like run
-Device events around back-to-back launches of one route, the routes alternating `--rounds` times after a warm-up; the whole
-A/B runs twice (`pass` 0 and 1) and the difference between the two passes of the SAME route is the spread a difference
-between the routes has to exceed.  One JSON line per shape: mean, minimum and spread of both routes, the algorithmic flops of
+Timed by the protocol of `tools/ab_protocol.py` (device events, a warm-up of 1).  One JSON line per shape: the protocol's
+fields per route, the algorithmic flops of
 k10_codebook_rate (complex product 6, complex multiply-add 8; the projection not counted) and, from the time of the whole
 fused route, their share of the fp32 vector peak (256 CUs x 4 SIMDs x 64 flop per clock at 2.4 GHz), the largest deviation
 between the two rates in bit and the share of users with the same PMI.  Without a GPU the tool fails.
 """
 import argparse
-import ctypes as C
 import json
 import math
 import os
@@ -28,9 +26,9 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ab_protocol as ab  # noqa: E402
 import deepmimo_amd as dm  # noqa: E402
 from deepmimo_amd.engine import ChannelEngine  # noqa: E402
-from deepmimo_amd import _native as nat  # noqa: E402
 from oracle import oracle_np as onp  # noqa: E402
 
 # (name, BS panel, UE panel, K, codewords, layers, users, twin users, users per chunk of the twin)
@@ -41,17 +39,7 @@ SHAPES = [("headline_L1_C64", [64, 4], [2, 2], 512, 64, 1, 100_000, 4_000, 1_000
 FP32_VALU_PEAK = 256 * 4 * 64 * 2.4e9
 
 
-def timed(fn, launches):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(launches):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / launches
-
-
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--paths", type=int, default=25)
     ap.add_argument("--snr-db", type=float, default=100.0)
@@ -61,10 +49,9 @@ def main():
     ap.add_argument("--scale", type=float, default=1.0, help="multiply every user count (rehearsals)")
     ap.add_argument("--routes", default="fused,twin")
     ap.add_argument("--out", default="")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     eng = ChannelEngine(0)
-    lib, L = eng.lib, args.paths
-    stream = eng._stream_ptr()
+    L = args.paths
     snr = 10.0 ** (args.snr_db / 10.0)
     lines = []
     for name, bs, ue, K, n_cw, n_layers, users, twin_users, chunk in SHAPES:
@@ -79,13 +66,12 @@ def main():
         p.ofdm.selected_subcarriers = np.arange(K)
         p.validate(n)
         prep = eng.prepare(rays, p, want_side="light")
-        ps, rs, ss = prep.params_struct, prep.rays_struct, prep.side_struct
+        stage1 = ab.stage1(eng, prep)
         m_tx, m_rx = int(np.prod(bs)), int(np.prod(ue))
         rows = n_cw * n_layers
         W = torch.from_numpy(dm.dft_codebook(bs)[:rows].reshape(n_cw, n_layers, m_tx)).to(eng.device)
         flat = W.reshape(rows, m_tx)
         Y = torch.empty((chunk, m_rx, rows, K), dtype=torch.complex64, device=eng.device)
-        wsp = C.c_void_p(prep.workspace.data_ptr())
         out = {}
         r_ref = torch.empty((n_twin,), dtype=torch.float32, device=eng.device)
         p_ref = torch.empty((n_twin,), dtype=torch.int64, device=eng.device)
@@ -93,11 +79,11 @@ def main():
         s = snr / n_layers
 
         def fused():
-            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            stage1()
             out["rate"], out["pmi"] = eng.codebook_rate(prep, W, args.snr_db)
 
         def twin():
-            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            stage1()
             for b in range(0, n_twin, chunk):
                 cnt = min(chunk, n_twin - b)
                 eng.channels(prep, out=Y[:cnt], user_begin=b, user_count=cnt, tx_codebook=flat)
@@ -110,28 +96,15 @@ def main():
                 r_ref[b:b + cnt], p_ref[b:b + cnt] = rate_c.max(dim=1)
 
         want = args.routes.split(",")
-        routes = [r for r in (("fused", fused), ("twin", twin)) if r[0] in want]
+        routes = [(rn, fn, ab.device(args.launches), ab.device(1)) for rn, fn in (("fused", fused), ("twin", twin)) if rn in want]
         rec = dict(shape=name, bs=bs, ue=ue, K=K, codewords=n_cw, layers=n_layers, users=n, twin_users=n_twin, paths=L,
                    snr_db=args.snr_db, chunk_users=chunk, beam_tensor_bytes_per_user=m_rx * rows * K * 8,
                    row_table_bytes_per_user=rows * L * 8, launches_per_route=2 * args.rounds * args.launches)
         # per (codeword, subcarrier): rows_pair over the layers (per path one product per row and M_rx multiply-adds), the
         # Gram's upper triangle, the elimination is not counted
         rec["fused_flops"] = n * K * n_cw * (n_layers * L * (6 + 8 * m_rx) + 8 * m_rx * n_layers * (n_layers + 1) // 2)
-        for ab in range(2):
-            for _, fn in routes:                                         # warm-up
-                timed(fn, 1)
-            ts = {rn: [] for rn, _ in routes}
-            for _ in range(args.rounds):
-                for rn, fn in routes:
-                    ts[rn].append(timed(fn, args.launches))
-            for rn, v in ts.items():
-                rec[f"{rn}_avg_ms_pass{ab}"] = round(float(np.mean(v)), 5)
-                rec[f"{rn}_min_ms_pass{ab}"] = round(float(np.min(v)), 5)
-        for rn, _ in routes:
-            a0, a1 = rec[f"{rn}_avg_ms_pass0"], rec[f"{rn}_avg_ms_pass1"]
-            rec[f"{rn}_avg_ms"] = round((a0 + a1) / 2, 5)
-            rec[f"{rn}_spread_ms"] = round(abs(a0 - a1), 5)
-        have = {rn for rn, _ in routes}
+        rec.update(ab.summaries(ab.alternate(routes, args.rounds)))
+        have = {r[0] for r in routes}
         if "fused" in have:
             rec["fused_share_of_fp32_valu_peak"] = round(rec["fused_flops"] / (rec["fused_avg_ms"] * 1e-3) / FP32_VALU_PEAK, 4)
             rec["mean_rate"] = float(out["rate"].double().mean())
@@ -145,9 +118,7 @@ def main():
         del Y, prep, rays, out, r_ref, p_ref
         torch.cuda.empty_cache()
     if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        ab.write_lines(args.out, lines, "w")
 
 
 if __name__ == "__main__":

@@ -2,11 +2,9 @@
 """Single-pass route against the two calls, alternating in ONE process: `python tools/direct_bench.py [--users 200000]`.
 
 For each shape: stage 1 (light side products) + stage 2 (`variant = 0`, i.e. what `single_pass = False` runs) and
-dmx_channels_fd_direct on the same uploaded rays, resident output, the same light side tensors; device events around
-`--launches` back-to-back launches of one route, the routes alternating `--rounds` times after a warm-up.  The whole
-A/B runs twice (`pass` 0 and 1): the difference between the two passes of the SAME route is the spread a difference
-between the routes has to exceed.  One JSON line per shape: average and minimum step time of both routes in both
-passes, algorithmic bytes (rays read + output written) and the share of the 8 TB/s HBM peak they amount to.
+dmx_channels_fd_direct on the same uploaded rays, resident output, the same light side tensors, timed by the protocol of
+`tools/ab_protocol.py` (device events around `--launches` launches, a warm-up of 10).  One JSON line per shape: the
+protocol's fields per route, algorithmic bytes (rays read + output written) and the share of the 8 TB/s HBM peak they amount to.
 `--profile` runs every route a few times only (for `rocprofv3 --kernel-trace --stats -- python tools/direct_bench.py --profile`).
 """
 import argparse
@@ -19,6 +17,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ab_protocol as ab  # noqa: E402
 import deepmimo_amd as dm  # noqa: E402
 from deepmimo_amd.engine import ChannelEngine  # noqa: E402
 from deepmimo_amd import _native as nat  # noqa: E402
@@ -30,17 +29,7 @@ SHAPES = [([8, 1], [1, 1], 1), ([8, 1], [1, 1], 16), ([8, 8], [1, 1], 1), ([8, 8
           ([8, 8], [2, 2], 8)]
 
 
-def timed(fn, launches):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(launches):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / launches
-
-
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--users", type=int, default=200000)
     ap.add_argument("--paths", type=int, default=25)
@@ -49,7 +38,7 @@ def main():
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--sweep", action="store_true", help="antenna pairs x K grid of the small-output region instead of the "
                     "shape list (the crossover table next to engine.single_pass_route)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     eng = ChannelEngine(0)
     lib = eng.lib
     n, L = args.users, args.paths
@@ -66,6 +55,7 @@ def main():
         p.validate(n)
         prep = eng.prepare(rays, p, want_side="light")
         ps, rs, ss = prep.params_struct, prep.rays_struct, prep.side_struct
+        stage1 = ab.stage1(eng, prep)
         out = torch.empty(eng.channel_shape(prep), dtype=torch.complex64, device=eng.device)
         wsp, outp = C.c_void_p(prep.workspace.data_ptr()), C.c_void_p(out.data_ptr())
         pairs = int(np.prod(bs) * np.prod(ue))
@@ -76,7 +66,7 @@ def main():
         rec["floor_ms"] = rec["bytes"] / HBM_PEAK * 1e3
 
         def two_calls():
-            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            stage1()
             nat.check(lib.dmx_channels_fd(C.byref(ps), wsp, n, L, 0, n, outp, 0, stream), "dmx_channels_fd")
 
         def single_pass():
@@ -92,20 +82,9 @@ def main():
                     fn()
             torch.cuda.synchronize()
             continue
-        for ab in range(2):
-            for _, fn in routes:                                   # warm-up
-                timed(fn, 10)
-            ts = {name: [] for name, _ in routes}
-            for _ in range(args.rounds):
-                for name, fn in routes:
-                    ts[name].append(timed(fn, args.launches))
-            for name, v in ts.items():
-                rec[f"{name}_avg_ms_pass{ab}"] = round(float(np.mean(v)), 5)
-                rec[f"{name}_min_ms_pass{ab}"] = round(float(np.min(v)), 5)
+        ts = ab.alternate([(name, fn, ab.device(args.launches), ab.device(10)) for name, fn in routes], args.rounds)
+        rec.update(ab.summaries(ts))
         for name, _ in routes:
-            a0, a1 = rec[f"{name}_avg_ms_pass0"], rec[f"{name}_avg_ms_pass1"]
-            rec[f"{name}_avg_ms"] = round((a0 + a1) / 2, 5)
-            rec[f"{name}_spread_ms"] = round(abs(a0 - a1), 5)
             rec[f"{name}_share_of_peak"] = round(rec["floor_ms"] / rec[f"{name}_avg_ms"], 4)
         if "single_pass_avg_ms" in rec:
             rec["speedup"] = round(rec["two_calls_avg_ms"] / rec["single_pass_avg_ms"], 3)

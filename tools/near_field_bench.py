@@ -13,9 +13,8 @@ arrays (200k users, 8 x 1 / 1 x 1, K = 512).  Seven routes on the same uploaded 
   beam_power_near, beam_power_far  dmx_path_prep + dmx_beam_power with 64 beams, with and without the flag (with it the
                projection is the scalar kernel for every panel)
 
-Device events around `--launches` back-to-back launches, `--rounds` of them per route after a warm-up, the routes alternating;
-the whole measurement runs twice (pass 0 and 1) and the difference between the two passes of the SAME route is the spread a
-difference between routes has to exceed.  One JSON line per (shape, route), appended to `--out`.
+Timed by the protocol of `tools/ab_protocol.py` (device events, a warm-up of 1).  One JSON line per (shape, route) with the
+protocol's fields unprefixed, appended to `--out`.
 """
 import argparse
 import ctypes as C
@@ -27,6 +26,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ab_protocol as ab  # noqa: E402
 import bench  # noqa: E402
 import deepmimo_amd as dm  # noqa: E402
 from deepmimo_amd import _native as nat  # noqa: E402
@@ -38,17 +38,7 @@ CARRIER, BANDWIDTH, BEAMS, SNR_DB = 28e9, 400e6, 64, 10.0
 TWINS = {"near": ("far_v1", "far_auto"), "rate_near": ("rate_far",), "beam_power_near": ("beam_power_far",)}
 
 
-def timed(fn, launches):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(launches):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / launches
-
-
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--label", default="this", help="which build this is (a field of every line)")
     ap.add_argument("--out", default=os.path.join("profiles", "r16_near_field_bench.jsonl"))
@@ -57,7 +47,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--shapes", nargs="+", default=[s["name"] for s in SHAPES], choices=[s["name"] for s in SHAPES])
     ap.add_argument("--scale", type=float, default=1.0, help="multiply both user counts (a rehearsal at a small size)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     eng = ChannelEngine(0)
     lib, dev, L = eng.lib, eng.device, args.paths
     stream = eng._stream_ptr()
@@ -82,11 +72,10 @@ def main():
 
         def add(route, near, call, what, **extra):
             prep = preps[near]
-            ps, rs, ss = prep.params_struct, prep.rays_struct, prep.side_struct
-            wsp, nb = C.c_void_p(prep.workspace.data_ptr()), prep.workspace_bytes
+            ps, wsp, stage1 = prep.params_struct, C.c_void_p(prep.workspace.data_ptr()), ab.stage1(eng, prep)
 
             def both():
-                nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, nb, C.byref(ss), stream), "dmx_path_prep")
+                stage1()
                 results[route] = call(prep, ps, wsp)
             runs.append((dict(build=args.label, shape=sh["name"], bs=sh["bs"], ue=sh["ue"], K=sh["K"], users=n, paths=L, route=route,
                               near_field=near, carrier_hz=CARRIER, bandwidth_hz=BANDWIDTH, calls="dmx_path_prep + " + what, **extra), both))
@@ -104,20 +93,10 @@ def main():
             tag = "near" if near else "far"
             add(f"rate_{tag}", near, lambda prep, ps, wsp: eng.rate(prep, SNR_DB), "dmx_channel_rate", snr_db=SNR_DB)
             add(f"beam_power_{tag}", near, lambda prep, ps, wsp: eng.beam_power(prep, F, want_best=False)[0], "dmx_beam_power", beams=BEAMS)
-        for ab in range(2):
-            for _, both in runs:                                    # warm-up
-                timed(both, 1)
-            ts = {rec["route"]: [] for rec, _ in runs}
-            for _ in range(args.rounds):
-                for rec, both in runs:
-                    ts[rec["route"]].append(timed(both, args.launches))
-            for rec, _ in runs:
-                rec[f"avg_ms_pass{ab}"] = round(float(np.mean(ts[rec["route"]])), 5)
-                rec[f"min_ms_pass{ab}"] = round(float(np.min(ts[rec["route"]])), 5)
+        ts = ab.alternate([(rec["route"], both, ab.device(args.launches), ab.device(1)) for rec, both in runs], args.rounds)
         by_route = {}
         for rec, _ in runs:
-            rec["avg_ms"] = round((rec["avg_ms_pass0"] + rec["avg_ms_pass1"]) / 2, 5)
-            rec["spread_ms"] = round(abs(rec["avg_ms_pass0"] - rec["avg_ms_pass1"]), 5)
+            rec.update(ab.summary(ts[rec["route"]]))
             by_route[rec["route"]] = rec
         for near, twins in TWINS.items():
             for twin in twins:
@@ -144,11 +123,7 @@ def main():
             lines.append(rec)
         del runs, out, rays, preps, results
         torch.cuda.empty_cache()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "a") as fh:
-        for rec in lines:
-            fh.write(json.dumps(rec) + "\n")
-            print(json.dumps(rec), flush=True)
+    ab.write_lines(args.out, [json.dumps(rec) for rec in lines], "a", echo=True)
 
 
 if __name__ == "__main__":

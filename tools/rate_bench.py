@@ -19,9 +19,8 @@ For each shape, on the same uploaded rays:
                 its time is reported for that count)
   (h) svd       (g)'s unfused twin: (b)'s channel chunks and torch.linalg.svd of H_k, the first singular pair kept, on the
                 first `--eig-users` users only, one launch per timing; `beams_speedup_per_user` compares time per user
-Device events around back-to-back launches of one route, the routes alternating `--rounds` times after a warm-up; the
-whole A/B runs twice (`pass` 0 and 1) and the difference between the two passes of the SAME route is the spread a
-difference between the routes has to exceed.  One JSON line per shape: mean, minimum and spread of both routes, the fused
+Timed by the protocol of `tools/ab_protocol.py` (device events, a warm-up of 1).  One JSON line per shape: the protocol's
+fields per route, the fused
 kernel's algorithmic flops (complex product 6, complex multiply-add 8) and their share of the fp32 vector peak (256 CUs x
 4 SIMDs x 64 flop per clock at 2.4 GHz), and the largest deviation between the two results in bit.  Without a GPU the
 tool fails.
@@ -37,6 +36,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ab_protocol as ab  # noqa: E402
 import deepmimo_amd as dm  # noqa: E402
 from deepmimo_amd.engine import ChannelEngine  # noqa: E402
 from deepmimo_amd import _native as nat  # noqa: E402
@@ -48,17 +48,7 @@ SHAPES = [("headline_K512", [64, 4], [2, 2], 512, 100_000, 5_000), ("defaults_K1
 FP32_VALU_PEAK = 256 * 4 * 64 * 2.4e9
 
 
-def timed(fn, launches):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(launches):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / launches
-
-
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--paths", type=int, default=25)
     ap.add_argument("--snr-db", type=float, default=110.0)
@@ -70,7 +60,7 @@ def main():
     ap.add_argument("--beam-users", type=int, default=20000, help="users of route (g)")
     ap.add_argument("--routes", default="fused,slogdet,spectrum,modes,eigvalsh,beams,beams2,svd")
     ap.add_argument("--out", default="")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     eng = ChannelEngine(0)
     lib, L = eng.lib, args.paths
     stream = eng._stream_ptr()
@@ -87,7 +77,7 @@ def main():
         p.ofdm.selected_subcarriers = np.arange(K)
         p.validate(n)
         prep = eng.prepare(rays, p, want_side="light")
-        ps, rs, ss = prep.params_struct, prep.rays_struct, prep.side_struct
+        ps, stage1 = prep.params_struct, ab.stage1(eng, prep)
         m_tx, m_rx = int(np.prod(bs)), int(np.prod(ue))
         m, big = min(m_tx, m_rx), max(m_tx, m_rx)
         H = torch.empty((chunk, m_rx, m_tx, K), dtype=torch.complex64, device=eng.device)
@@ -110,12 +100,12 @@ def main():
         s = snr / m_tx
 
         def fused():
-            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            stage1()
             nat.check(lib.dmx_channel_rate(C.byref(ps), wsp, n, L, 0, n, snr, C.c_void_p(r_fused.data_ptr()), None, stream),
                       "dmx_channel_rate")
 
         def slogdet():
-            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            stage1()
             for b in range(0, n, chunk):
                 cnt = min(chunk, n - b)
                 nat.check(lib.dmx_channels_fd(C.byref(ps), wsp, n, L, b, cnt, C.c_void_p(H.data_ptr()), 0, stream), "dmx_channels_fd")
@@ -123,17 +113,17 @@ def main():
                 r_ref[b:b + cnt] = (torch.linalg.slogdet(eye + s * G)[1] / math.log(2.0)).mean(dim=1)
 
         def spectrum():
-            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            stage1()
             nat.check(lib.dmx_channel_spectrum(C.byref(ps), wsp, n, L, 0, n, snr, None, C.c_void_p(r_wf.data_ptr()), None, stream),
                       "dmx_channel_spectrum")
 
         def modes():
-            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            stage1()
             nat.check(lib.dmx_channel_spectrum(C.byref(ps), wsp, n, L, 0, n, snr, C.c_void_p(g_fused.data_ptr()), None, None, stream),
                       "dmx_channel_spectrum")
 
         def eigvalsh():
-            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            stage1()
             for b in range(0, n_eig, chunk):
                 cnt = min(chunk, n_eig - b)
                 nat.check(lib.dmx_channels_fd(C.byref(ps), wsp, n, L, b, cnt, C.c_void_p(H.data_ptr()), 0, stream), "dmx_channels_fd")
@@ -143,7 +133,7 @@ def main():
         def beam_call(count, with_big):
             small, bigp = C.c_void_p(b_small.data_ptr()), C.c_void_p(b_big.data_ptr()) if with_big else None
             tx, rx = (bigp, small) if m_rx <= m_tx else (small, bigp)
-            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            stage1()
             nat.check(lib.dmx_channel_precoders(C.byref(ps), wsp, n, L, 0, count, snr, 1, C.c_void_p(b_gamma.data_ptr()), tx, rx, stream),
                       "dmx_channel_precoders")
 
@@ -154,33 +144,21 @@ def main():
             beam_call(n_beam, True)
 
         def svd():
-            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
+            stage1()
             for b in range(0, n_eig, chunk):
                 cnt = min(chunk, n_eig - b)
                 nat.check(lib.dmx_channels_fd(C.byref(ps), wsp, n, L, b, cnt, C.c_void_p(H.data_ptr()), 0, stream), "dmx_channels_fd")
                 _, _, vh = torch.linalg.svd(H[:cnt].permute(0, 3, 1, 2) * math.sqrt(snr), full_matrices=False)
                 v_ref[b:b + cnt] = vh[..., 0, :].conj()
 
-        routes = [r for r in (("fused", fused), ("slogdet", slogdet), ("spectrum", spectrum), ("modes", modes), ("eigvalsh", eigvalsh),
-                              ("beams", beams), ("beams2", beams2), ("svd", svd)) if r[0] in want]
+        routes = [(rn, fn, ab.device(1 if rn in ("eigvalsh", "svd") else args.launches), ab.device(1))
+                  for rn, fn in (("fused", fused), ("slogdet", slogdet), ("spectrum", spectrum), ("modes", modes), ("eigvalsh", eigvalsh),
+                                 ("beams", beams), ("beams2", beams2), ("svd", svd)) if rn in want]
         rec = dict(shape=name, bs=bs, ue=ue, K=K, users=n, paths=L, snr_db=args.snr_db, chunk_users=chunk,
                    H_bytes=n * m_rx * m_tx * K * 8, launches_per_route=2 * args.rounds * args.launches)
         rec["fused_flops"] = n * K * big * (L * (6 + 8 * m) + 8 * m * (m + 1) // 2)
-        for ab in range(2):
-            for _, fn in routes:                                         # warm-up
-                timed(fn, 1)
-            ts = {rn: [] for rn, _ in routes}
-            for _ in range(args.rounds):
-                for rn, fn in routes:
-                    ts[rn].append(timed(fn, 1 if rn in ("eigvalsh", "svd") else args.launches))
-            for rn, v in ts.items():
-                rec[f"{rn}_avg_ms_pass{ab}"] = round(float(np.mean(v)), 5)
-                rec[f"{rn}_min_ms_pass{ab}"] = round(float(np.min(v)), 5)
-        for rn, _ in routes:
-            a0, a1 = rec[f"{rn}_avg_ms_pass0"], rec[f"{rn}_avg_ms_pass1"]
-            rec[f"{rn}_avg_ms"] = round((a0 + a1) / 2, 5)
-            rec[f"{rn}_spread_ms"] = round(abs(a0 - a1), 5)
-        have = {rn for rn, _ in routes}
+        rec.update(ab.summaries(ab.alternate(routes, args.rounds)))
+        have = {r[0] for r in routes}
         if {"fused", "slogdet"} <= have:
             rec["speedup"] = round(rec["slogdet_avg_ms"] / rec["fused_avg_ms"], 3)
             rec["max_dev_bit"] = float((r_fused - r_ref).abs().max())
@@ -219,9 +197,7 @@ def main():
         del H, prep, rays, b_gamma, b_small, b_big, v_ref, g_fused, g_ref
         torch.cuda.empty_cache()
     if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        ab.write_lines(args.out, lines, "w")
 
 
 if __name__ == "__main__":

@@ -10,14 +10,12 @@ For each shape, on the same uploaded rays and the same workspace, stage 1 includ
                 sub-selection sc[s B : (s + 1) B], n_sb preparations and n_sb projections of the codebook.  The sub-selection
                 is set in the parameter block of the one preparation (pointer and count) and restored afterwards, which is
                 what n_sb preparations of their own compute, without n_sb workspaces
-Device events around back-to-back launches of one route, the routes alternating `--rounds` times after a warm-up; the whole
-run twice (`pass` 0 and 1) and the difference between the two passes of the SAME route is the spread a difference between
-routes has to exceed.  One JSON line per shape: mean, minimum and spread of each route, (a) / (b) and (c) / (a), whether (a)
+Timed by the protocol of `tools/ab_protocol.py` (device events, a warm-up of 1).  One JSON line per shape: the protocol's
+fields per route, (a) / (b) and (c) / (a), whether (a)
 is faster than (c) by more than the two spreads, and whether the subband outputs of (a) equal the results of (c) bit for bit.
 Without a GPU the tool fails.
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -26,9 +24,9 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ab_protocol as ab  # noqa: E402
 import deepmimo_amd as dm  # noqa: E402
 from deepmimo_amd.engine import ChannelEngine  # noqa: E402
-from deepmimo_amd import _native as nat  # noqa: E402
 from oracle import oracle_np as onp  # noqa: E402
 
 # (name, BS panel, UE panel, K, codewords, layers, subband size, users)
@@ -37,17 +35,7 @@ SHAPES = [("headline_C64_B32", [64, 4], [2, 2], 512, 64, 1, 32, 100_000),
           ("defaults_C8_B32", [8, 1], [1, 1], 512, 8, 1, 32, 200_000)]
 
 
-def timed(fn, launches):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(launches):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / launches
-
-
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--paths", type=int, default=25)
     ap.add_argument("--snr-db", type=float, default=100.0)
@@ -57,10 +45,9 @@ def main():
     ap.add_argument("--scale", type=float, default=1.0, help="multiply every user count (rehearsals)")
     ap.add_argument("--routes", default="subbands,wideband,loop")
     ap.add_argument("--out", default="")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     eng = ChannelEngine(0)
-    lib, L = eng.lib, args.paths
-    stream = eng._stream_ptr()
+    L = args.paths
     lines = []
     for name, bs, ue, K, n_cw, n_layers, B, users in SHAPES:
         if name not in args.shapes.split(","):
@@ -72,17 +59,13 @@ def main():
         p.ofdm.selected_subcarriers = np.arange(K)
         p.validate(n)
         prep = eng.prepare(rays, p, want_side="light")
-        ps, rs, ss = prep.params_struct, prep.rays_struct, prep.side_struct
+        ps, stage1 = prep.params_struct, ab.stage1(eng, prep)
         m_tx = int(np.prod(bs))
         W = torch.from_numpy(dm.dft_codebook(bs)[:n_cw * n_layers].reshape(n_cw, n_layers, m_tx)).to(eng.device)
-        wsp = C.c_void_p(prep.workspace.data_ptr())
         sel_ptr, n_sb = int(ps.selected_subcarriers), (K + B - 1) // B
         out = {}
         loop_rate = torch.empty((n, n_sb), dtype=torch.float32, device=eng.device)
         loop_pmi = torch.empty((n, n_sb), dtype=torch.int32, device=eng.device)
-
-        def stage1():
-            nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, prep.workspace_bytes, C.byref(ss), stream), "dmx_path_prep")
 
         def subbands():
             stage1()
@@ -103,24 +86,12 @@ def main():
                 ps.selected_subcarriers, ps.n_selected = sel_ptr, K
 
         want = args.routes.split(",")
-        routes = [r for r in (("subbands", subbands), ("wideband", wideband), ("loop", loop)) if r[0] in want]
+        routes = [(rn, fn, ab.device(args.launches), ab.device(1))
+                  for rn, fn in (("subbands", subbands), ("wideband", wideband), ("loop", loop)) if rn in want]
         rec = dict(shape=name, bs=bs, ue=ue, K=K, codewords=n_cw, layers=n_layers, subband_size=B, subbands=n_sb, users=n, paths=L,
                    snr_db=args.snr_db, launches_per_route=2 * args.rounds * args.launches)
-        for ab in range(2):
-            for _, fn in routes:                                         # warm-up
-                timed(fn, 1)
-            ts = {rn: [] for rn, _ in routes}
-            for _ in range(args.rounds):
-                for rn, fn in routes:
-                    ts[rn].append(timed(fn, args.launches))
-            for rn, v in ts.items():
-                rec[f"{rn}_avg_ms_pass{ab}"] = round(float(np.mean(v)), 5)
-                rec[f"{rn}_min_ms_pass{ab}"] = round(float(np.min(v)), 5)
-        for rn, _ in routes:
-            a0, a1 = rec[f"{rn}_avg_ms_pass0"], rec[f"{rn}_avg_ms_pass1"]
-            rec[f"{rn}_avg_ms"] = round((a0 + a1) / 2, 5)
-            rec[f"{rn}_spread_ms"] = round(abs(a0 - a1), 5)
-        have = {rn for rn, _ in routes}
+        rec.update(ab.summaries(ab.alternate(routes, args.rounds)))
+        have = {r[0] for r in routes}
         if "subbands" in have:
             rec["mean_rate"] = float(out["rate"].double().mean())
             rec["mean_rate_sb"] = float(out["rate_sb"].double().mean())
@@ -138,9 +109,7 @@ def main():
         del prep, rays, out, loop_rate, loop_pmi
         torch.cuda.empty_cache()
     if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        ab.write_lines(args.out, lines, "w")
 
 
 if __name__ == "__main__":

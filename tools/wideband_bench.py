@@ -10,9 +10,8 @@ channels written into a resident tensor:
   narrow_v1   the narrowband call forced to the same kernel, variant = 1: (wideband / narrow_v1) is what the body costs
   narrow_auto the narrowband automatic route, variant = 0: (wideband / narrow_auto) is the price of the effect
 
-Device events around `--launches` back-to-back launches, `--rounds` of them per route after a warm-up, the routes alternating;
-the whole measurement runs twice (pass 0 and 1) and the difference between the two passes of the SAME route is the spread a
-difference between routes has to exceed.  One JSON line per (shape, route), appended to `--out`.
+Timed by the protocol of `tools/ab_protocol.py` (device events, a warm-up of 1).  One JSON line per (shape, route) with the
+protocol's fields unprefixed, appended to `--out`.
 """
 import argparse
 import ctypes as C
@@ -24,6 +23,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ab_protocol as ab  # noqa: E402
 import bench  # noqa: E402
 import deepmimo_amd as dm  # noqa: E402
 from deepmimo_amd import _native as nat  # noqa: E402
@@ -35,17 +35,7 @@ SHAPES = [dict(name="headline", bs=[8, 8], ue=[2, 2], K=512, users=100_000),
 CARRIER, BANDWIDTH = 28e9, 400e6
 
 
-def timed(fn, launches):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(launches):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / launches
-
-
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--label", default="this", help="which build this is (a field of every line)")
     ap.add_argument("--out", default=os.path.join("profiles", "r15_wideband_bench.jsonl"))
@@ -54,7 +44,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--shapes", nargs="+", default=[s["name"] for s in SHAPES], choices=[s["name"] for s in SHAPES])
     ap.add_argument("--scale", type=float, default=1.0, help="multiply both user counts (a rehearsal at a small size)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     eng = ChannelEngine(0)
     lib, dev, L = eng.lib, eng.device, args.paths
     stream = eng._stream_ptr()
@@ -74,29 +64,19 @@ def main():
         runs = []
         for route, wideband, variant in ROUTES:
             prep = eng.prepare(rays, p, want_side="light", carrier_freq=CARRIER, spatial_wideband=wideband)
-            ps, rs, ss = prep.params_struct, prep.rays_struct, prep.side_struct
+            ps = prep.params_struct
             rec = dict(build=args.label, shape=sh["name"], bs=sh["bs"], ue=sh["ue"], K=sh["K"], users=n, paths=L, route=route,
                        carrier_hz=CARRIER, bandwidth_hz=BANDWIDTH, variant=variant, kernel=int(lib.dmx_fd_kernel_choice(C.byref(ps), L))
                        if variant == 0 else variant, calls="dmx_path_prep + dmx_channels_fd")
 
-            def both(rs=rs, ps=ps, ss=ss, wsp=C.c_void_p(prep.workspace.data_ptr()), nb=prep.workspace_bytes, variant=variant):
-                nat.check(lib.dmx_path_prep(C.byref(rs), C.byref(ps), wsp, nb, C.byref(ss), stream), "dmx_path_prep")
+            def both(ps=ps, stage1=ab.stage1(eng, prep), wsp=C.c_void_p(prep.workspace.data_ptr()), variant=variant):
+                stage1()
                 nat.check(lib.dmx_channels_fd(C.byref(ps), wsp, n, L, 0, n, outp, variant, stream), "dmx_channels_fd")
             runs.append((rec, prep, both))
-        for ab in range(2):
-            for _, _, both in runs:                                 # warm-up
-                timed(both, 1)
-            ts = {rec["route"]: [] for rec, _, _ in runs}
-            for _ in range(args.rounds):
-                for rec, _, both in runs:
-                    ts[rec["route"]].append(timed(both, args.launches))
-            for rec, _, _ in runs:
-                rec[f"avg_ms_pass{ab}"] = round(float(np.mean(ts[rec["route"]])), 5)
-                rec[f"min_ms_pass{ab}"] = round(float(np.min(ts[rec["route"]])), 5)
+        ts = ab.alternate([(rec["route"], both, ab.device(args.launches), ab.device(1)) for rec, _, both in runs], args.rounds)
         by_route = {}
         for rec, _, _ in runs:
-            rec["avg_ms"] = round((rec["avg_ms_pass0"] + rec["avg_ms_pass1"]) / 2, 5)
-            rec["spread_ms"] = round(abs(rec["avg_ms_pass0"] - rec["avg_ms_pass1"]), 5)
+            rec.update(ab.summary(ts[rec["route"]]))
             by_route[rec["route"]] = rec
         for rec, _, _ in runs:
             rec["wideband_over_this"] = round(by_route["wideband"]["avg_ms"] / rec["avg_ms"], 4)
@@ -118,11 +98,7 @@ def main():
             rec["check_sc0_rel"], rec["check_edge_rel"] = round(float(d0.max()), 9), round(float(d_edge.max()), 5)
         del runs, out, rays
         torch.cuda.empty_cache()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "a") as fh:
-        for rec in lines:
-            fh.write(json.dumps(rec) + "\n")
-            print(json.dumps(rec), flush=True)
+    ab.write_lines(args.out, [json.dumps(rec) for rec in lines], "a", echo=True)
 
 
 if __name__ == "__main__":
