@@ -33,8 +33,9 @@ static int check_patterns(const dmx_params* p) {
     return DMX_OK;
 }
 
-// `takes`: which of DMX_FLAG_SPATIAL_WIDEBAND (dmx_path_prep and dmx_channels_fd only) and DMX_FLAG_NEAR_FIELD (those two, the
-// consumers, dmx_beam_power and their dmx_*_supported queries) the caller takes; a flag it does not take is refused here
+// `takes`: which of DMX_FLAG_SPATIAL_WIDEBAND (dmx_path_prep and dmx_channels_fd only), DMX_FLAG_NEAR_FIELD (those two, the
+// consumers, dmx_beam_power and their dmx_*_supported queries) and DMX_FLAG_BEAM_MEAN_POWER (dmx_beam_power only) the caller
+// takes; a flag it does not take is refused here
 static int check_params(const dmx_params* p, uint32_t takes = 0) {
     if (!p) { set_error("params is NULL"); return DMX_ERR_ARG; }
     for (int i = 0; i < 2; ++i) {
@@ -45,7 +46,13 @@ static int check_params(const dmx_params* p, uint32_t takes = 0) {
     }
     if (check_patterns(p)) return DMX_ERR_ARG;
     if (p->num_paths < 0) { set_error("num_paths must be >= 0"); return DMX_ERR_ARG; }
-    if ((p->flags & ~(DMX_FLAG_ADAPTIVE_TERMS | DMX_FLAG_SPATIAL_WIDEBAND | DMX_FLAG_NEAR_FIELD)) != 0 || p->reserved0 != 0) { set_error("unknown bits in dmx_params.flags / reserved0"); return DMX_ERR_ARG; }
+    if ((p->flags & ~(DMX_FLAG_ADAPTIVE_TERMS | DMX_FLAG_SPATIAL_WIDEBAND | DMX_FLAG_NEAR_FIELD | DMX_FLAG_BEAM_MEAN_POWER)) != 0 ||
+        p->reserved0 != 0) { set_error("unknown bits in dmx_params.flags / reserved0"); return DMX_ERR_ARG; }
+    if ((p->flags & DMX_FLAG_BEAM_MEAN_POWER) && !(takes & DMX_FLAG_BEAM_MEAN_POWER)) {
+        set_error("DMX_FLAG_BEAM_MEAN_POWER is an option of the dmx_beam_power call alone: no other entry point takes it, "
+                  "dmx_path_prep included");
+        return DMX_ERR_ARG;
+    }
     if ((p->flags & DMX_FLAG_NEAR_FIELD) && (p->flags & DMX_FLAG_SPATIAL_WIDEBAND)) {
         set_error("DMX_FLAG_NEAR_FIELD | DMX_FLAG_SPATIAL_WIDEBAND: the two are not covered together");
         return DMX_ERR_ARG;
@@ -297,6 +304,7 @@ int dmx_fd_kernel_choice(const dmx_params* prm, int32_t n_paths_loaded) {
     if (n_paths_loaded < 0 || prm->n_selected < 0 || prm->bs_shape[0] < 1 || prm->bs_shape[1] < 1 || prm->ue_shape[0] < 1 ||
         prm->ue_shape[1] < 1) { set_error("bad shape"); return DMX_ERR_SHAPE; }
     if (check_patterns(prm)) return DMX_ERR_ARG;
+    if (prm->flags & DMX_FLAG_BEAM_MEAN_POWER) { set_error("DMX_FLAG_BEAM_MEAN_POWER is an option of the dmx_beam_power call alone"); return DMX_ERR_ARG; }
     if (prm->flags & (DMX_FLAG_SPATIAL_WIDEBAND | DMX_FLAG_NEAR_FIELD)) return 1;
     WsView ws{};
     ws.P = used_paths(prm, n_paths_loaded);
@@ -376,7 +384,8 @@ int dmx_beam_power(const dmx_params* prm, const void* workspace, int64_t n_ue, i
                    void* beam_workspace, size_t beam_workspace_bytes_, float* out_mean_amp, int32_t* out_best_beam,
                    void* stream) {
     WsView ws;
-    int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_mean_amp, &ws, DMX_FLAG_NEAR_FIELD);
+    int rc = stage2_common(prm, workspace, n_ue, n_paths_loaded, user_begin, user_count, out_mean_amp, &ws,
+                           DMX_FLAG_NEAR_FIELD | DMX_FLAG_BEAM_MEAN_POWER);
     if (rc) return rc;
     if ((rc = check_beam_call(prm, "dmx_beam_power", codebook_c64, n_beams, 1))) return rc;
     if (prm->n_selected < 1) { set_error("dmx_beam_power needs at least one selected subcarrier"); return DMX_ERR_ARG; }

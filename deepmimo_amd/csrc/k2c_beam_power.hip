@@ -42,7 +42,7 @@ struct BeamPowArgs {
     double inv_n;
     const float2* ftab;      // [user_count, n_beams, P]
     const int32_t* fexp;     // [user_count]
-    float* out;              // [user_count, n_beams] mean amplitude
+    float* out;              // [user_count, n_beams] mean amplitude (PWR: mean power)
     int32_t* best;           // [user_count] argmax_b (first maximum), -1 without paths; may be nullptr
     int adaptive;            // 1 = a weak last K-step may take one product term
     NearFieldEnd nf;         // DMX_FLAG_NEAR_FIELD, the UE end (array_phase.h); the BS end is inside ftab
@@ -54,8 +54,10 @@ __host__ __device__ inline size_t beam_pow_lds_bytes(int M, int NW) {
 }
 
 // NF: the receive-side phase of the A' fill is the near-field one (DMX_FLAG_NEAR_FIELD); its own instantiations, the
-// far-field ones compile as before (the kernel sits at its register cap)
-template <int NW, bool NF = false>
+// far-field ones compile as before (the kernel sits at its register cap).
+// PWR: DMX_FLAG_BEAM_MEAN_POWER - the row sums collect |Y|^2 = re^2 + im^2 itself, not its square root, and the scale is
+// squared with them; tables, A' / B' generation, the MFMA chain, the row-sum layout and its fixed order are shared.
+template <int NW, bool NF = false, bool PWR = false>
 __global__ __launch_bounds__(NW * 64, 4) void k2c_beam_power(WsView ws, BeamPowArgs a, int64_t user_count) {
     constexpr int BP_WAVES = NW, BP_CHUNK = NW / 4, MAX_ROWS = 32 * NW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -226,7 +228,8 @@ __global__ __launch_bounds__(NW * 64, 4) void k2c_beam_power(WsView ws, BeamPowA
                         for (int i = 0; i < 8; ++i) {
                             const pv2 re = {are[2 * i], are[2 * i + 1]}, im = {aim[2 * i], aim[2 * i + 1]};
                             const pv2 p = __builtin_elementwise_fma(re, re, im * im);
-                            rowsum[i] += pv2{__builtin_amdgcn_sqrtf(p.x), __builtin_amdgcn_sqrtf(p.y)};
+                            if constexpr (PWR) rowsum[i] += p;
+                            else rowsum[i] += pv2{__builtin_amdgcn_sqrtf(p.x), __builtin_amdgcn_sqrtf(p.y)};
                         }
                     }
                 }
@@ -253,6 +256,7 @@ __global__ __launch_bounds__(NW * 64, 4) void k2c_beam_power(WsView ws, BeamPowA
                 for (int g = 0; g < BP_WAVES / ntp; ++g) t += rs[((blk * BP_WAVES + g * ntp + tile) << 5) + (w & 31)];
             }
             t *= norm;
+            if constexpr (PWR) t *= misc[0];             // misc[0]^2 / (M_rx K), the large sum first: misc[0]^2 alone may underflow
             a.out[(size_t)ul * B + b] = t;
             bbuf_f[b] = t;                               // the strip buffer is idle here
         }
@@ -292,8 +296,11 @@ int launch_beam_power(const dmx_params& prm, const WsView& ws, int64_t user_begi
     a.best = out_best;
     a.adaptive = (prm.flags & DMX_FLAG_ADAPTIVE_TERMS) ? 1 : 0;     // default: three product terms everywhere
     a.nf = near_field_of(prm).rx();
-    const auto kernel = a.nf.on ? (nw == 4 ? k2c_beam_power<4, true> : k2c_beam_power<8, true>)
-                                : (nw == 4 ? k2c_beam_power<4> : k2c_beam_power<8>);
+    const bool pwr = (prm.flags & DMX_FLAG_BEAM_MEAN_POWER) != 0;
+    const auto kernel = pwr ? (a.nf.on ? (nw == 4 ? k2c_beam_power<4, true, true> : k2c_beam_power<8, true, true>)
+                                       : (nw == 4 ? k2c_beam_power<4, false, true> : k2c_beam_power<8, false, true>))
+                            : (a.nf.on ? (nw == 4 ? k2c_beam_power<4, true> : k2c_beam_power<8, true>)
+                                       : (nw == 4 ? k2c_beam_power<4> : k2c_beam_power<8>));
     int64_t grid = resident_workgroups(kernel, nw * 64, smem);
     // a few users per workgroup let the dispatcher balance the tail (k2_channel_fd_mfma.hip: ITEMS_PER_WG)
     const int64_t g4 = user_count / 4;

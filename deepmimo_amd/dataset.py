@@ -511,7 +511,8 @@ class Dataset(DotDict):
         cb = codebook if hasattr(codebook, "shape") else np.asarray(codebook)
         return eng.channels_to_host(prep, tx_codebook=cb)
 
-    def compute_beam_power(self, codebook, params: Optional[ChannelGenParameters] = None, return_best: bool = False):
+    def compute_beam_power(self, codebook, params: Optional[ChannelGenParameters] = None, return_best: bool = False,
+                           metric: str = "amplitude"):
         """Received power per beam of a TX codebook [n_beams, M_tx] - the beam sweep of docs/manual.ipynb cells
         105 / 110 / 112 in one call, with no channel tensor written anywhere (extension):
 
@@ -520,17 +521,27 @@ class Dataset(DotDict):
             best_beams      = np.argmax(recv_bf_pwr_dbm, axis=1) as float, NaN where dataset.los == -1
 
         Returns ``recv_bf_pwr_dbm`` float64 [n_ue, n_beams] (and ``best_beams`` with ``return_best``).  The raw means stay
-        available as ``dataset['beam_mean_amplitude']`` (float32 [n_ue, n_beams])."""
+        available as ``dataset['beam_mean_amplitude']`` (float32 [n_ue, n_beams]).
+
+        ``metric="power"`` averages the power instead, what 3GPP calls RSRP (an SSB sweep, an L1-RSRP report, cell selection):
+
+            mean_power      = (np.abs(codebook @ dataset.channel) ** 2).mean(axis=1).mean(axis=-1)
+            recv_bf_pwr_dbm = np.around(10 * np.log10(mean_power) + 30, 1)
+
+        with the same NaN rule and ``best_beams``; the raw means are kept as ``dataset['beam_mean_power']``.  The two
+        metrics do not always agree on the best beam.  Any other ``metric`` raises ValueError before any GPU work."""
+        from .engine import check_beam_metric
+        power = check_beam_metric("compute_beam_power", metric)
         self._call_params(params)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
-        amp, _ = eng.beam_power(prep, codebook, want_best=False)
+        amp, _ = eng.beam_power(prep, codebook, want_best=False, metric=metric)
         amp = amp.cpu().numpy()
-        self._data["beam_mean_amplitude"] = amp
+        self._data["beam_mean_power" if power else "beam_mean_amplitude"] = amp
         no_paths = self[c.LOS_PARAM_NAME] == -1
         pwr = np.zeros(amp.shape) * np.nan                                      # float64, as the notebook allocates it
         with np.errstate(divide="ignore"):
-            pwr[~no_paths] = np.around(20 * np.log10(amp[~no_paths]) + 30, 1)
+            pwr[~no_paths] = np.around((10 if power else 20) * np.log10(amp[~no_paths]) + 30, 1)
         if not return_best:
             return pwr
         best = np.argmax(pwr, axis=1).astype(float) if pwr.shape[1] else np.zeros(len(pwr))
@@ -1295,7 +1306,7 @@ class Dataset(DotDict):
         return self._split_users("split_rx_beams", x, Q, n, "n_rx_beams * n_ue")
 
     def compute_beam_pair_power(self, tx_codebook, rx_codebook="dft", params: Optional[ChannelGenParameters] = None,
-                                return_best: bool = False):
+                                return_best: bool = False, metric: str = "amplitude"):
         """Received power of every pair of a UE beam and a BS beam - the two-sided beam sweep in one call, with the semantics
         of ``compute_beam_power`` and no channel or beam-space tensor written anywhere (extension).  For a BS codebook F
         [B, M_tx] and a UE combining codebook W [Q, M_rx] (``"dft"``: ``dm.dft_codebook`` of the UE panel):
@@ -1310,11 +1321,13 @@ class Dataset(DotDict):
         (float32 [n_ue, Q, B]).  W is applied without a conjugate, like F.  It runs the beam-power kernel on the
         ``with_rx_combiner`` view, a block of UE beams at a time.  A bad codebook on either side, the time domain,
         ``rx_filter = 1`` or a subcarrier index beyond the bound of the beam entry points raise ValueError before any GPU
-        work."""
+        work.  ``metric="power"`` as in ``compute_beam_power``: the mean of ``np.abs(.) ** 2``, ``10 * np.log10``, and the raw
+        means as ``dataset['beam_pair_mean_power']``; any other name raises ValueError alike."""
         import torch
         from .combiner import check_rx_codebook
-        from .engine import check_beam_bound, check_selection
+        from .engine import check_beam_bound, check_beam_metric, check_selection
         who = "compute_beam_pair_power"
+        power = check_beam_metric(who, metric)
         self._refuse_on_near_field(who, "the combiner's response to a path is the plane-wave one")
         params = self._call_params(params)
         bs_shape = params[c.PARAMSET_ANT_BS][c.PARAMSET_ANT_SHAPE]
@@ -1340,14 +1353,14 @@ class Dataset(DotDict):
             np.random.seed(1001)
             _, prep = view._run_prep(want_side="light")
             # the block's small [nb, n_ue, B] result into its user-major place in HBM: a strided copy of the amplitudes alone
-            amp[:, b:b + nb] = eng.beam_power(prep, F, want_best=False)[0].view(nb, n_ue, B).permute(1, 0, 2)
+            amp[:, b:b + nb] = eng.beam_power(prep, F, want_best=False, metric=metric)[0].view(nb, n_ue, B).permute(1, 0, 2)
         amp = amp.cpu().numpy()
-        self._data["beam_pair_mean_amplitude"] = amp
+        self._data["beam_pair_mean_power" if power else "beam_pair_mean_amplitude"] = amp
         # compute_beam_power's np.around(20 * np.log10(amp) + 30, 1) in float32, then float64: the same operations per
         # element, in place on the one temporary - at 100k users x 4 x 64 pairs the passes over it are the cost of the call
         with np.errstate(divide="ignore"):
             dbm = np.log10(amp)
-        dbm *= 20
+        dbm *= 10 if power else 20
         dbm += 30
         pwr = np.around(dbm, 1, out=dbm).astype(np.float64)
         pwr[no_paths] = np.nan
@@ -1433,7 +1446,7 @@ class Dataset(DotDict):
 class MacroDataset:
     """List of Datasets (one per TX / RX-set pair); attribute access and method calls fan out to
     every child, a single child returns its value unwrapped (dataset.py:888-998).  Methods of its own: `compute_cell_rate`
-    reads all children in one launch, `at_times` and `with_rx_combiner` return a MacroDataset of the children's views."""
+    reads all children in one launch, `compute_serving_beam` sweeps every child and picks a cell per user, `at_times` and `with_rx_combiner` return a MacroDataset of the children's views."""
 
     SINGLE_ACCESS_METHODS = {"info"}
     PROPAGATE_METHODS = {name for name, _ in inspect.getmembers(Dataset, predicate=inspect.isfunction)
@@ -1507,6 +1520,44 @@ class MacroDataset:
         res = runs[0][0].cell_rate([prep for _, prep in runs], snr_db, serving=serving, per_subcarrier=per_subcarrier,
                                    details=details)
         return Dataset._deliver(res)
+
+    def compute_serving_beam(self, codebook, params=None, metric: str = "power"):
+        """Serving cell and beam of every user from a beam sweep of every child - cell selection on RSRP - every child one
+        cell over the same users (extension).  Each child runs ``compute_beam_power(codebook, params, metric=metric)``; a
+        cell's value for a user is that of its best beam, and the user is served by the cell of largest value, the first on
+        ties, among the cells that have a path to it.
+
+        ``codebook``: one array [n_beams, M_tx] for all children, or a list or tuple with one per child (the BS arrays and
+        the beam counts may differ); ``params`` alike.  Returns a DotDict: ``dbm_by_cell`` float64 [n_ue, n_cells], NaN where
+        the cell has no path to the user; ``beam_by_cell`` int32 [n_ue, n_cells], -1 alike; ``serving`` int32 [n_ue], -1
+        where no cell has a path - it goes as it is into ``compute_cell_rate(serving=...)``; ``beam`` int32 [n_ue] and
+        ``dbm`` float64 [n_ue], the serving cell's beam and value, -1 and NaN alike.  Children of unequal ``n_ue``, a list of
+        another length than the children or a ``metric`` other than "amplitude" / "power" raise ValueError before any GPU
+        work."""
+        from .engine import check_beam_metric, select_serving_beam
+        who = "compute_serving_beam"
+        check_beam_metric(who, metric)
+        n_cells = len(self.datasets)
+        if n_cells < 1:
+            raise ValueError(f"{who}: the MacroDataset is empty")
+        n_ue = int(self.datasets[0].n_ue)
+        if any(int(d.n_ue) != n_ue for d in self.datasets):
+            raise ValueError(f"{who}: the children must cover the same users (equal n_ue), got "
+                             f"{[int(d.n_ue) for d in self.datasets]}")
+        cbs = list(codebook) if isinstance(codebook, (list, tuple)) else [codebook] * n_cells
+        plist = list(params) if isinstance(params, (list, tuple)) else [params] * n_cells
+        if len(cbs) != n_cells or len(plist) != n_cells:
+            raise ValueError(f"{who}: {len(cbs)} codebooks and {len(plist)} parameter sets for {n_cells} children")
+        dbm_by_cell = np.full((n_ue, n_cells), np.nan)
+        beam_by_cell = np.full((n_ue, n_cells), -1, np.int32)
+        rows = np.arange(n_ue)
+        for i, (d, cb, prm) in enumerate(zip(self.datasets, cbs, plist)):
+            pwr, best = d.compute_beam_power(cb, prm, return_best=True, metric=metric)
+            has = ~np.isnan(best)
+            beam_by_cell[has, i] = best[has].astype(np.int32)
+            dbm_by_cell[has, i] = pwr[rows[has], beam_by_cell[has, i]]
+        serving, beam, dbm = select_serving_beam(dbm_by_cell, beam_by_cell)
+        return DotDict({"dbm_by_cell": dbm_by_cell, "beam_by_cell": beam_by_cell, "serving": serving, "beam": beam, "dbm": dbm})
 
     def at_times(self, times, carrier_freq=None) -> "MacroDataset":
         """A MacroDataset of the children's ``Dataset.at_times(times, carrier_freq)`` views - T * n_ue users each, time-major

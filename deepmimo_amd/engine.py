@@ -174,6 +174,44 @@ def check_beam_bound(sc_abs_max: int):
                          f"(DMX_SC_ABS_MAX_F32); the selection reaches {sc_abs_max}")
 
 
+BEAM_METRICS = ("amplitude", "power")
+
+
+def check_beam_metric(who: str, metric) -> bool:
+    """The `metric` of a beam sweep: False for "amplitude" (mean |F H|, the notebook's), True for "power" (mean |F H|^2,
+    RSRP: DMX_FLAG_BEAM_MEAN_POWER); ValueError for anything else."""
+    if not isinstance(metric, str) or metric not in BEAM_METRICS:
+        raise ValueError(f"{who}: metric must be 'amplitude' or 'power', got {metric!r}")
+    return metric == "power"
+
+
+def select_serving_beam(dbm_by_cell, beam_by_cell):
+    """Serving cell and beam of every user from the per-cell best-beam values (pure NumPy): `dbm_by_cell` float [n_ue, n_cells],
+    NaN where the cell has no path to the user, `beam_by_cell` that beam's index.  Returns (serving int32 [n_ue]: the first
+    maximum over the cells that have a path, -1 where none has; beam int32 [n_ue]: the serving cell's beam, -1 alike;
+    dbm float64 [n_ue]: its value, NaN alike)."""
+    dbm_by_cell = np.asarray(dbm_by_cell, dtype=np.float64)
+    beam_by_cell = np.asarray(beam_by_cell)
+    if dbm_by_cell.ndim != 2 or beam_by_cell.shape != dbm_by_cell.shape:
+        raise ValueError(f"select_serving_beam: dbm_by_cell and beam_by_cell must be [n_ue, n_cells] alike, got "
+                         f"{dbm_by_cell.shape} and {beam_by_cell.shape}")
+    n_ue, n_cells = dbm_by_cell.shape
+    none = np.isnan(dbm_by_cell).all(axis=1) if n_cells else np.ones(n_ue, bool)
+    serving = np.full(n_ue, -1, np.int32)
+    beam = np.full(n_ue, -1, np.int32)
+    dbm = np.full(n_ue, np.nan)
+    if n_cells:
+        # first maximum; a NaN cell never wins, not even against a cell whose power underflowed to 0 (-inf dBm)
+        key = np.maximum(dbm_by_cell, np.finfo(np.float64).min)
+        key[np.isnan(dbm_by_cell)] = -np.inf
+        arg = np.argmax(key, axis=1)
+        rows = np.arange(n_ue)
+        serving[~none] = arg[~none]
+        beam[~none] = beam_by_cell[rows, arg][~none]
+        dbm[~none] = dbm_by_cell[rows, arg][~none]
+    return serving, beam, dbm
+
+
 WIDEBAND_VARIANTS = (0, 1)
 
 
@@ -849,10 +887,13 @@ class ChannelEngine:
         return self._pool
 
     def beam_power(self, prep: PrepResult, tx_codebook, user_begin: int = 0, user_count: Optional[int] = None,
-                   want_best: bool = True):
+                   want_best: bool = True, metric: str = "amplitude"):
         """dmx_beam_power: the beam-sweep reduction of docs/manual.ipynb cell 105 without any [N, ., K] tensor.
         Returns (mean_amplitude float32 [user_count, n_beams], best_beam int32 [user_count] or None), both in HBM:
-        mean_amplitude[u, b] = np.abs(F @ H[u]).mean(axis=0).mean(axis=-1)."""
+        mean_amplitude[u, b] = np.abs(F @ H[u]).mean(axis=0).mean(axis=-1).  metric "power": the power average (RSRP),
+        (np.abs(F @ H[u]) ** 2).mean(axis=0).mean(axis=-1), linear, and its first maximum - DMX_FLAG_BEAM_MEAN_POWER on a copy
+        of the preparation's parameter block, for this call only."""
+        power = check_beam_metric("beam_power", metric)
         p = prep.params_struct
         user_count = self._users(prep.n_ue, user_begin, user_count)
         m_tx = p.bs_shape[0] * p.bs_shape[1]
@@ -868,8 +909,12 @@ class ChannelEngine:
         with torch.cuda.device(self.device):
             nbytes = int(self.lib.dmx_beam_workspace_bytes(C.byref(p), user_count, prep.n_paths_loaded, nb))
             bws = self._scratch(nbytes)
-            rc = self.lib.dmx_beam_power(*self._record_args(prep, user_begin, user_count), _ptr(cb), nb, _ptr(bws), nbytes,
-                                         _ptr(amp), _ptr(best), self._stream_ptr())
+            args = self._record_args(prep, user_begin, user_count)
+            if power:
+                call_p = nat.DmxParams.from_buffer_copy(p)       # the pointers inside stay owned by the preparation
+                call_p.flags |= nat.FLAG_BEAM_MEAN_POWER
+                args = (C.byref(call_p),) + args[1:]
+            rc = self.lib.dmx_beam_power(*args, _ptr(cb), nb, _ptr(bws), nbytes, _ptr(amp), _ptr(best), self._stream_ptr())
             nat.check(rc, "dmx_beam_power")
         return amp, best
 

@@ -169,6 +169,15 @@ typedef struct dmx_params {
  *   DMX_ERR_ARG / not taken, with DMX_FLAG_NEAR_FIELD in dmx_last_error(). */
 #define DMX_FLAG_NEAR_FIELD 16u
 
+/* Power-averaged beam sweep (RSRP): dmx_beam_power reports mean |F H|^2 in place of mean |F H|.  The flag (value 64; 2, 8
+ * and 32 stay unknown bits) is an option of that one call, not of the preparation: the workspace is that of dmx_path_prep
+ * WITHOUT the flag, and dmx_beam_power is the only entry point that takes it.  It combines with DMX_FLAG_ADAPTIVE_TERMS and
+ * with DMX_FLAG_NEAR_FIELD.  Every other entry point that takes a dmx_params block - dmx_path_prep, dmx_channels_fd,
+ * dmx_channels_fd_lpf, dmx_channels_td, dmx_channels_fd_beams, dmx_channels_fd_direct, dmx_fd_kernel_choice, every consumer,
+ * every link of dmx_cell_rate - and every dmx_*_supported query: DMX_ERR_ARG, with DMX_FLAG_BEAM_MEAN_POWER in dmx_last_error().  The
+ * values are defined at dmx_beam_power below. */
+#define DMX_FLAG_BEAM_MEAN_POWER 64u
+
 /* Subcarrier index bound of the float32-phase kernels.  The matrix-core and folded kernels (variants 2-5, 8, 10-12, the
  * beam entry points) reduce the phase dn k / N in float32 as qh (k mod 4096) + ql k, whose error grows linearly with
  * |k|: they meet the error claim above (~2e-6 of a user's peak) only while every selected |k| is below this bound.  The
@@ -290,6 +299,12 @@ int dmx_channels_fd_beams(const dmx_params* prm, const void* workspace, int64_t 
  *   out_best_beam[u]   = argmax_b out_mean_amp[u, b] (first maximum; -1 for a user without paths)   int32 [user_count], may be NULL
  * (cells 110 / 112 take argmax / max of the rounded dBm values 20 log10(.) + 30: the host does that on the small
  * [N, n_beams] result).  Frequency domain without rx_filter; same workspace as dmx_channels_fd_beams.
+ * With DMX_FLAG_BEAM_MEAN_POWER in prm->flags (for this call only: the records were prepared without it) the two outputs are
+ * the power average, what 3GPP calls RSRP, from the same matrix-core products one instruction before the square root:
+ *   out_mean_amp[u, b] = 1 / (M_rx K) * sum_rx sum_k | sum_tx F[b,tx] H[u, rx, tx, k] |^2      linear, the channel's 1/sqrt(N) included
+ *   out_best_beam[u]   = its first maximum (-1 and zeros for a user without paths)
+ * Both forms sum in a fixed order (no atomics): a launch repeats bit for bit, and a sub-range of users gives the same rows
+ * as a whole launch.  The power form is scaled once at the end in float32: a mean below FLT_MIN may come out as 0.
  */
 int dmx_beam_power(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
                    int64_t user_begin, int64_t user_count, const void* codebook_c64, int32_t n_beams,
