@@ -16,6 +16,7 @@ FLAG_ADAPTIVE_TERMS = 1
 FLAG_SPATIAL_WIDEBAND = 4                 # DMX_FLAG_SPATIAL_WIDEBAND: per-subcarrier array response (beam squint)
 FLAG_NEAR_FIELD = 16                      # DMX_FLAG_NEAR_FIELD: spherical-wavefront array response per path
 FLAG_BEAM_MEAN_POWER = 64                 # DMX_FLAG_BEAM_MEAN_POWER: dmx_beam_power reports mean |F H|^2 (RSRP); that call only
+FLAG_RX_LINEAR_MMSE = 256                 # DMX_FLAG_RX_LINEAR_MMSE: per-layer SINR rate of a linear MMSE receiver; the codebook-rate calls only
 
 EXPORTED_SYMBOLS = ("dmx_version", "dmx_last_error", "dmx_workspace_bytes", "dmx_decode_max_delay",
                     "dmx_path_prep", "dmx_channels_fd", "dmx_channels_td", "dmx_channels_fd_lpf",

@@ -34,8 +34,9 @@ static int check_patterns(const dmx_params* p) {
 }
 
 // `takes`: which of DMX_FLAG_SPATIAL_WIDEBAND (dmx_path_prep and dmx_channels_fd only), DMX_FLAG_NEAR_FIELD (those two, the
-// consumers, dmx_beam_power and their dmx_*_supported queries) and DMX_FLAG_BEAM_MEAN_POWER (dmx_beam_power only) the caller
-// takes; a flag it does not take is refused here
+// consumers, dmx_beam_power and their dmx_*_supported queries), DMX_FLAG_BEAM_MEAN_POWER (dmx_beam_power only) and
+// DMX_FLAG_RX_LINEAR_MMSE (dmx_codebook_rate, dmx_codebook_rate_subbands and their two queries only) the caller takes; a flag
+// it does not take is refused here
 static int check_params(const dmx_params* p, uint32_t takes = 0) {
     if (!p) { set_error("params is NULL"); return DMX_ERR_ARG; }
     for (int i = 0; i < 2; ++i) {
@@ -46,11 +47,17 @@ static int check_params(const dmx_params* p, uint32_t takes = 0) {
     }
     if (check_patterns(p)) return DMX_ERR_ARG;
     if (p->num_paths < 0) { set_error("num_paths must be >= 0"); return DMX_ERR_ARG; }
-    if ((p->flags & ~(DMX_FLAG_ADAPTIVE_TERMS | DMX_FLAG_SPATIAL_WIDEBAND | DMX_FLAG_NEAR_FIELD | DMX_FLAG_BEAM_MEAN_POWER)) != 0 ||
+    if ((p->flags & ~(DMX_FLAG_ADAPTIVE_TERMS | DMX_FLAG_SPATIAL_WIDEBAND | DMX_FLAG_NEAR_FIELD | DMX_FLAG_BEAM_MEAN_POWER |
+                      DMX_FLAG_RX_LINEAR_MMSE)) != 0 ||
         p->reserved0 != 0) { set_error("unknown bits in dmx_params.flags / reserved0"); return DMX_ERR_ARG; }
     if ((p->flags & DMX_FLAG_BEAM_MEAN_POWER) && !(takes & DMX_FLAG_BEAM_MEAN_POWER)) {
         set_error("DMX_FLAG_BEAM_MEAN_POWER is an option of the dmx_beam_power call alone: no other entry point takes it, "
                   "dmx_path_prep included");
+        return DMX_ERR_ARG;
+    }
+    if ((p->flags & DMX_FLAG_RX_LINEAR_MMSE) && !(takes & DMX_FLAG_RX_LINEAR_MMSE)) {
+        set_error("DMX_FLAG_RX_LINEAR_MMSE is an option of the dmx_codebook_rate and dmx_codebook_rate_subbands calls and their "
+                  "dmx_*_supported queries alone: no other entry point takes it, dmx_path_prep included");
         return DMX_ERR_ARG;
     }
     if ((p->flags & DMX_FLAG_NEAR_FIELD) && (p->flags & DMX_FLAG_SPATIAL_WIDEBAND)) {
@@ -158,10 +165,10 @@ static dmx_side side_or_none(const dmx_side* side) {
 
 // Before the shape rule: the parameter block, the user range, what the entry point found `missing` (counted only with users
 // to run) or `misaligned` among its pointers - the message, or nullptr - around the workspace alignment, and plain frequency
-// domain under the entry point's name `fn`.
+// domain under the entry point's name `fn`.  `takes`: check_params' mask.
 static int consumer_args(const char* fn, const dmx_params* prm, const void* workspace, int64_t n_ue, int64_t user_begin,
-                         int64_t user_count, const char* missing, const char* misaligned) {
-    int rc = check_params(prm, DMX_FLAG_NEAR_FIELD);
+                         int64_t user_count, const char* missing, const char* misaligned, uint32_t takes = DMX_FLAG_NEAR_FIELD) {
+    int rc = check_params(prm, takes);
     if (rc || (rc = check_user_range(n_ue, user_begin, user_count))) return rc;
     if (user_count > 0 && missing) { set_error("%s", missing); return DMX_ERR_ARG; }
     if ((rc = check_workspace_aligned(workspace))) return rc;
@@ -183,10 +190,10 @@ static int check_snr(const char* what, double snr_linear) {
 // What a launching entry point returns for that answer:
 static int shape_status(int shape) { return shape < 0 ? shape : shape == 0 ? DMX_ERR_SHAPE : DMX_OK; }
 
-// a dmx_*_supported query: the parameter block, then the shape rule
+// a dmx_*_supported query: the parameter block (`takes`: check_params' mask), then the shape rule
 template <class Shape>
-static int supported(const dmx_params* prm, Shape shape) {
-    const int rc = check_params(prm, DMX_FLAG_NEAR_FIELD);
+static int supported(const dmx_params* prm, Shape shape, uint32_t takes = DMX_FLAG_NEAR_FIELD) {
+    const int rc = check_params(prm, takes);
     return rc ? rc : shape();
 }
 
@@ -305,6 +312,10 @@ int dmx_fd_kernel_choice(const dmx_params* prm, int32_t n_paths_loaded) {
         prm->ue_shape[1] < 1) { set_error("bad shape"); return DMX_ERR_SHAPE; }
     if (check_patterns(prm)) return DMX_ERR_ARG;
     if (prm->flags & DMX_FLAG_BEAM_MEAN_POWER) { set_error("DMX_FLAG_BEAM_MEAN_POWER is an option of the dmx_beam_power call alone"); return DMX_ERR_ARG; }
+    if (prm->flags & DMX_FLAG_RX_LINEAR_MMSE) {
+        set_error("DMX_FLAG_RX_LINEAR_MMSE is an option of the dmx_codebook_rate and dmx_codebook_rate_subbands calls alone");
+        return DMX_ERR_ARG;
+    }
     if (prm->flags & (DMX_FLAG_SPATIAL_WIDEBAND | DMX_FLAG_NEAR_FIELD)) return 1;
     WsView ws{};
     ws.P = used_paths(prm, n_paths_loaded);
@@ -681,8 +692,11 @@ static int codebook_rate_shape(const dmx_params* prm, int32_t n_paths_loaded, in
     return 1;
 }
 
+// the codebook-rate calls and their queries take the receiver option beside the near field
+static constexpr uint32_t CODEBOOK_RATE_TAKES = DMX_FLAG_NEAR_FIELD | DMX_FLAG_RX_LINEAR_MMSE;
+
 int dmx_codebook_rate_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_codewords, int32_t n_layers) {
-    return supported(prm, [&] { return codebook_rate_shape(prm, n_paths_loaded, n_codewords, n_layers); });
+    return supported(prm, [&] { return codebook_rate_shape(prm, n_paths_loaded, n_codewords, n_layers); }, CODEBOOK_RATE_TAKES);
 }
 
 // the checks dmx_codebook_rate and dmx_codebook_rate_subbands share, up to the shape; `out` is the output that must not be NULL,
@@ -694,7 +708,8 @@ static int codebook_rate_args(const char* fn, const dmx_params* prm, const void*
     snprintf(snr_name, sizeof(snr_name), "%s: snr_linear", fn);
     const int rc = consumer_args(fn, prm, workspace, n_ue, user_begin, user_count,
                                  !workspace || !out ? WS_OUT_NULL : !codebook_c64 ? "codebook missing" : nullptr,
-                                 out_misaligned ? out_misaligned : (uintptr_t)codebook_c64 & 7u ? "codebook must be 8-byte aligned" : nullptr);
+                                 out_misaligned ? out_misaligned : (uintptr_t)codebook_c64 & 7u ? "codebook must be 8-byte aligned" : nullptr,
+                                 CODEBOOK_RATE_TAKES);
     return rc ? rc : check_snr(snr_name, snr_linear);
 }
 
@@ -730,7 +745,8 @@ static int codebook_rate_subbands_shape(const dmx_params* prm, int32_t n_paths_l
 
 int dmx_codebook_rate_subbands_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_codewords, int32_t n_layers,
                                          int32_t subband_size) {
-    return supported(prm, [&] { return codebook_rate_subbands_shape(prm, n_paths_loaded, n_codewords, n_layers, subband_size); });
+    return supported(prm, [&] { return codebook_rate_subbands_shape(prm, n_paths_loaded, n_codewords, n_layers, subband_size); },
+                     CODEBOOK_RATE_TAKES);
 }
 
 int dmx_codebook_rate_subbands(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,

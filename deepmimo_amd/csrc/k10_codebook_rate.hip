@@ -43,6 +43,11 @@
 // rate_sb[:, s], pmi_sb[:, s] are what the wideband kernel gives for the selection sc[s B : (s + 1) B], and with one
 // subband all six outputs are the wideband kernel's; with more than one the wideband outputs are another summation order of
 // the same terms (held to the oracle tolerance only).  LDS of one wave: (M_rx + min(C L, rc) + min(B, K, 64)) * P * 8 bytes.
+//
+// Linear MMSE receiver (DMX_FLAG_RX_LINEAR_MMSE, the template parameter MMSE): phase 4 ends in epilogue_mmse<L> on the same Gram
+// registers, sum_i log2(1 + sinr_i) = -sum_i log2 [(I + s G)^-1]_ii from L eliminations of L x L (k7_rate_body.h), in place of
+// epilogue_logdet<L>.  Nothing else differs, so every statement above on bits and order holds with the flag on both sides.
+// Instantiated for L >= 2 only: one layer is its own MMSE rate and the launcher takes the instantiation without the flag.
 #include "dmx_common.h"
 #include "k2_small_body.h"
 #include "k7_rate_body.h"
@@ -95,8 +100,9 @@ __device__ __forceinline__ void chunk_best(float acc, float inv, int src_lane, i
     v = __shfl(v, 0, 64); vi = __shfl(vi, 0, 64);
 }
 
-// SB = false: the wideband kernel (sb unused, out_rate not NULL); SB = true: the subband form, every wideband output optional
-template <int M, int L, bool SB>
+// SB = false: the wideband kernel (sb unused, out_rate not NULL); SB = true: the subband form, every wideband output optional.
+// MMSE: the receiver of DMX_FLAG_RX_LINEAR_MMSE, epilogue_mmse<L> on the Gram in place of epilogue_logdet<L> (L > 1 only)
+template <int M, int L, bool SB, bool MMSE>
 __device__ __forceinline__ void codebook_rate_body(const WsView& ws, const CbArgs& a, const SbArgs& sb, float* __restrict__ out_rate,
                                                    int32_t* __restrict__ out_pmi, float* __restrict__ out_rate_c) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -212,7 +218,8 @@ __device__ __forceinline__ void codebook_rate_body(const WsView& ws, const CbArg
                                     if (q > p) { gr[q * L + p] = 0.f; gi[q * L + p] = 0.f; }
                                 }
                             }
-                            lg = epilogue_logdet<L>(gr, gi);
+                            if constexpr (MMSE) lg = epilogue_mmse<L>(gr, gi);
+                            else lg = epilogue_logdet<L>(gr, gi);
                         }
                         for (int d = 1; d < a.kcp; d <<= 1) lg += __shfl_xor(lg, d, 64);
                         acc += kl == it ? lg : 0.f;
@@ -251,16 +258,16 @@ __device__ __forceinline__ void codebook_rate_body(const WsView& ws, const CbArg
     }
 }
 
-template <int M, int L>
+template <int M, int L, bool MMSE = false>
 __global__ __launch_bounds__(256) void k10_codebook_rate(WsView ws, CbArgs a, float* __restrict__ out_rate,
                                                          int32_t* __restrict__ out_pmi, float* __restrict__ out_rate_c) {
-    codebook_rate_body<M, L, false>(ws, a, SbArgs{}, out_rate, out_pmi, out_rate_c);
+    codebook_rate_body<M, L, false, MMSE>(ws, a, SbArgs{}, out_rate, out_pmi, out_rate_c);
 }
 
-template <int M, int L>
+template <int M, int L, bool MMSE = false>
 __global__ __launch_bounds__(256) void k10_codebook_rate_sb(WsView ws, CbArgs a, SbArgs sb, float* __restrict__ out_rate,
                                                             int32_t* __restrict__ out_pmi, float* __restrict__ out_rate_c) {
-    codebook_rate_body<M, L, true>(ws, a, sb, out_rate, out_pmi, out_rate_c);
+    codebook_rate_body<M, L, true, MMSE>(ws, a, sb, out_rate, out_pmi, out_rate_c);
 }
 
 // LDS bytes of one wave for P path slots (0: the shape is not taken): the a_rx table, one chunk of whole codewords of the
@@ -304,14 +311,30 @@ struct CbLaunch {
     const WsView* ws;
     const CbArgs* a;
     const SbArgs* sb;        // NULL: the wideband kernel
+    bool mmse;               // DMX_FLAG_RX_LINEAR_MMSE
     float* out_rate;
     int32_t* out_pmi;
     float* out_rate_c;
 };
 
+// the linear MMSE receiver's instantiations, two layers or more
+template <int M, int L>
+int launch_cb_mmse(const CbLaunch& l) {
+    if (l.sb) {
+        return launch_dyn_lds(k10_codebook_rate_sb<M, L, true>, "k10_codebook_rate_sb", l.g, l.b, l.smem, WAVE_LDS_MAX, l.stream,
+                              *l.ws, *l.a, *l.sb, l.out_rate, l.out_pmi, l.out_rate_c);
+    }
+    return launch_dyn_lds(k10_codebook_rate<M, L, true>, "k10_codebook_rate", l.g, l.b, l.smem, WAVE_LDS_MAX, l.stream, *l.ws, *l.a,
+                          l.out_rate, l.out_pmi, l.out_rate_c);
+}
+
 template <int M, int L>
 int launch_cb_ml(const CbLaunch& l) {
     if constexpr (L <= M) {
+        // one layer is its own linear MMSE rate: the flag picks the instantiation below, the same bits
+        if constexpr (L > 1) {
+            if (l.mmse) return launch_cb_mmse<M, L>(l);
+        }
         if (l.sb) {
             return launch_dyn_lds(k10_codebook_rate_sb<M, L>, "k10_codebook_rate_sb", l.g, l.b, l.smem, WAVE_LDS_MAX, l.stream, *l.ws,
                                   *l.a, *l.sb, l.out_rate, l.out_pmi, l.out_rate_c);
@@ -377,6 +400,7 @@ static int launch_cb(const dmx_params& prm, const WsView& ws, int64_t user_begin
     l.smem = (size_t)wpb * lds;
     l.g = dim3((unsigned)((user_count + wpb - 1) / wpb)); l.b = dim3(64 * wpb);      // flat: one wave per user
     l.stream = stream; l.ws = &ws; l.a = &a; l.sb = sb;
+    l.mmse = (prm.flags & DMX_FLAG_RX_LINEAR_MMSE) != 0;
     l.out_rate = out_rate; l.out_pmi = out_pmi; l.out_rate_c = out_rate_c;
     switch (m_rx) {
         case 1: return launch_cb_m<1>(l, n_layers);

@@ -83,14 +83,15 @@ __device__ __forceinline__ void copy_rows_to_lds(float2* dst, const float2* src,
     }
 }
 
-// 4  pivots of I + G by elimination on the upper triangle, each clamped to >= 1: log2 det(I + G)
-template <int M>
+// 4  pivots of I + G by elimination on the upper triangle, each clamped to >= 1: log2 det(I + G).  LAST: log2 of the last
+//    pivot alone, the Schur complement of I + G at its last row and column
+template <int M, bool LAST = false>
 __device__ __forceinline__ float epilogue_logdet(float (&gr)[M * M], float (&gi)[M * M]) {
     float lg = 0.f;
 #pragma unroll
     for (int p = 0; p < M; ++p) {
         const float d = fmaxf(gr[p * M + p] + (p == 0 ? 1.f : 0.f), 1.f);
-        lg += log2f(d);
+        if (!LAST || p == M - 1) lg += log2f(d);
         const float inv = 1.f / d;
 #pragma unroll
         for (int i = p + 1; i < M; ++i) {
@@ -103,6 +104,31 @@ __device__ __forceinline__ float epilogue_logdet(float (&gr)[M * M], float (&gi)
             }
             if (p == 0) gr[i * M + i] += 1.f;                            // the identity, once per diagonal entry
         }
+    }
+    return lg;
+}
+
+// 4' the linear MMSE receiver on the same Gram (upper triangle, as epilogue_logdet takes it): sum over the layers t of
+//    log2(1 + sinr_t), 1 + sinr_t = 1 / [(I + G)^-1]_tt, which is the Schur complement of I + G at layer t: the last pivot
+//    of the elimination above run with the rows and columns t and M - 1 exchanged, on a register copy.  No difference of
+//    two logarithms, and with every pivot clamped to >= 1 no term below zero.
+template <int M>
+__device__ __forceinline__ float epilogue_mmse(const float (&gr)[M * M], const float (&gi)[M * M]) {
+    float lg = 0.f;
+#pragma unroll
+    for (int t = 0; t < M; ++t) {
+        float ar[M * M], ai[M * M];
+#pragma unroll
+        for (int p = 0; p < M; ++p) {
+#pragma unroll
+            for (int q = 0; q < M; ++q) {
+                const int a = p == t ? M - 1 : (p == M - 1 ? t : p), b = q == t ? M - 1 : (q == M - 1 ? t : q);
+                const bool up = a <= b;                                  // below the diagonal of G: the conjugate
+                ar[p * M + q] = q < p ? 0.f : (up ? gr[a * M + b] : gr[b * M + a]);
+                ai[p * M + q] = q <= p ? 0.f : (up ? gi[a * M + b] : -gi[b * M + a]);
+            }
+        }
+        lg += epilogue_logdet<M, true>(ar, ai);
     }
     return lg;
 }

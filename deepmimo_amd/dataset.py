@@ -700,7 +700,7 @@ class Dataset(DotDict):
         return self._deliver(eng.angle_delay(prep, int(n_taps), n_fft=n_fft, tx_codebook=cb))
 
     def compute_codebook_rate(self, params: Optional[ChannelGenParameters] = None, *, codebook="dft", snr_db=None,
-                              per_codeword: bool = False):
+                              per_codeword: bool = False, receiver: str = "joint"):
         """Rate of every codeword of a finite precoding codebook and the best codeword per user - the precoder-matrix
         indicator (PMI) of a CSI report and the rate behind its CQI - with no channel tensor written anywhere (extension):
 
@@ -717,10 +717,22 @@ class Dataset(DotDict):
         ``config('channel_output') == 'torch'``.  ``snr_db`` is required and keyword-only.  One PMI over the whole selection;
         ``compute_subband_pmi`` adds a PMI per subband and ``compute_csi_report`` the rank.  Frequency domain without
         ``rx_filter``, at most 32 used paths and 8 UE elements (include/deepmimo_amd.h has the rule): anything else raises
-        ValueError before any GPU work.  Not cached."""
-        return self._codebook_rate("compute_codebook_rate", params, codebook, snr_db, per_codeword)
+        ValueError before any GPU work.  Not cached.
 
-    def _codebook_rate(self, who: str, params, codebook, snr_db, per_codeword, subbands: bool = False, subband_size=None):
+        ``receiver``: ``"joint"`` (default) is the log2 det above, the rate of a maximum-likelihood receiver or of MMSE with
+        successive cancellation; ``"mmse"`` is what a UE with a linear MMSE receiver reports, the sum over the layers of
+        log2(1 + SINR_i) after equalisation, equal power per layer:
+
+            A = I + s * E.conj().T @ E
+            rate_c[u, c] = mean over k of -np.log2(np.linalg.inv(A).diagonal().real).sum()
+
+        It is at or below the joint rate, by more where the layers of a codeword leak into each other, so PMI (and the
+        rank of ``compute_csi_report``) can differ; with one layer the two are the same bits.  Anything else is a
+        ValueError."""
+        return self._codebook_rate("compute_codebook_rate", params, codebook, snr_db, per_codeword, receiver=receiver)
+
+    def _codebook_rate(self, who: str, params, codebook, snr_db, per_codeword, subbands: bool = False, subband_size=None,
+                       receiver="joint"):
         """`compute_codebook_rate`, or with `subbands` `compute_subband_pmi`: the same checks and preparation, the launch
         without or with a PMI per subband.  `who`: the public method, for the messages."""
         from .engine import check_codebook_rate_call, check_subband_size
@@ -729,15 +741,16 @@ class Dataset(DotDict):
             subband_size = check_subband_size(subband_size)
         params = self._call_params(params)
         cb = _precoding_codebook(who, params, codebook)
-        check_codebook_rate_call(params, self._loaded_paths(), int(cb.shape[0]), int(cb.shape[1]), snr_db)
+        check_codebook_rate_call(params, self._loaded_paths(), int(cb.shape[0]), int(cb.shape[1]), snr_db, receiver)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
         if subbands:
-            return self._deliver(eng.codebook_rate_subbands(prep, cb, snr_db, subband_size, per_codeword=bool(per_codeword)))
-        return self._deliver(eng.codebook_rate(prep, cb, snr_db, per_codeword=bool(per_codeword)))
+            return self._deliver(eng.codebook_rate_subbands(prep, cb, snr_db, subband_size, per_codeword=bool(per_codeword),
+                                                            receiver=receiver))
+        return self._deliver(eng.codebook_rate(prep, cb, snr_db, per_codeword=bool(per_codeword), receiver=receiver))
 
     def compute_subband_pmi(self, params: Optional[ChannelGenParameters] = None, *, codebook="dft", snr_db=None,
-                            subband_size=None, per_codeword: bool = False):
+                            subband_size=None, per_codeword: bool = False, receiver: str = "joint"):
         """``compute_codebook_rate`` with a PMI per subband from the same launch - the wideband and the subband part of a CSI
         report for the layer count of ``codebook`` (extension).  Subbands partition the selected subcarriers in their own
         order: subband s covers the positions s B .. min((s + 1) B, K) - 1 with B = ``subband_size`` (an integer >= 1; None:
@@ -752,11 +765,12 @@ class Dataset(DotDict):
         ``per_codeword`` also ``rate_c`` [n_ue, C] and ``rate_sb_c`` [n_ue, n_sb, C].  Column s equals what
         ``compute_codebook_rate`` returns for the selection ``sc[s B : (s + 1) B]`` bit for bit; with one subband all of it
         equals ``compute_codebook_rate``.  ``codebook``, ``snr_db``, the shapes taken and the return convention are those of
-        ``compute_codebook_rate``; anything else raises ValueError before any GPU work.  Not cached."""
-        return self._codebook_rate("compute_subband_pmi", params, codebook, snr_db, per_codeword, True, subband_size)
+        ``compute_codebook_rate``; anything else raises ValueError before any GPU work.  ``receiver``: as
+        ``compute_codebook_rate`` - with ``"mmse"`` every rate above is the linear MMSE receiver's.  Not cached."""
+        return self._codebook_rate("compute_subband_pmi", params, codebook, snr_db, per_codeword, True, subband_size, receiver)
 
     def compute_csi_report(self, params: Optional[ChannelGenParameters] = None, *, codebooks=None, snr_db=None,
-                           subband_size=None):
+                           subband_size=None, receiver: str = "joint"):
         """Rank indicator, wideband PMI and a PMI per subband of every user - the three parts of a CSI report - from one
         subband launch per candidate rank on the same preparation, no channel tensor written (extension).  ``codebooks``: a
         sequence of complex arrays [C_L, L, M_tx] (2-D: L = 1) with distinct layer counts L, one per candidate rank.
@@ -769,7 +783,9 @@ class Dataset(DotDict):
         [n_ue, n_ranks], the wideband rate of every candidate in ascending L.  ``subband_size``, ``snr_db`` (the total
         transmit power, split over the layers of each candidate) and the return convention as ``compute_subband_pmi``; a
         duplicate L, an empty ``codebooks`` or a shape not taken raises ValueError before any GPU work.  Mapping a rate to a
-        CQI index is a table lookup left to the caller.  Not cached."""
+        CQI index is a table lookup left to the caller.  ``receiver``: as ``compute_codebook_rate``, passed to the launch
+        of every rank; with ``"mmse"`` the rank is the L of the largest linear-MMSE wideband rate (the single-layer column
+        of ``rate_by_rank`` is the same bits for both receivers).  Not cached."""
         import torch
         from .engine import check_codebook_rate_call, check_subband_size
         self._required_snr("compute_csi_report", snr_db)
@@ -783,10 +799,10 @@ class Dataset(DotDict):
         if len(set(ranks)) != len(ranks):
             raise ValueError(f"compute_csi_report: the codebooks must have distinct layer counts, got L = {ranks}")
         for cb in cbs:
-            check_codebook_rate_call(params, self._loaded_paths(), int(cb.shape[0]), int(cb.shape[1]), snr_db)
+            check_codebook_rate_call(params, self._loaded_paths(), int(cb.shape[0]), int(cb.shape[1]), snr_db, receiver)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
-        per_rank = [eng.codebook_rate_subbands(prep, cb, snr_db, subband_size) for cb in cbs]
+        per_rank = [eng.codebook_rate_subbands(prep, cb, snr_db, subband_size, receiver=receiver) for cb in cbs]
         rate, pmi, rate_sb, pmi_sb = (t.clone() for t in per_rank[0])
         rank = torch.where(pmi >= 0, ranks[0], 0).to(torch.int32)
         for L, (r, p, rs, ps) in zip(ranks[1:], per_rank[1:]):                 # a strict >: the smallest L on ties

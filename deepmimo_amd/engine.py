@@ -185,6 +185,18 @@ def check_beam_metric(who: str, metric) -> bool:
     return metric == "power"
 
 
+RECEIVERS = ("joint", "mmse")
+
+
+def check_receiver(who: str, receiver) -> bool:
+    """The `receiver` of a codebook-rate call: False for "joint" (log2 det: maximum likelihood, or MMSE with successive
+    cancellation), True for "mmse" (the per-layer SINR of a linear MMSE receiver: DMX_FLAG_RX_LINEAR_MMSE); ValueError for
+    anything else."""
+    if not isinstance(receiver, str) or receiver not in RECEIVERS:
+        raise ValueError(f"{who}: receiver must be 'joint' or 'mmse', got {receiver!r}")
+    return receiver == "mmse"
+
+
 def select_serving_beam(dbm_by_cell, beam_by_cell):
     """Serving cell and beam of every user from the per-cell best-beam values (pure NumPy): `dbm_by_cell` float [n_ue, n_cells],
     NaN where the cell has no path to the user, `beam_by_cell` that beam's index.  Returns (serving int32 [n_ue]: the first
@@ -391,14 +403,16 @@ def check_angle_delay_call(params, n_paths_loaded: int, n_rows, n_fft, n_taps) -
     return n_fft
 
 
-def check_codebook_rate_call(params, n_paths_loaded: int, n_codewords, n_layers, snr_db) -> float:
-    """Everything `Dataset.compute_codebook_rate` can refuse without a GPU, as ValueError: an snr_db that is not finite, time
-    domain, rx_filter, `n_codewords` / `n_layers` that are no integers, and a shape dmx_codebook_rate_supported does not take
-    (the message is the library's and names the limit).  `params`: validated ChannelGenParameters.  Returns the linear
-    SNR."""
+def check_codebook_rate_call(params, n_paths_loaded: int, n_codewords, n_layers, snr_db, receiver="joint") -> float:
+    """Everything `Dataset.compute_codebook_rate` can refuse without a GPU, as ValueError: a `receiver` that is neither
+    "joint" nor "mmse", an snr_db that is not finite, time domain, rx_filter, `n_codewords` / `n_layers` that are no
+    integers, and a shape dmx_codebook_rate_supported does not take (the message is the library's and names the limit; the
+    query is asked with the receiver's flag).  `params`: validated ChannelGenParameters.  Returns the linear SNR."""
+    mmse = check_receiver("codebook rate", receiver)
     snr = snr_linear_from_db(snr_db)
     n_codewords, n_layers = _int_arg("codebook rate", "n_codewords", n_codewords), _int_arg("codebook rate", "n_layers", n_layers)
     p, _ = _query_params("codebook rate", params)
+    p.flags |= nat.FLAG_RX_LINEAR_MMSE if mmse else 0
     _ask("codebook rate", "dmx_codebook_rate_supported", C.byref(p), int(n_paths_loaded), n_codewords, n_layers)
     return snr
 
@@ -926,17 +940,29 @@ class ChannelEngine:
             nat.check(rc, query)
         return rc == 1
 
-    def _prep_supported(self, query: str, prep: PrepResult, *ints) -> bool:
-        return self._supported(query, C.byref(prep.params_struct), prep.n_paths_loaded, *map(int, ints))
+    def _prep_supported(self, query: str, prep: PrepResult, *ints, call_p=None) -> bool:
+        return self._supported(query, C.byref(prep.params_struct if call_p is None else call_p), prep.n_paths_loaded, *map(int, ints))
+
+    @staticmethod
+    def _receiver_params(prep: PrepResult, mmse: bool):
+        """The parameter block of a codebook-rate call: the preparation's, or for the linear MMSE receiver a copy of it with
+        DMX_FLAG_RX_LINEAR_MMSE (the pointers inside stay owned by the preparation) - an option of the call, as the power
+        metric is of `beam_power`."""
+        if not mmse:
+            return None
+        call_p = nat.DmxParams.from_buffer_copy(prep.params_struct)
+        call_p.flags |= nat.FLAG_RX_LINEAR_MMSE
+        return call_p
 
     @staticmethod
     def _users(n_ue: int, user_begin: int, user_count: Optional[int]) -> int:
         """`user_count` of a call: None means up to the last user."""
         return n_ue - user_begin if user_count is None else user_count
 
-    def _record_args(self, prep: PrepResult, user_begin: int, user_count: int):
-        """The leading arguments of every C call on a preparation's records."""
-        return (C.byref(prep.params_struct), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue, prep.n_paths_loaded,
+    def _record_args(self, prep: PrepResult, user_begin: int, user_count: int, call_p=None):
+        """The leading arguments of every C call on a preparation's records; `call_p`: the call's own copy of the parameter
+        block in place of the preparation's."""
+        return (C.byref(prep.params_struct if call_p is None else call_p), C.c_void_p(prep.workspace.data_ptr()), prep.n_ue, prep.n_paths_loaded,
                 int(user_begin), int(user_count))
 
     def covariance_supported(self, prep: PrepResult, side="tx") -> bool:
@@ -1152,12 +1178,14 @@ class ChannelEngine:
             nbytes = int(self.lib.dmx_beam_workspace_bytes(C.byref(p), cnt, prep.n_paths_loaded, n_rows))
             yield b, cnt, self._scratch(nbytes), nbytes
 
-    def codebook_rate_supported(self, prep: PrepResult, n_codewords: int, n_layers: int = 1) -> bool:
+    def codebook_rate_supported(self, prep: PrepResult, n_codewords: int, n_layers: int = 1, receiver: str = "joint") -> bool:
         """dmx_codebook_rate_supported for this preparation (host-only query; `codebook_rate` raises where it says no)."""
-        return self._prep_supported("dmx_codebook_rate_supported", prep, n_codewords, n_layers)
+        mmse = check_receiver("codebook_rate_supported", receiver)                   # before anything else: no engine is needed to be refused
+        call_p = self._receiver_params(prep, mmse)
+        return self._prep_supported("dmx_codebook_rate_supported", prep, n_codewords, n_layers, call_p=call_p)
 
     def codebook_rate(self, prep: PrepResult, codebook, snr_db, per_codeword: bool = False, user_begin: int = 0,
-                      user_count: Optional[int] = None):
+                      user_count: Optional[int] = None, receiver: str = "joint"):
         """dmx_codebook_rate: the rate of every codeword of a precoding codebook and the best one per user at `snr_db` (total
         transmit power over noise power per subcarrier, split equally over the layers), from the per-path records of `prep` -
         neither the channel tensor nor the beam-space tensor is written.  `codebook`: complex [C, L, M_tx], C codewords of
@@ -1165,43 +1193,54 @@ class ChannelEngine:
         rate_c[u, c] = mean over k of log2 det(I + snr / L E^H E).  Returns (rate float32 [user_count], pmi int32
         [user_count]) - pmi the first codeword of the largest rate, -1 and rate 0 for a user without a path - and with
         `per_codeword` also rate_c float32 [user_count, C], all in HBM.  Users go in blocks whose beam workspace stays within
-        CODEBOOK_WS_BYTES; a block equals the same rows of one launch bit for bit."""
+        CODEBOOK_WS_BYTES; a block equals the same rows of one launch bit for bit.  receiver "mmse": the per-layer SINR rate of
+        a linear MMSE receiver, rate_c[u, c] = mean over k of -sum_i log2 [(I + snr / L E^H E)^-1]_ii, at or below the joint
+        one - DMX_FLAG_RX_LINEAR_MMSE on a copy of the preparation's parameter block, for this call only; at L = 1 the same
+        bits as "joint"."""
+        mmse = check_receiver("codebook_rate", receiver)                   # before anything else: no engine is needed to be refused
+        call_p = self._receiver_params(prep, mmse)
         snr = snr_linear_from_db(snr_db)
         user_count = self._users(prep.n_ue, user_begin, user_count)
         cb, n_cw, n_layers = self._codebook_on_device(prep, codebook)
-        if not self.codebook_rate_supported(prep, n_cw, n_layers):   # DMX_ERR_SHAPE, before anything is allocated
+        if not self.codebook_rate_supported(prep, n_cw, n_layers, receiver):   # DMX_ERR_SHAPE, before anything is allocated
             nat.check(-2, "dmx_codebook_rate")
         rate = torch.empty((user_count,), dtype=torch.float32, device=self.device)
         pmi = torch.empty((user_count,), dtype=torch.int32, device=self.device)
         rate_c = torch.empty((user_count, n_cw), dtype=torch.float32, device=self.device) if per_codeword else None
         with torch.cuda.device(self.device):
             for b, cnt, bws, nbytes in self._codebook_user_blocks(prep, user_count, n_cw * n_layers):
-                rc = self.lib.dmx_codebook_rate(*self._record_args(prep, int(user_begin) + b, cnt), _ptr(cb), n_cw, n_layers,
+                rc = self.lib.dmx_codebook_rate(*self._record_args(prep, int(user_begin) + b, cnt, call_p), _ptr(cb), n_cw, n_layers,
                                                 _ptr(bws), nbytes, snr, _ptr(rate[b:]), _ptr(pmi[b:]),
                                                 _ptr(rate_c[b:]) if per_codeword else None, self._stream_ptr())
                 nat.check(rc, "dmx_codebook_rate")
         return (rate, pmi, rate_c) if per_codeword else (rate, pmi)
 
-    def codebook_rate_subbands_supported(self, prep: PrepResult, n_codewords: int, n_layers: int = 1, subband_size: int = 1) -> bool:
+    def codebook_rate_subbands_supported(self, prep: PrepResult, n_codewords: int, n_layers: int = 1, subband_size: int = 1,
+                                         receiver: str = "joint") -> bool:
         """dmx_codebook_rate_subbands_supported for this preparation (host-only query)."""
-        return self._prep_supported("dmx_codebook_rate_subbands_supported", prep, n_codewords, n_layers, subband_size)
+        mmse = check_receiver("codebook_rate_subbands_supported", receiver)                   # before anything else: no engine is needed to be refused
+        call_p = self._receiver_params(prep, mmse)
+        return self._prep_supported("dmx_codebook_rate_subbands_supported", prep, n_codewords, n_layers, subband_size, call_p=call_p)
 
     def codebook_rate_subbands(self, prep: PrepResult, codebook, snr_db, subband_size, per_codeword: bool = False,
-                               user_begin: int = 0, user_count: Optional[int] = None):
+                               user_begin: int = 0, user_count: Optional[int] = None, receiver: str = "joint"):
         """dmx_codebook_rate_subbands: `codebook_rate` with a PMI per subband in the same launch.  Subband s covers the
         selection positions s B .. min((s + 1) B, K) - 1, B = `subband_size` (an integer >= 1; None: one subband over the
         whole selection), n_sb = ceil(K / B).  Returns (rate [user_count], pmi [user_count], rate_sb [user_count, n_sb],
         pmi_sb [user_count, n_sb]) - float32 / int32 - and with `per_codeword` also rate_c [user_count, C] and rate_sb_c
         [user_count, n_sb, C], all in HBM.  Column s of the subband outputs equals `codebook_rate` on the selection
         sc[s B : (s + 1) B] bit for bit, and with one subband everything equals `codebook_rate`; with more the wideband
-        outputs add the subbands in order (another summation order than `codebook_rate`).  User blocks as `codebook_rate`."""
+        outputs add the subbands in order (another summation order than `codebook_rate`).  User blocks and `receiver` as
+        `codebook_rate`."""
+        mmse = check_receiver("codebook_rate_subbands", receiver)                   # before anything else: no engine is needed to be refused
+        call_p = self._receiver_params(prep, mmse)
         snr = snr_linear_from_db(snr_db)
         B = check_subband_size(subband_size)
         K = int(prep.params_struct.n_selected)
         B = max(1, K) if B is None else min(B, max(1, K))
         user_count = self._users(prep.n_ue, user_begin, user_count)
         cb, n_cw, n_layers = self._codebook_on_device(prep, codebook)
-        if not self.codebook_rate_subbands_supported(prep, n_cw, n_layers, B):   # DMX_ERR_SHAPE, before anything is allocated
+        if not self.codebook_rate_subbands_supported(prep, n_cw, n_layers, B, receiver):   # DMX_ERR_SHAPE, before anything is allocated
             nat.check(-2, "dmx_codebook_rate_subbands")
         n_sb = (K + B - 1) // B
         new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)   # noqa: E731
@@ -1212,7 +1251,7 @@ class ChannelEngine:
         ptr = lambda t, b: None if t is None else _ptr(t[b:])   # noqa: E731
         with torch.cuda.device(self.device):
             for b, cnt, bws, nbytes in self._codebook_user_blocks(prep, user_count, n_cw * n_layers):
-                rc = self.lib.dmx_codebook_rate_subbands(*self._record_args(prep, int(user_begin) + b, cnt), _ptr(cb), n_cw, n_layers,
+                rc = self.lib.dmx_codebook_rate_subbands(*self._record_args(prep, int(user_begin) + b, cnt, call_p), _ptr(cb), n_cw, n_layers,
                                                          _ptr(bws), nbytes, snr, B, ptr(rate_sb, b), ptr(pmi_sb, b),
                                                          ptr(rate_sb_c, b), ptr(rate, b), ptr(pmi, b), ptr(rate_c, b),
                                                          self._stream_ptr())

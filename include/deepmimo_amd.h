@@ -178,6 +178,34 @@ typedef struct dmx_params {
  * values are defined at dmx_beam_power below. */
 #define DMX_FLAG_BEAM_MEAN_POWER 64u
 
+/* Linear MMSE receiver in the codebook rate: dmx_codebook_rate and dmx_codebook_rate_subbands score a codeword by the
+ * post-equalisation SINR of each layer, what a UE that separates its layers with a linear MMSE receiver forms CQI, PMI and
+ * rank from, in place of log2 det (the rate of a joint receiver: maximum likelihood, or MMSE with successive cancellation).
+ * With E, L, snr_linear, W and the subband partition as defined at those two calls, s = snr_linear / L and
+ * A_ck = I_L + s E_ck^H E_ck:
+ *   sinr[u, c, i, k] = 1 / [A_ck^-1]_ii - 1                                 (linear MMSE, equal power per layer)
+ *   rate_c[u, c]     = 1 / K sum_k sum_i log2(1 + sinr[u, c, i, k]) = -1 / K sum_k sum_i log2 [A_ck^-1]_ii
+ * pmi, rate, rate_sb_c, pmi_sb and rate_sb follow from this rate_c exactly as without the flag: the first maximum,
+ * rate == rate_c[u, pmi] bit for bit, +0.0 / -1 / +0.0 for a user without a kept path, no output NaN, infinite or negative;
+ * launches repeat bit for bit, a user sub-range equals the rows of a whole launch, subband s equals the wideband call on
+ * selected_subcarriers[s B : (s + 1) B] and one subband equals the wideband call, all with the flag set on both sides.  The
+ * value is at or below the one without the flag (Hadamard's inequality on A^-1), up to rounding.  1 + sinr_i is the Schur
+ * complement of A_ck at layer i: the last pivot of the elimination of the rate without the flag, run once per layer with
+ * that layer ordered last, every pivot clamped to >= 1 as there.  At L = 1 the two receivers are the same number: the flag
+ * then runs the same kernel and every output is bit-equal to the call without it.
+ * The flag (value 256; 2, 8, 32 and 128 stay unknown bits) is, like the power option of the beam sweep above, an option of
+ * the call and not of the preparation: the workspace is that of dmx_path_prep WITHOUT the flag.  It combines with
+ * DMX_FLAG_ADAPTIVE_TERMS and with DMX_FLAG_NEAR_FIELD, and the shape limits are unchanged:
+ *   dmx_codebook_rate, dmx_codebook_rate_subbands, dmx_codebook_rate_supported, dmx_codebook_rate_subbands_supported
+ *                         take it.
+ *   every other entry point that takes a dmx_params block - dmx_path_prep, dmx_channels_fd, dmx_channels_fd_lpf,
+ *   dmx_channels_td, dmx_channels_fd_beams, dmx_beam_power, dmx_channels_fd_direct, dmx_fd_kernel_choice, every other
+ *   consumer, every link of dmx_cell_rate - and every other dmx_*_supported query: DMX_ERR_ARG, with
+ *   DMX_FLAG_RX_LINEAR_MMSE in dmx_last_error().
+ * Not covered: the per-layer SINRs as an output, zero-forcing and maximum-ratio receivers, unequal power per layer, the
+ * linear receiver in dmx_channel_rate and dmx_cell_rate, L > 4. */
+#define DMX_FLAG_RX_LINEAR_MMSE 256u
+
 /* Subcarrier index bound of the float32-phase kernels.  The matrix-core and folded kernels (variants 2-5, 8, 10-12, the
  * beam entry points) reduce the phase dn k / N in float32 as qh (k mod 4096) + ql k, whose error grows linearly with
  * |k|: they meet the error claim above (~2e-6 of a user's peak) only while every selected |k| is below this bound.  The
