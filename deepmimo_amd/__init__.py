@@ -19,11 +19,12 @@ from .dataset import Dataset, MacroDataset
 from .geometry import (dft_codebook, focus_codebook, fraunhofer_distance, near_field_phase, near_field_response, pattern_gain,
                        steering_vec, wideband_array_response)
 from .combiner import combine_rays, combiner_response, mu_partners, precode_rays, precoder_response
+from .delay import delay_spread, tap_delays
 from .core import generate, load
 from .generator_utils import get_idxs_with_limits, LinearPath
 
 __version__ = consts.VERSION
 
 __all__ = ["generate", "load", "Dataset", "MacroDataset", "ChannelGenParameters", "config", "steering_vec", "wideband_array_response", "near_field_response",
-           "near_field_phase", "focus_codebook", "fraunhofer_distance", "dft_codebook",
+           "near_field_phase", "focus_codebook", "fraunhofer_distance", "dft_codebook", "tap_delays", "delay_spread",
            "pattern_gain", "combiner_response", "combine_rays", "precoder_response", "precode_rays", "mu_partners", "get_idxs_with_limits", "LinearPath", "DotDict", "consts"]

@@ -17,6 +17,8 @@ FLAG_SPATIAL_WIDEBAND = 4                 # DMX_FLAG_SPATIAL_WIDEBAND: per-subca
 FLAG_NEAR_FIELD = 16                      # DMX_FLAG_NEAR_FIELD: spherical-wavefront array response per path
 FLAG_BEAM_MEAN_POWER = 64                 # DMX_FLAG_BEAM_MEAN_POWER: dmx_beam_power reports mean |F H|^2 (RSRP); that call only
 FLAG_RX_LINEAR_MMSE = 256                 # DMX_FLAG_RX_LINEAR_MMSE: per-layer SINR rate of a linear MMSE receiver; the codebook-rate calls only
+FLAG_ANGLE_DELAY_POWER = 1024             # DMX_FLAG_ANGLE_DELAY_POWER: dmx_channels_angle_delay writes sum_rx |X|^2, float32 [n, R, T]; that call only
+FLAG_ANGLE_DELAY_PROFILE = 4096           # DMX_FLAG_ANGLE_DELAY_PROFILE: beside the power flag, its row sum, float32 [n, T]
 
 EXPORTED_SYMBOLS = ("dmx_version", "dmx_last_error", "dmx_workspace_bytes", "dmx_decode_max_delay",
                     "dmx_path_prep", "dmx_channels_fd", "dmx_channels_td", "dmx_channels_fd_lpf",

@@ -36,7 +36,10 @@ static int check_patterns(const dmx_params* p) {
 // `takes`: which of DMX_FLAG_SPATIAL_WIDEBAND (dmx_path_prep and dmx_channels_fd only), DMX_FLAG_NEAR_FIELD (those two, the
 // consumers, dmx_beam_power and their dmx_*_supported queries), DMX_FLAG_BEAM_MEAN_POWER (dmx_beam_power only) and
 // DMX_FLAG_RX_LINEAR_MMSE (dmx_codebook_rate, dmx_codebook_rate_subbands and their two queries only) the caller takes; a flag
-// it does not take is refused here
+// it does not take is refused here.  DMX_FLAG_ANGLE_DELAY_POWER and DMX_FLAG_ANGLE_DELAY_PROFILE (dmx_channels_angle_delay and
+// its query only; the second only beside the first) are asked last, so that the refusals above keep their order.
+static constexpr uint32_t ANGLE_DELAY_OUTPUT_FLAGS = DMX_FLAG_ANGLE_DELAY_POWER | DMX_FLAG_ANGLE_DELAY_PROFILE;
+
 static int check_params(const dmx_params* p, uint32_t takes = 0) {
     if (!p) { set_error("params is NULL"); return DMX_ERR_ARG; }
     for (int i = 0; i < 2; ++i) {
@@ -48,7 +51,7 @@ static int check_params(const dmx_params* p, uint32_t takes = 0) {
     if (check_patterns(p)) return DMX_ERR_ARG;
     if (p->num_paths < 0) { set_error("num_paths must be >= 0"); return DMX_ERR_ARG; }
     if ((p->flags & ~(DMX_FLAG_ADAPTIVE_TERMS | DMX_FLAG_SPATIAL_WIDEBAND | DMX_FLAG_NEAR_FIELD | DMX_FLAG_BEAM_MEAN_POWER |
-                      DMX_FLAG_RX_LINEAR_MMSE)) != 0 ||
+                      DMX_FLAG_RX_LINEAR_MMSE | ANGLE_DELAY_OUTPUT_FLAGS)) != 0 ||
         p->reserved0 != 0) { set_error("unknown bits in dmx_params.flags / reserved0"); return DMX_ERR_ARG; }
     if ((p->flags & DMX_FLAG_BEAM_MEAN_POWER) && !(takes & DMX_FLAG_BEAM_MEAN_POWER)) {
         set_error("DMX_FLAG_BEAM_MEAN_POWER is an option of the dmx_beam_power call alone: no other entry point takes it, "
@@ -82,6 +85,19 @@ static int check_params(const dmx_params* p, uint32_t takes = 0) {
     if ((p->flags & DMX_FLAG_SPATIAL_WIDEBAND) && !(takes & DMX_FLAG_SPATIAL_WIDEBAND)) {
         set_error("DMX_FLAG_SPATIAL_WIDEBAND is taken by dmx_path_prep and dmx_channels_fd only: no other kernel forms a per-subcarrier "
                   "array response");
+        return DMX_ERR_ARG;
+    }
+    if ((p->flags & ANGLE_DELAY_OUTPUT_FLAGS) && !(takes & DMX_FLAG_ANGLE_DELAY_POWER)) {
+        set_error("%s is an option of the dmx_channels_angle_delay call and its dmx_angle_delay_supported query alone: no other "
+                  "entry point takes it, dmx_path_prep included",
+                  (p->flags & ANGLE_DELAY_OUTPUT_FLAGS) == ANGLE_DELAY_OUTPUT_FLAGS ? "DMX_FLAG_ANGLE_DELAY_POWER | DMX_FLAG_ANGLE_DELAY_PROFILE"
+                  : (p->flags & DMX_FLAG_ANGLE_DELAY_POWER)                       ? "DMX_FLAG_ANGLE_DELAY_POWER"
+                                                                                  : "DMX_FLAG_ANGLE_DELAY_PROFILE");
+        return DMX_ERR_ARG;
+    }
+    if ((p->flags & ANGLE_DELAY_OUTPUT_FLAGS) == DMX_FLAG_ANGLE_DELAY_PROFILE) {
+        set_error("DMX_FLAG_ANGLE_DELAY_PROFILE is valid only together with DMX_FLAG_ANGLE_DELAY_POWER: the profile is the row sum "
+                  "of the power matrix");
         return DMX_ERR_ARG;
     }
     if (p->freq_domain) {
@@ -314,6 +330,10 @@ int dmx_fd_kernel_choice(const dmx_params* prm, int32_t n_paths_loaded) {
     if (prm->flags & DMX_FLAG_BEAM_MEAN_POWER) { set_error("DMX_FLAG_BEAM_MEAN_POWER is an option of the dmx_beam_power call alone"); return DMX_ERR_ARG; }
     if (prm->flags & DMX_FLAG_RX_LINEAR_MMSE) {
         set_error("DMX_FLAG_RX_LINEAR_MMSE is an option of the dmx_codebook_rate and dmx_codebook_rate_subbands calls alone");
+        return DMX_ERR_ARG;
+    }
+    if (prm->flags & ANGLE_DELAY_OUTPUT_FLAGS) {
+        set_error("DMX_FLAG_ANGLE_DELAY_POWER and DMX_FLAG_ANGLE_DELAY_PROFILE are options of the dmx_channels_angle_delay call alone");
         return DMX_ERR_ARG;
     }
     if (prm->flags & (DMX_FLAG_SPATIAL_WIDEBAND | DMX_FLAG_NEAR_FIELD)) return 1;
@@ -639,8 +659,11 @@ static int angle_delay_shape(const dmx_params* prm, int32_t n_paths_loaded, int3
     return 1;
 }
 
+// the angle-delay call and its query take the two output options beside the near field
+static constexpr uint32_t ANGLE_DELAY_TAKES = DMX_FLAG_NEAR_FIELD | ANGLE_DELAY_OUTPUT_FLAGS;
+
 int dmx_angle_delay_supported(const dmx_params* prm, int32_t n_paths_loaded, int32_t n_rows, int32_t n_fft, int32_t n_taps) {
-    return supported(prm, [&] { return angle_delay_shape(prm, n_paths_loaded, n_rows, n_fft, n_taps); });
+    return supported(prm, [&] { return angle_delay_shape(prm, n_paths_loaded, n_rows, n_fft, n_taps); }, ANGLE_DELAY_TAKES);
 }
 
 int dmx_channels_angle_delay(const dmx_params* prm, const void* workspace, int64_t n_ue, int32_t n_paths_loaded,
@@ -648,7 +671,11 @@ int dmx_channels_angle_delay(const dmx_params* prm, const void* workspace, int64
                              void* beam_workspace, size_t beam_workspace_bytes_, int32_t n_fft, int32_t n_taps, void* out_c64,
                              void* stream) {
     int rc = consumer_args("dmx_channels_angle_delay", prm, workspace, n_ue, user_begin, user_count,
-                           !workspace || !out_c64 ? WS_OUT_NULL : nullptr, (uintptr_t)out_c64 & 7u ? "out must be 8-byte aligned" : nullptr);
+                           !workspace || !out_c64 ? WS_OUT_NULL : nullptr,
+                           prm && (prm->flags & DMX_FLAG_ANGLE_DELAY_POWER)                          // float32 out
+                               ? ((uintptr_t)out_c64 & 3u ? "out must be 4-byte aligned" : nullptr)
+                               : ((uintptr_t)out_c64 & 7u ? "out must be 8-byte aligned" : nullptr),
+                           ANGLE_DELAY_TAKES);
     if (rc) return rc;
     if (prm->sc_stride < 1) {
         set_error("dmx_channels_angle_delay needs a uniformly spaced selection promised by sc_stride > 0"); return DMX_ERR_ARG;

@@ -54,7 +54,22 @@ __device__ __forceinline__ cd mul_conj(cd a, cd b) {                         // 
     return cd{__builtin_fma(a.x, b.x, a.y * b.y), __builtin_fma(a.y, b.x, -(a.x * b.y))};
 }
 
+// OUT: what phase 3 stores.  0: X, complex [M][R][T] per user.  1: the angle-delay power P[r][t] = sum_rx |X[rx][r][t]|^2, one
+// float per (row, tap) - a lane holds all M entries of its (row, tap) in registers after rows_pair<M>, so the sum is
+// |h[0]|^2 + ... + |h[M-1]|^2 in ascending rx, each term fmaf(im, im, re re).  2: the delay profile p[t] = sum_r P[r][t]: a lane
+// adds its rows in the order it meets them (r0 ascending, base ascending, row ra before rb), the S row slices of a tap are then
+// added in ascending slice order by lane shuffle and slice 0 stores.  `out` is float [R][T] / [T] per user for 1 / 2.
 template <int M>
+__device__ __forceinline__ float row_power(const float2 (&h)[M]) {
+    float p = fmaf(h[0].y, h[0].y, h[0].x * h[0].x);
+#pragma unroll
+    for (int i = 1; i < M; ++i) p += fmaf(h[i].y, h[i].y, h[i].x * h[i].x);
+    return p;
+}
+
+// The float pointers of OUT 1 and 2 are formed inside their `if constexpr` branches: a pointer formed beside `o`, dead in OUT 0,
+// changed the register allocation of the OUT 0 instantiations, which are to stay the instruction streams they were.
+template <int M, int OUT>
 __global__ __launch_bounds__(256) void k9_angle_delay(WsView ws, AdArgs a, float2* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
@@ -70,7 +85,13 @@ __global__ __launch_bounds__(256) void k9_angle_delay(WsView ws, AdArgs a, float
     float2* o = out + (size_t)ul * M * R * T;                                        // [M][R][T]
     const int n = kept_paths(ws, u);
     if (n <= 0) {                                                            // no kept path: +0.0 everywhere
-        for (size_t i = lane; i < (size_t)M * R * T; i += 64) o[i] = make_float2(0.f, 0.f);
+        if constexpr (OUT == 0) {
+            for (size_t i = lane; i < (size_t)M * R * T; i += 64) o[i] = make_float2(0.f, 0.f);
+        } else {
+            const size_t per_user = (size_t)(OUT == 2 ? 1 : R) * T;         // [R][T], or [T]
+            float* of = reinterpret_cast<float*>(out) + (size_t)ul * per_user;
+            for (size_t i = lane; i < per_user; i += 64) of[i] = 0.f;
+        }
         return;
     }
     const WsRecords rec{ws, (size_t)u * ws.P, a.nf};
@@ -125,6 +146,7 @@ __global__ __launch_bounds__(256) void k9_angle_delay(WsView ws, AdArgs a, float
             }
         }
 
+        float acc = 0.f;                  // OUT 2: this lane's rows of tap t0 + tl; unused and removed in OUT 0 and 1
         for (int r0 = 0; r0 < R; r0 += rc) {
             const int nr = R - r0 < rc ? R - r0 : rc;
             // 2' rows r0 .. r0 + nr of the row table
@@ -146,14 +168,28 @@ __global__ __launch_bounds__(256) void k9_angle_delay(WsView ws, AdArgs a, float
                     const float2* b1 = ab + (size_t)(vb ? rb : 0) * ld;
                     float2 h0[M], h1[M];
                     rows_pair<M>(as, b0, b1, wk, ld, tc, n, h0, h1);
+                    if constexpr (OUT == 0) {
 #pragma unroll
-                    for (int i = 0; i < M; ++i) {
-                        float2* row = o + ((size_t)i * R + r0) * T + t0 + tl;
-                        if (va) row[(size_t)ra * T] = h0[i];
-                        if (vb) row[(size_t)rb * T] = h1[i];
+                        for (int i = 0; i < M; ++i) {
+                            float2* row = o + ((size_t)i * R + r0) * T + t0 + tl;
+                            if (va) row[(size_t)ra * T] = h0[i];
+                            if (vb) row[(size_t)rb * T] = h1[i];
+                        }
+                    } else if constexpr (OUT == 1) {
+                        float* row = reinterpret_cast<float*>(out) + ((size_t)ul * R + r0) * T + t0 + tl;
+                        if (va) row[(size_t)ra * T] = row_power<M>(h0);
+                        if (vb) row[(size_t)rb * T] = row_power<M>(h1);
+                    } else {
+                        if (va) acc += row_power<M>(h0);
+                        if (vb) acc += row_power<M>(h1);
                     }
                 }
             }
+        }
+        if constexpr (OUT == 2) {                                            // every lane shuffles: a source lane shares tl
+            float sum = 0.f;
+            for (int s = 0; s < S; ++s) sum += __shfl(acc, (s << a.log2_tcp) + tl, 64);
+            if (active && sl == 0) reinterpret_cast<float*>(out)[(size_t)ul * T + t0 + tl] = sum;
         }
     }
 }
@@ -175,12 +211,18 @@ int angle_delay_waves_per_block(const dmx_params& prm, int P, int n_rows, int n_
 }
 
 template <int M>
-static int launch_ad_m(const dim3 g, const dim3 b, size_t smem, hipStream_t stream, const WsView& ws, const AdArgs& a, float2* out) {
-    return launch_dyn_lds(k9_angle_delay<M>, "k9_angle_delay", g, b, smem, WAVE_LDS_MAX, stream, ws, a, out);
+static int launch_ad_m(int output, const dim3 g, const dim3 b, size_t smem, hipStream_t stream, const WsView& ws, const AdArgs& a,
+                       float2* out) {
+    switch (output) {
+        case 0: return launch_dyn_lds(k9_angle_delay<M, 0>, "k9_angle_delay", g, b, smem, WAVE_LDS_MAX, stream, ws, a, out);
+        case 1: return launch_dyn_lds(k9_angle_delay<M, 1>, "k9_angle_delay", g, b, smem, WAVE_LDS_MAX, stream, ws, a, out);
+        default: return launch_dyn_lds(k9_angle_delay<M, 2>, "k9_angle_delay", g, b, smem, WAVE_LDS_MAX, stream, ws, a, out);
+    }
 }
 
-// out [user_count, M_rx, n_rows, n_taps]; with a codebook the projection runs first into beam_ws (beam_workspace_bytes), as
-// in launch_beam_power
+// out complex [user_count, M_rx, n_rows, n_taps], or by the call's flags float [user_count, n_rows, n_taps]
+// (DMX_FLAG_ANGLE_DELAY_POWER) or float [user_count, n_taps] (with DMX_FLAG_ANGLE_DELAY_PROFILE beside it); with a codebook the
+// projection runs first into beam_ws (beam_workspace_bytes), as in launch_beam_power
 int launch_angle_delay(const dmx_params& prm, const WsView& ws, int64_t user_begin, int64_t user_count, const float2* codebook,
                        int n_rows, void* beam_ws, int n_fft, int n_taps, float2* out, hipStream_t stream) {
     if (user_count == 0) return DMX_OK;
@@ -210,15 +252,16 @@ int launch_angle_delay(const dmx_params& prm, const WsView& ws, int64_t user_beg
     const int m_rx = prm.ue_shape[0] * prm.ue_shape[1];
     const size_t smem = (size_t)wpb * angle_delay_lds_bytes(prm, ws.P, n_rows, n_taps);
     const dim3 g((unsigned)((user_count + wpb - 1) / wpb)), b(64 * wpb);    // flat: one wave per user
+    const int output = !(prm.flags & DMX_FLAG_ANGLE_DELAY_POWER) ? 0 : (prm.flags & DMX_FLAG_ANGLE_DELAY_PROFILE) ? 2 : 1;
     switch (m_rx) {
-        case 1: return launch_ad_m<1>(g, b, smem, stream, ws, a, out);
-        case 2: return launch_ad_m<2>(g, b, smem, stream, ws, a, out);
-        case 3: return launch_ad_m<3>(g, b, smem, stream, ws, a, out);
-        case 4: return launch_ad_m<4>(g, b, smem, stream, ws, a, out);
-        case 5: return launch_ad_m<5>(g, b, smem, stream, ws, a, out);
-        case 6: return launch_ad_m<6>(g, b, smem, stream, ws, a, out);
-        case 7: return launch_ad_m<7>(g, b, smem, stream, ws, a, out);
-        default: return launch_ad_m<8>(g, b, smem, stream, ws, a, out);
+        case 1: return launch_ad_m<1>(output, g, b, smem, stream, ws, a, out);
+        case 2: return launch_ad_m<2>(output, g, b, smem, stream, ws, a, out);
+        case 3: return launch_ad_m<3>(output, g, b, smem, stream, ws, a, out);
+        case 4: return launch_ad_m<4>(output, g, b, smem, stream, ws, a, out);
+        case 5: return launch_ad_m<5>(output, g, b, smem, stream, ws, a, out);
+        case 6: return launch_ad_m<6>(output, g, b, smem, stream, ws, a, out);
+        case 7: return launch_ad_m<7>(output, g, b, smem, stream, ws, a, out);
+        default: return launch_ad_m<8>(output, g, b, smem, stream, ws, a, out);
     }
 }
 

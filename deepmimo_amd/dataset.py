@@ -659,9 +659,11 @@ class Dataset(DotDict):
         eng, prep = self._run_prep(want_side="light")
         return self._deliver(eng.precoders(prep, snr_db, n_layers=int(n_layers), rx=bool(combiners)))
 
-    def compute_angle_delay(self, params: Optional[ChannelGenParameters] = None, *, n_taps=None, n_fft=None, codebook="dft"):
+    def compute_angle_delay(self, params: Optional[ChannelGenParameters] = None, *, n_taps=None, n_fft=None, codebook="dft",
+                            output: str = "complex"):
         """Angle-delay representation of every user's channel, with no channel tensor written anywhere (extension) - what
-        CSI-feedback, fingerprinting and positioning models train on:
+        CSI-feedback models train on (``output="complex"``); fingerprinting, localisation and channel-charting models train on
+        its power matrix (``"power"``) and on the delay profile (``"profile"``):
 
             Y = codebook @ H                                         # [n_ue, M_rx, R, K], H the frequency-domain channel
             X = np.fft.ifft(Y, n=n_fft, axis=-1)[..., :n_taps]       # the first n_taps delay taps
@@ -672,9 +674,23 @@ class Dataset(DotDict):
         NumPy array by default, the HBM-resident torch tensor when ``config('channel_output') == 'torch'``.  Users without
         a path get 0.  Frequency domain without ``rx_filter``, a uniformly spaced selection, at most 32 used paths and 8 UE
         elements, K <= n_fft <= 2**20, 1 <= n_taps <= n_fft (include/deepmimo_amd.h has the rule): anything else raises
-        ValueError before any GPU work.  Not cached."""
-        from .engine import check_angle_delay_call
+        ValueError before any GPU work.  Not cached.
+
+        ``output``: ``"complex"`` (default) is X above.  ``"power"`` is the angle-delay channel power matrix and
+        ``"profile"`` its row sum, the power-delay profile,
+
+            P = (np.abs(X) ** 2).sum(axis=1)                         # float32 [n_ue, R, n_taps]
+            p = P.sum(axis=1)                                        # float32 [n_ue, n_taps]
+
+        raw sums (divide by M_rx, or M_rx * R, for means) formed in the kernel's registers: X is written nowhere, so the
+        result is 2 M_rx, or 2 M_rx R, times smaller than X and the host-copy guard counts that size.  With an orthonormal
+        codebook (``"dft"``) the profile equals the antenna-domain one (``codebook=None``) by Parseval.  ``dm.tap_delays``
+        gives the delay of every tap and ``dm.delay_spread`` the mean excess delay and RMS delay spread of a profile.  On a
+        view of ``with_rx_combiner`` M_rx = 1, so ``"power"`` is ``|w_q H|^2`` per UE beam q, in the angle-delay domain.
+        Anything else is a ValueError."""
+        from .engine import check_angle_delay_call, check_angle_delay_output
         from .geometry import dft_codebook
+        check_angle_delay_output("compute_angle_delay", output)                # before the engine is needed
         if n_taps is None:
             raise ValueError("compute_angle_delay: n_taps (keyword) is required")
         params = self._call_params(params)
@@ -691,13 +707,14 @@ class Dataset(DotDict):
             if len(cb.shape) != 2 or cb.shape[1] != m_tx or cb.shape[0] < 1:
                 raise ValueError(f"compute_angle_delay: codebook must be [R, {m_tx}], got {tuple(cb.shape)}")
         n_rows = m_tx if cb is None else int(cb.shape[0])
-        n_fft = check_angle_delay_call(params, self._loaded_paths(), n_rows, n_fft, n_taps)
+        n_fft = check_angle_delay_call(params, self._loaded_paths(), n_rows, n_fft, n_taps, output)
         if config.get("channel_output", "numpy") != "torch":                   # before any GPU work is spent on it
             m_rx = int(np.prod(params[c.PARAMSET_ANT_UE][c.PARAMSET_ANT_SHAPE]))
-            self._guard_host_copy(8 * int(self.n_ue) * m_rx * n_rows * int(n_taps))
+            per_user = {"complex": 8 * m_rx * n_rows, "power": 4 * n_rows, "profile": 4}[output] * int(n_taps)
+            self._guard_host_copy(int(self.n_ue) * per_user)
         np.random.seed(1001)
         eng, prep = self._run_prep(want_side="light")
-        return self._deliver(eng.angle_delay(prep, int(n_taps), n_fft=n_fft, tx_codebook=cb))
+        return self._deliver(eng.angle_delay(prep, int(n_taps), n_fft=n_fft, tx_codebook=cb, output=output))
 
     def compute_codebook_rate(self, params: Optional[ChannelGenParameters] = None, *, codebook="dft", snr_db=None,
                               per_codeword: bool = False, receiver: str = "joint"):
@@ -1271,7 +1288,9 @@ class Dataset(DotDict):
     def with_rx_combiner(self, codebook="dft", params: Optional[ChannelGenParameters] = None) -> "Dataset":
         """The dataset behind a UE combining codebook W [Q, M_rx] as a plain Dataset of Q * n_ue single-antenna users,
         combiner-major: row q * n_ue + u is user u behind row q, the UE beam q (extension).  Every ``compute_*`` works on
-        it unchanged and gives what it would give for ``W[q] @ H[u]``, with no [n_ue, M_rx, ...] tensor written.
+        it unchanged and gives what it would give for ``W[q] @ H[u]``, with no [n_ue, M_rx, ...] tensor written.  On the
+        view M_rx = 1, so ``compute_angle_delay(..., output="power")`` is ``|W[q] @ H[u]|**2`` per UE beam in the angle-delay
+        domain: its sum over the receive elements has one term.
 
         A combiner row multiplies the complex gain of each path and nothing else:
 

@@ -15,6 +15,7 @@ include/deepmimo_amd.h and calls the C-ABI:
     dmx_channel_precoders -> float32 [N, K, m], complex64 [N, K, L, M_tx], [N, K, L, M_rx]  (eigenbeams, no channel tensor)
     dmx_cell_rate        -> float32 [N] (and [N, K], int32 [N], float32 [N, B])  (rate under inter-cell interference, B links)
     dmx_channels_angle_delay -> complex64 [N, M_rx, R, n_taps]  (codebook x inverse DFT, first delay taps, no channel tensor)
+                                float32 [N, R, n_taps] / [N, n_taps] with output="power" / "profile" (sum over rx of |.|^2, and over rows)
     dmx_codebook_rate   -> float32 [N], int32 [N], float32 [N, C]  (rate and PMI over a precoding codebook, no channel tensor)
     dmx_codebook_rate_subbands -> the same and float32 [N, n_sb], int32 [N, n_sb], float32 [N, n_sb, C]  (a PMI per subband)
 
@@ -195,6 +196,19 @@ def check_receiver(who: str, receiver) -> bool:
     if not isinstance(receiver, str) or receiver not in RECEIVERS:
         raise ValueError(f"{who}: receiver must be 'joint' or 'mmse', got {receiver!r}")
     return receiver == "mmse"
+
+
+ANGLE_DELAY_OUTPUTS = ("complex", "power", "profile")
+
+
+def check_angle_delay_output(who: str, output) -> int:
+    """The `output` of an angle-delay call as the flag bits of the call: 0 for "complex" (X itself), DMX_FLAG_ANGLE_DELAY_POWER
+    for "power" (sum over rx of |X|^2), that | DMX_FLAG_ANGLE_DELAY_PROFILE for "profile" (summed over the rows as well);
+    ValueError for anything else."""
+    if not isinstance(output, str) or output not in ANGLE_DELAY_OUTPUTS:
+        raise ValueError(f"{who}: output must be 'complex', 'power' or 'profile', got {output!r}")
+    return {"complex": 0, "power": nat.FLAG_ANGLE_DELAY_POWER,
+            "profile": nat.FLAG_ANGLE_DELAY_POWER | nat.FLAG_ANGLE_DELAY_PROFILE}[output]
 
 
 def select_serving_beam(dbm_by_cell, beam_by_cell):
@@ -388,12 +402,15 @@ def check_precoder_call(params, n_paths_loaded: int, snr_db, n_layers) -> float:
     return snr
 
 
-def check_angle_delay_call(params, n_paths_loaded: int, n_rows, n_fft, n_taps) -> int:
-    """Everything `Dataset.compute_angle_delay` can refuse without a GPU, as ValueError: time domain, rx_filter, a selection
-    that is not uniformly spaced, `n_rows` / `n_fft` / `n_taps` that are no integers, and a shape dmx_angle_delay_supported
-    does not take (the message is the library's and names the limit).  `params`: validated ChannelGenParameters;
-    `n_fft` None = the number of selected subcarriers.  Returns n_fft."""
+def check_angle_delay_call(params, n_paths_loaded: int, n_rows, n_fft, n_taps, output="complex") -> int:
+    """Everything `Dataset.compute_angle_delay` can refuse without a GPU, as ValueError: an `output` that is none of
+    "complex", "power", "profile", time domain, rx_filter, a selection that is not uniformly spaced, `n_rows` / `n_fft` /
+    `n_taps` that are no integers, and a shape dmx_angle_delay_supported does not take (the message is the library's and
+    names the limit; the query is asked with the output's flags).  `params`: validated ChannelGenParameters; `n_fft` None =
+    the number of selected subcarriers.  Returns n_fft."""
+    out_flags = check_angle_delay_output("angle-delay", output)
     p, sel = _query_params("angle-delay", params, promise_stride=True)
+    p.flags |= out_flags
     if p.sc_stride <= 0:
         raise ValueError("angle-delay: ofdm.selected_subcarriers must be uniformly spaced, first + k * stride with 0 < stride < 2^20 "
                          "and |first| < 2^30 (the delay transform is an inverse DFT over the selection)")
@@ -1126,30 +1143,52 @@ class ChannelEngine:
         res = (r,) + ((rk,) if per_subcarrier else ()) + ((sv, ls) if details else ())
         return res[0] if len(res) == 1 else res
 
-    def angle_delay_supported(self, prep: PrepResult, n_rows: int, n_fft: int, n_taps: int) -> bool:
+    @staticmethod
+    def _angle_delay_params(prep: PrepResult, out_flags: int):
+        """The parameter block of an angle-delay call: the preparation's, or for the power and profile outputs a copy of it
+        with the output's flags (the pointers inside stay owned by the preparation) - options of the call, as
+        `_receiver_params`."""
+        if not out_flags:
+            return None
+        call_p = nat.DmxParams.from_buffer_copy(prep.params_struct)
+        call_p.flags |= out_flags
+        return call_p
+
+    def angle_delay_supported(self, prep: PrepResult, n_rows: int, n_fft: int, n_taps: int, output: str = "complex") -> bool:
         """dmx_angle_delay_supported for this preparation (host-only query; `angle_delay` raises where it says no)."""
-        return self._prep_supported("dmx_angle_delay_supported", prep, n_rows, n_fft, n_taps)
+        out_flags = check_angle_delay_output("angle_delay_supported", output)         # before anything else: no engine is needed to be refused
+        call_p = self._angle_delay_params(prep, out_flags)
+        return self._prep_supported("dmx_angle_delay_supported", prep, n_rows, n_fft, n_taps, call_p=call_p)
 
     def angle_delay(self, prep: PrepResult, n_taps: int, n_fft: Optional[int] = None, tx_codebook=None, user_begin: int = 0,
-                    user_count: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """dmx_channels_angle_delay: the angle-delay representation ifft(F @ H, n=n_fft, axis=-1)[..., :n_taps] of the
+                    user_count: Optional[int] = None, out: Optional[torch.Tensor] = None, output: str = "complex") -> torch.Tensor:
+        """dmx_channels_angle_delay: the angle-delay representation X = ifft(F @ H, n=n_fft, axis=-1)[..., :n_taps] of the
         frequency-domain channel, complex64 [user_count, M_rx, R, n_taps] in HBM, from the per-path records of `prep` - the
         channel tensor is not written.  tx_codebook: complex [R, M_tx], or None for the antenna domain (R = M_tx, the
         delay-domain channel of every antenna pair).  n_fft: None = the number of selected subcarriers.  The selection has
-        to be uniformly spaced."""
+        to be uniformly spaced.  output "power": the angle-delay power matrix (abs(X) ** 2).sum(1), float32 [user_count, R,
+        n_taps]; "profile": its row sum, the power-delay profile, float32 [user_count, n_taps] - raw sums formed in the
+        kernel's registers, X is not written; the flags go on a copy of the preparation's parameter block, for this call
+        only.  `out` has the shape and dtype of the chosen output."""
+        out_flags = check_angle_delay_output("angle_delay", output)                   # before anything else: no engine is needed to be refused
+        call_p = self._angle_delay_params(prep, out_flags)
         p = prep.params_struct
         user_count = self._users(prep.n_ue, user_begin, user_count)
         m_rx, m_tx = p.ue_shape[0] * p.ue_shape[1], p.bs_shape[0] * p.bs_shape[1]
         cb = None if tx_codebook is None else self._codebook(tx_codebook, m_tx, min_beams=1)
         rows = m_tx if cb is None else int(cb.shape[0])
         n_fft = int(p.n_selected) if n_fft is None else int(n_fft)
-        out = self._out(out, (user_count, m_rx, rows, max(int(n_taps), 0)))
+        taps = max(int(n_taps), 0)
+        if output == "complex":
+            out = self._out(out, (user_count, m_rx, rows, taps))
+        else:
+            out = self._outs(out, [((user_count, rows, taps) if output == "power" else (user_count, taps), torch.float32)])[0]
         with torch.cuda.device(self.device):
             nbytes, bws = 0, None
             if cb is not None and user_count > 0:
                 nbytes = int(self.lib.dmx_beam_workspace_bytes(C.byref(p), user_count, prep.n_paths_loaded, rows))
                 bws = self._scratch(nbytes)
-            rc = self.lib.dmx_channels_angle_delay(*self._record_args(prep, user_begin, user_count), _ptr(cb), rows, _ptr(bws),
+            rc = self.lib.dmx_channels_angle_delay(*self._record_args(prep, user_begin, user_count, call_p), _ptr(cb), rows, _ptr(bws),
                                                    nbytes, n_fft, int(n_taps), _ptr(out), self._stream_ptr())
         nat.check(rc, "dmx_channels_angle_delay")
         return out

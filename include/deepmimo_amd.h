@@ -206,6 +206,37 @@ typedef struct dmx_params {
  * linear receiver in dmx_channel_rate and dmx_cell_rate, L > 4. */
 #define DMX_FLAG_RX_LINEAR_MMSE 256u
 
+/* Angle-delay power matrix and delay profile: dmx_channels_angle_delay writes, in place of the complex tensor X it defines
+ * below, the two reduced quantities that fingerprinting, localisation and channel-charting models train on.  With X, F,
+ * n_rows, n_fft and n_taps as at that call:
+ *   P[u, r, t] = sum_{rx < M_rx} |X[u, rx, r, t]|^2      float32 [user_count, n_rows, n_taps]     DMX_FLAG_ANGLE_DELAY_POWER
+ *   p[u, t]    = sum_{r < n_rows} P[u, r, t]             float32 [user_count, n_taps]             ... | DMX_FLAG_ANGLE_DELAY_PROFILE
+ * raw sums, no division: the angle-delay channel power matrix (ADCPM) and its row sum, the power-delay profile.  With rows
+ * that are orthonormal (a unitary DFT codebook) p equals the profile of the antenna domain (Parseval).  The output goes
+ * through the unchanged out_c64 parameter, C-contiguous, taps fastest, 4-byte aligned; X is not written
+ * anywhere, and nothing beyond the smaller extent is touched.  |X|^2 of one (rx, r, t) is fmaf(im, im, re re) of the fp32
+ * value the complex call would store; P adds them in ascending rx, p adds P over the rows in an order fixed by (n_rows,
+ * n_taps) alone, all in fp32 without atomics: launches repeat bit for bit, a user sub-range equals the same rows of a whole
+ * launch, P is within (M_rx + 2) 2^-24 P + FLT_MIN of the float64 sum over the complex call's own output and p within
+ * (n_rows + 1) 2^-24 p + FLT_MIN of the float64 row sum of P (to first order M_rx + 1 and n_rows - 1 roundings; the rest covers
+ * the terms of second order and the float32 store).  A user without kept paths gets +0.0 in every element; no output is NaN, infinite or
+ * negative; a value below FLT_MIN may come out as 0.
+ * The flags (values 1024 and 4096; 2, 8, 32, 128, 512 and 2048 stay unknown bits) are options of the call and not of the
+ * preparation, like the options of the beam sweep and of the codebook rate above: the workspace is that of dmx_path_prep
+ * WITHOUT them.  DMX_FLAG_ANGLE_DELAY_PROFILE is valid only together with DMX_FLAG_ANGLE_DELAY_POWER; alone it is DMX_ERR_ARG,
+ * with both names in dmx_last_error().  They combine with DMX_FLAG_ADAPTIVE_TERMS and with DMX_FLAG_NEAR_FIELD, and the shape
+ * limits are unchanged:
+ *   dmx_channels_angle_delay, dmx_angle_delay_supported
+ *                         take them.
+ *   every other entry point that takes a dmx_params block - dmx_path_prep, dmx_channels_fd, dmx_channels_fd_lpf,
+ *   dmx_channels_td, dmx_channels_fd_beams, dmx_beam_power, dmx_channels_fd_direct, dmx_fd_kernel_choice, every other
+ *   consumer, every link of dmx_cell_rate - and every other dmx_*_supported query: DMX_ERR_ARG, with the flag's name in
+ *   dmx_last_error().
+ * Not covered: the power per receive element or its maximum over elements, a Doppler axis, the delay spread inside the
+ * kernel (it is array code on p), the rx_filter and time-domain forms, the spatial-wideband flag. */
+#define DMX_FLAG_ANGLE_DELAY_POWER 1024u
+#define DMX_FLAG_ANGLE_DELAY_PROFILE 4096u
+
 /* Subcarrier index bound of the float32-phase kernels.  The matrix-core and folded kernels (variants 2-5, 8, 10-12, the
  * beam entry points) reduce the phase dn k / N in float32 as qh (k mod 4096) + ql k, whose error grows linearly with
  * |k|: they meet the error claim above (~2e-6 of a user's peak) only while every selected |k| is below this bound.  The
@@ -563,7 +594,10 @@ int dmx_cell_rate(const dmx_link* links, int32_t n_links, int64_t n_ue, int64_t 
  * prm->flags changes the order of a user's records and so the summation order only; the workspace of either arithmetic mode
  * is accepted.  With a codebook the projection runs first into `beam_workspace` (dmx_beam_workspace_bytes(prm, user_count,
  * n_paths_loaded, n_rows) bytes, 256-byte aligned, device; unused and may be NULL without a codebook); a BS panel the
- * projection cannot take is DMX_ERR_SHAPE from the call.
+ * projection cannot take is DMX_ERR_SHAPE from the call.  With DMX_FLAG_ANGLE_DELAY_POWER in prm->flags (for this call
+ * only: the records were prepared without it) out is float32 [user_count, n_rows, n_taps], the sum of |X|^2 over rx, and with
+ * DMX_FLAG_ANGLE_DELAY_PROFILE beside it float32 [user_count, n_taps], that summed over the rows as well; both are defined at
+ * the flags above.
  *
  * dmx_angle_delay_supported - host-only: 1 if dmx_channels_angle_delay takes this shape, 0 if not (dmx_last_error() then
  * names the limit), negative on a bad argument.  No GPU involved.  Taken: freq_domain = 1, rx_filter = 0, sc_stride > 0 (a
