@@ -25,6 +25,15 @@ from .generator_utils import get_idxs_with_limits, LinearPath
 
 __version__ = consts.VERSION
 
+
+def __getattr__(name):
+    # lives beside select_serving_beam in engine.py, whose import brings torch in: resolved on first use
+    if name == "serving_clusters":
+        from .engine import serving_clusters
+        return serving_clusters
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 __all__ = ["generate", "load", "Dataset", "MacroDataset", "ChannelGenParameters", "config", "steering_vec", "wideband_array_response", "near_field_response",
            "near_field_phase", "focus_codebook", "fraunhofer_distance", "dft_codebook", "tap_delays", "delay_spread",
-           "pattern_gain", "combiner_response", "combine_rays", "precoder_response", "precode_rays", "mu_partners", "get_idxs_with_limits", "LinearPath", "DotDict", "consts"]
+           "pattern_gain", "combiner_response", "combine_rays", "precoder_response", "precode_rays", "mu_partners", "serving_clusters", "get_idxs_with_limits", "LinearPath", "DotDict", "consts"]

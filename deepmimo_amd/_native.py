@@ -19,6 +19,7 @@ FLAG_BEAM_MEAN_POWER = 64                 # DMX_FLAG_BEAM_MEAN_POWER: dmx_beam_p
 FLAG_RX_LINEAR_MMSE = 256                 # DMX_FLAG_RX_LINEAR_MMSE: per-layer SINR rate of a linear MMSE receiver; the codebook-rate calls only
 FLAG_ANGLE_DELAY_POWER = 1024             # DMX_FLAG_ANGLE_DELAY_POWER: dmx_channels_angle_delay writes sum_rx |X|^2, float32 [n, R, T]; that call only
 FLAG_ANGLE_DELAY_PROFILE = 4096           # DMX_FLAG_ANGLE_DELAY_PROFILE: beside the power flag, its row sum, float32 [n, T]
+FLAG_SERVING_SET = 16384                  # DMX_FLAG_SERVING_SET: dmx_cell_rate reads serving[u] as a set of links (bit b = link b); that call only, on every link
 
 EXPORTED_SYMBOLS = ("dmx_version", "dmx_last_error", "dmx_workspace_bytes", "dmx_decode_max_delay",
                     "dmx_path_prep", "dmx_channels_fd", "dmx_channels_td", "dmx_channels_fd_lpf",

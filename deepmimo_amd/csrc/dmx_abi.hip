@@ -37,7 +37,8 @@ static int check_patterns(const dmx_params* p) {
 // consumers, dmx_beam_power and their dmx_*_supported queries), DMX_FLAG_BEAM_MEAN_POWER (dmx_beam_power only) and
 // DMX_FLAG_RX_LINEAR_MMSE (dmx_codebook_rate, dmx_codebook_rate_subbands and their two queries only) the caller takes; a flag
 // it does not take is refused here.  DMX_FLAG_ANGLE_DELAY_POWER and DMX_FLAG_ANGLE_DELAY_PROFILE (dmx_channels_angle_delay and
-// its query only; the second only beside the first) are asked last, so that the refusals above keep their order.
+// its query only; the second only beside the first) are asked after those, so that the refusals above keep their order, and
+// DMX_FLAG_SERVING_SET (dmx_cell_rate and its query only) after them.
 static constexpr uint32_t ANGLE_DELAY_OUTPUT_FLAGS = DMX_FLAG_ANGLE_DELAY_POWER | DMX_FLAG_ANGLE_DELAY_PROFILE;
 
 static int check_params(const dmx_params* p, uint32_t takes = 0) {
@@ -51,7 +52,7 @@ static int check_params(const dmx_params* p, uint32_t takes = 0) {
     if (check_patterns(p)) return DMX_ERR_ARG;
     if (p->num_paths < 0) { set_error("num_paths must be >= 0"); return DMX_ERR_ARG; }
     if ((p->flags & ~(DMX_FLAG_ADAPTIVE_TERMS | DMX_FLAG_SPATIAL_WIDEBAND | DMX_FLAG_NEAR_FIELD | DMX_FLAG_BEAM_MEAN_POWER |
-                      DMX_FLAG_RX_LINEAR_MMSE | ANGLE_DELAY_OUTPUT_FLAGS)) != 0 ||
+                      DMX_FLAG_RX_LINEAR_MMSE | ANGLE_DELAY_OUTPUT_FLAGS | DMX_FLAG_SERVING_SET)) != 0 ||
         p->reserved0 != 0) { set_error("unknown bits in dmx_params.flags / reserved0"); return DMX_ERR_ARG; }
     if ((p->flags & DMX_FLAG_BEAM_MEAN_POWER) && !(takes & DMX_FLAG_BEAM_MEAN_POWER)) {
         set_error("DMX_FLAG_BEAM_MEAN_POWER is an option of the dmx_beam_power call alone: no other entry point takes it, "
@@ -98,6 +99,11 @@ static int check_params(const dmx_params* p, uint32_t takes = 0) {
     if ((p->flags & ANGLE_DELAY_OUTPUT_FLAGS) == DMX_FLAG_ANGLE_DELAY_PROFILE) {
         set_error("DMX_FLAG_ANGLE_DELAY_PROFILE is valid only together with DMX_FLAG_ANGLE_DELAY_POWER: the profile is the row sum "
                   "of the power matrix");
+        return DMX_ERR_ARG;
+    }
+    if ((p->flags & DMX_FLAG_SERVING_SET) && !(takes & DMX_FLAG_SERVING_SET)) {
+        set_error("DMX_FLAG_SERVING_SET is an option of the dmx_cell_rate call and its dmx_cell_rate_supported query alone: no other "
+                  "entry point takes it, dmx_path_prep included");
         return DMX_ERR_ARG;
     }
     if (p->freq_domain) {
@@ -336,6 +342,7 @@ int dmx_fd_kernel_choice(const dmx_params* prm, int32_t n_paths_loaded) {
         set_error("DMX_FLAG_ANGLE_DELAY_POWER and DMX_FLAG_ANGLE_DELAY_PROFILE are options of the dmx_channels_angle_delay call alone");
         return DMX_ERR_ARG;
     }
+    if (prm->flags & DMX_FLAG_SERVING_SET) { set_error("DMX_FLAG_SERVING_SET is an option of the dmx_cell_rate call alone"); return DMX_ERR_ARG; }
     if (prm->flags & (DMX_FLAG_SPATIAL_WIDEBAND | DMX_FLAG_NEAR_FIELD)) return 1;
     WsView ws{};
     ws.P = used_paths(prm, n_paths_loaded);
@@ -544,13 +551,29 @@ int dmx_channel_precoders(const dmx_params* prm, const void* workspace, int64_t 
 // the links in range of `n_links` (none when the count is not one the kernel takes: the shape rule refuses it)
 static int links_in_range(int32_t n_links) { return n_links >= 1 && n_links <= DMX_MAX_LINKS ? n_links : 0; }
 
+// what a link's parameter block may carry: DMX_FLAG_NEAR_FIELD per link, DMX_FLAG_SERVING_SET on every link or on none
+static constexpr uint32_t CELL_RATE_TAKES = DMX_FLAG_NEAR_FIELD | DMX_FLAG_SERVING_SET;
+
+// links whose blocks passed check_params
+static int check_serving_set_uniform(const dmx_link* links, int n_links) {
+    for (int b = 1; b < n_links; ++b) {
+        if ((links[b].prm->flags ^ links[0].prm->flags) & DMX_FLAG_SERVING_SET) {
+            set_error("DMX_FLAG_SERVING_SET is set on every link of a call or on none: link %d %s it, link 0 %s", b,
+                      links[b].prm->flags & DMX_FLAG_SERVING_SET ? "has" : "lacks",
+                      links[0].prm->flags & DMX_FLAG_SERVING_SET ? "has it" : "does not");
+            return DMX_ERR_ARG;
+        }
+    }
+    return DMX_OK;
+}
+
 // every link's parameter block
 static int check_link_params(const dmx_link* links, int32_t n_links) {
     if (!links) { set_error("links is NULL"); return DMX_ERR_ARG; }
     for (int b = 0; b < links_in_range(n_links); ++b) {
-        if (int rc = check_params(links[b].prm, DMX_FLAG_NEAR_FIELD)) return rc;
+        if (int rc = check_params(links[b].prm, CELL_RATE_TAKES)) return rc;
     }
-    return DMX_OK;
+    return check_serving_set_uniform(links, links_in_range(n_links));
 }
 
 // Every link's params are checked.
@@ -561,9 +584,10 @@ static int cell_rate_shape(const dmx_link* links, int32_t n_links) {
         return 0;
     }
     for (int b = 0; b < n_links; ++b) {
-        if (int rc = check_params(links[b].prm, DMX_FLAG_NEAR_FIELD)) return rc;
+        if (int rc = check_params(links[b].prm, CELL_RATE_TAKES)) return rc;
         if (links[b].n_paths_loaded < 0) { set_error("link %d: n_paths_loaded must be >= 0", b); return DMX_ERR_ARG; }
     }
+    if (int rc = check_serving_set_uniform(links, n_links)) return rc;
     const dmx_params* p0 = links[0].prm;
     const long long m_rx = (long long)p0->ue_shape[0] * p0->ue_shape[1];
     for (int b = 0; b < n_links; ++b) {

@@ -25,6 +25,10 @@
 // B = 1: G_int = 0, log2 det N = 0 exactly and the steps above are k7_rate<M, EPI_LOGDET>'s for M_rx <= M_tx - the same bits.
 // fp32 vector arithmetic, no atomics, every sum in a fixed order that does not depend on where the user sits in the launch.
 // LDS of one wave: max_b (M_rx + M_tx,b + kc) * P_b * 8 bytes; cell_rate_lds_bytes has the rule.
+// SET (DMX_FLAG_SERVING_SET on every link): serving[u] is a set of links, bit b = link b transmits to the user.  The same
+// steps with another destination of the adds: the members' Grams add into the serving Gram in link order (the first one is
+// copied, as the one serving link is without the flag), everything else into G_int.  A set of one bit runs the steps of that
+// index bit for bit; the full set leaves G_int = 0 and gives log2 det(I + sum_b G_b).
 #include "dmx_common.h"
 #include "k2_small_body.h"
 #include "k7_rate_body.h"
@@ -101,7 +105,7 @@ __device__ __forceinline__ void gram_reduce(const int S, float (&gr)[M * M], flo
     }
 }
 
-template <int M>
+template <int M, bool SET>
 __global__ __launch_bounds__(256) void k8_cell_rate(CellArgs a, const int32_t* __restrict__ serving, float* __restrict__ out_rate,
                                                     float* __restrict__ out_rate_k, int32_t* __restrict__ out_serving,
                                                     float* __restrict__ out_link_snr) {
@@ -118,6 +122,7 @@ __global__ __launch_bounds__(256) void k8_cell_rate(CellArgs a, const int32_t* _
     int s = 0;
     float best = -1.f;
     bool any = false;
+    int reach = 0;                                                           // bit b: link b has a kept path to the user
     for (int b = 0; b < B; ++b) {
         const WsView& ws = a.link[b].ws;
         const int n = kept_paths(ws, u);
@@ -130,14 +135,23 @@ __global__ __launch_bounds__(256) void k8_cell_rate(CellArgs a, const int32_t* _
         const float ls = (float)fmin((double)p * a.link[b].snr, 3.402823466e38);
         if (out_link_snr && lane == 0) out_link_snr[(size_t)ul * B + b] = ls;
         any = any || n > 0;
+        if (n > 0) reach |= 1 << b;
         if (ls > best) { best = ls; s = b; }                                 // strictly: the first of equal values
     }
-    if (serving) s = serving[ul]; else if (!any) s = -1;
-    s = __builtin_amdgcn_readfirstlane(s);
-    if (s < 0 || s >= B) s = -1;
-    if (out_serving && lane == 0) out_serving[ul] = s;
     int n_s = 0;
-    if (s >= 0) n_s = kept_paths(a.link[s].ws, u);
+    if constexpr (SET) {                                                     // s: the set, bit b = link b serves
+        s = serving ? serving[ul] : -1;                                      // NULL: every link
+        if (serving && s < 0) s = 0;                                         // a negative entry: nobody
+        s = __builtin_amdgcn_readfirstlane(s) & ((1 << B) - 1);              // B <= DMX_MAX_LINKS = 8
+        if (out_serving && lane == 0) out_serving[ul] = s;
+        n_s = (s & reach) != 0;                                              // a member reaches the user
+    } else {
+        if (serving) s = serving[ul]; else if (!any) s = -1;
+        s = __builtin_amdgcn_readfirstlane(s);
+        if (s < 0 || s >= B) s = -1;
+        if (out_serving && lane == 0) out_serving[ul] = s;
+        if (s >= 0) n_s = kept_paths(a.link[s].ws, u);
+    }
     if (n_s <= 0) {                                                          // not served, or no kept path to be served by
         if (ok) for (int i = lane; i < K; i += 64) ok[i] = 0.f;
         if (lane == 0) out_rate[ul] = 0.f;
@@ -150,6 +164,7 @@ __global__ __launch_bounds__(256) void k8_cell_rate(CellArgs a, const int32_t* _
         float ir[M * M], ii[M * M], sr[M * M], si[M * M];                    // G_int and the serving link's Gram, lane = k
 #pragma unroll
         for (int i = 0; i < M * M; ++i) ir[i] = ii[i] = sr[i] = si[i] = 0.f;
+        bool first = true;                                                   // SET: no member's Gram is in sr, si yet
         for (int b = 0; b < B; ++b) {
             const CellLink& lk = a.link[b];
             const int ld = lk.ws.P, Mb = lk.m_tx;
@@ -186,9 +201,14 @@ __global__ __launch_bounds__(256) void k8_cell_rate(CellArgs a, const int32_t* _
                     }
                 }
             }
-            if (b == s) {
+            const bool mine = SET ? ((s >> b) & 1) != 0 : b == s;
+            if (mine && (!SET || first)) {
 #pragma unroll
                 for (int i = 0; i < M * M; ++i) { sr[i] = gr[i]; si[i] = gi[i]; }
+                first = false;
+            } else if (mine) {
+#pragma unroll
+                for (int i = 0; i < M * M; ++i) { sr[i] += gr[i]; si[i] += gi[i]; }
             } else {
 #pragma unroll
                 for (int i = 0; i < M * M; ++i) { ir[i] += gr[i]; ii[i] += gi[i]; }
@@ -229,13 +249,17 @@ size_t cell_rate_lds_bytes(const dmx_link* links, int n_links) {
 }
 
 template <int M>
-static int launch_cell_m(const dim3 g, const dim3 b, size_t smem, hipStream_t stream, const CellArgs& a, const int32_t* serving,
-                         float* out_rate, float* out_rate_k, int32_t* out_serving, float* out_link_snr) {
-    return launch_dyn_lds(k8_cell_rate<M>, "k8_cell_rate", g, b, smem, WAVE_LDS_MAX, stream, a, serving, out_rate, out_rate_k,
-                          out_serving, out_link_snr);
+static int launch_cell_m(const bool set, const dim3 g, const dim3 b, size_t smem, hipStream_t stream, const CellArgs& a,
+                         const int32_t* serving, float* out_rate, float* out_rate_k, int32_t* out_serving, float* out_link_snr) {
+    if (set)
+        return launch_dyn_lds(k8_cell_rate<M, true>, "k8_cell_rate", g, b, smem, WAVE_LDS_MAX, stream, a, serving, out_rate,
+                              out_rate_k, out_serving, out_link_snr);
+    return launch_dyn_lds(k8_cell_rate<M, false>, "k8_cell_rate", g, b, smem, WAVE_LDS_MAX, stream, a, serving, out_rate,
+                          out_rate_k, out_serving, out_link_snr);
 }
 
-// links: checked by the caller (dmx_abi.hip, cell_rate_shape): equal ue_shape, n_subcarriers and n_selected, M_rx <= 8
+// links: checked by the caller (dmx_abi.hip, cell_rate_shape): equal ue_shape, n_subcarriers and n_selected, M_rx <= 8,
+// DMX_FLAG_SERVING_SET on every link or on none - link 0 picks the instantiation
 int launch_cell_rate(const dmx_link* links, int n_links, int64_t n_ue, int64_t user_begin, int64_t user_count,
                      const int32_t* serving, float* out_rate, float* out_rate_k, int32_t* out_serving, float* out_link_snr,
                      hipStream_t stream) {
@@ -266,17 +290,18 @@ int launch_cell_rate(const dmx_link* links, int n_links, int64_t n_ue, int64_t u
         lk.nf = near_field_of(prm);
     }
     const int m_rx = p0.ue_shape[0] * p0.ue_shape[1];
+    const bool set = (p0.flags & DMX_FLAG_SERVING_SET) != 0;
     const size_t smem = (size_t)wpb * bytes;
     const dim3 g((unsigned)((user_count + wpb - 1) / wpb)), blk(64 * wpb);  // flat: one wave per user
     switch (m_rx) {
-        case 1: return launch_cell_m<1>(g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
-        case 2: return launch_cell_m<2>(g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
-        case 3: return launch_cell_m<3>(g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
-        case 4: return launch_cell_m<4>(g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
-        case 5: return launch_cell_m<5>(g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
-        case 6: return launch_cell_m<6>(g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
-        case 7: return launch_cell_m<7>(g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
-        default: return launch_cell_m<8>(g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
+        case 1: return launch_cell_m<1>(set, g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
+        case 2: return launch_cell_m<2>(set, g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
+        case 3: return launch_cell_m<3>(set, g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
+        case 4: return launch_cell_m<4>(set, g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
+        case 5: return launch_cell_m<5>(set, g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
+        case 6: return launch_cell_m<6>(set, g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
+        case 7: return launch_cell_m<7>(set, g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
+        default: return launch_cell_m<8>(set, g, blk, smem, stream, a, serving, out_rate, out_rate_k, out_serving, out_link_snr);
     }
 }
 

@@ -1477,7 +1477,15 @@ class Dataset(DotDict):
         them.  ValueError before any GPU work: ``snr_db`` missing or not finite, a bad codebook, ``beams`` that is no int
         array [n_ue], a scheduled user whose beam is outside 0 .. B - 1, ``groups`` that is no 2-D int array, G outside
         1 .. 8, an index outside -1 .. n_ue - 1, a user that appears twice, the time domain, ``rx_filter = 1``, a UE array of
-        more than 8 elements, a near-field view.  Not cached."""
+        more than 8 elements, a near-field view.  Not cached.
+
+        Several streams per user: ``beams`` int [n_ue, L], row u the codebook rows of user u's streams, -1 padding a user
+        with fewer (the first entry of a scheduled user must be a row of F), G * L <= 8.  Link j * L + i is then stream i
+        of member j of the group - the user itself is member 0 - seen through the user's rays; the total power is split
+        equally over the valid streams of the group, and the links 0 .. L - 1 that exist are the user's serving set
+        (``MacroDataset.compute_cell_rate(serving_set=...)``): ``rate`` is the sum rate of the user's streams at a joint
+        receiver, the partners' streams coloured noise.  ``stream_snr`` is then float32 [n_ue, G * L] in link order.
+        ``beams`` [n_ue, 1] gives the bits of ``beams`` [n_ue]."""
         import torch
         from .combiner import check_tx_codebook, mu_partners
         from .engine import check_cell_rate_call
@@ -1491,42 +1499,59 @@ class Dataset(DotDict):
             own = np.asarray(beams.detach().cpu().numpy() if hasattr(beams, "detach") else beams)
         except (TypeError, ValueError):
             own = np.empty(0, object)
-        if own.dtype.kind not in "iu" or own.shape != (n_ue,):
+        multi = own.ndim == 2 and own.shape[0] == n_ue and own.shape[1] >= 1       # [n_ue, L]: streams per user
+        if own.dtype.kind not in "iu" or not (own.shape == (n_ue,) or multi):
             raise ValueError(f"{who}: beams must be an integer array of shape ({n_ue},), the codebook row of each user, got "
                              f"{own.dtype} of shape {own.shape}")
         partners, group_size, scheduled = mu_partners(groups, n_ue, who)
-        own = np.where(scheduled, own.astype(np.int64), -1)              # the beam of a user in no group is never read
+        streams = np.where(scheduled[:, None], own.astype(np.int64).reshape(n_ue, -1), -1)   # [n_ue, L]; a user in no group: never read
+        own, L = streams[:, 0], streams.shape[1]
         bad = scheduled & ((own < 0) | (own >= len(F)))
         if bad.any():
             u = int(np.flatnonzero(bad)[0])
             raise ValueError(f"{who}: user {u} is scheduled on beam {int(own[u])}, outside 0 .. {len(F) - 1}")
+        bad = (streams < -1) | (streams >= len(F))
+        if bad.any():
+            u, i = (int(v[0]) for v in np.nonzero(bad))
+            raise ValueError(f"{who}: stream {i} of user {u} is on beam {int(streams[u, i])}, outside -1 .. {len(F) - 1}")
         G = partners.shape[1] + 1
+        if G * L > 8:
+            raise ValueError(f"{who}: groups of {G} users with {L} streams each are {G * L} links, the call takes G * L <= 8")
+        n_links = G * L
         link = params.deepcopy()
         link[c.PARAMSET_ANT_BS][c.PARAMSET_ANT_SHAPE] = np.array([1, 1])
         try:
-            check_cell_rate_call([link] * G, [self._loaded_paths()] * G, snr_db)
+            check_cell_rate_call([link] * n_links, [self._loaded_paths()] * n_links, snr_db)
         except ValueError as err:
             raise ValueError(f"{who}: {err}") from None
-        # the link table: link 0 the user's own beam, link j the beam of its (j - 1)-th partner, all seen through its rays
-        idx = np.full((G, n_ue), -1, np.int64)
-        idx[0] = own
+        # the link table: links 0 .. L - 1 the user's own beams, link j L + i stream i of its (j - 1)-th partner, all seen
+        # through its rays; the power is split over the valid streams of the group
+        idx = np.full((n_links, n_ue), -1, np.int64)
+        idx[:L] = streams.T
+        total = (streams >= 0).sum(axis=1)
         for j in range(1, G):
-            idx[j] = np.where(partners[:, j - 1] >= 0, own[np.maximum(partners[:, j - 1], 0)], -1)
-        scale = np.broadcast_to(1.0 / np.sqrt(np.maximum(group_size, 1).astype(np.float64)), (G, n_ue))
-        serving = np.where(scheduled, 0, -1).astype(np.int32)
+            has, mate = partners[:, j - 1] >= 0, np.maximum(partners[:, j - 1], 0)
+            idx[j * L:(j + 1) * L] = np.where(has[None, :], streams[mate].T, -1)
+            total = total + np.where(has, (streams[mate] >= 0).sum(axis=1), 0)
+        scale = np.broadcast_to(1.0 / np.sqrt(np.maximum(total, 1).astype(np.float64)), (n_links, n_ue))
+        if multi:                                                          # the links 0 .. L - 1 that exist are the user's set
+            served = dict(serving_set=np.concatenate([streams >= 0, np.zeros((n_ue, n_links - L), bool)], axis=1))
+        else:
+            served = dict(serving=np.where(scheduled, 0, -1).astype(np.int32))
         src = self._in_hbm(_BLOCK_KEYS)                                    # the rays cross PCIe once, unprecoded
         theta, phi = src._tx_departure_angles()
         eng = _engine()
         parts = []
-        for ub, nb in self._mu_blocks(G):
+        for ub, nb in self._mu_blocks(n_links):
             users = slice(ub, ub + nb)
             links = [src._tx_view(F, idx[j:j + 1, users], theta, phi, scale[j:j + 1, users], only=_BLOCK_KEYS, users=users)
-                     for j in range(G)]
+                     for j in range(n_links)]
             preps = []
             for view in links:
                 np.random.seed(1001)
                 preps.append(view._run_prep(want_side="light")[1])
-            res = eng.cell_rate(preps, snr_db, serving=serving[users], per_subcarrier=per_subcarrier, details=details)
+            res = eng.cell_rate(preps, snr_db, per_subcarrier=per_subcarrier, details=details,
+                                **{k: v[users] for k, v in served.items()})
             parts.append(res if isinstance(res, tuple) else (res,))
         got = [p[0] if len(p) == 1 else torch.cat(p) for p in zip(*parts)]
         res = got[:2] if per_subcarrier else got[:1]
@@ -1706,7 +1731,7 @@ class MacroDataset:
         return res[0] if len(res) == 1 else res
 
     def compute_cell_rate(self, params=None, *, snr_db=None, serving=None, per_subcarrier: bool = False,
-                          details: bool = False):
+                          details: bool = False, serving_set=None):
         """Per-user downlink rate in bit/s/Hz under inter-cell interference, every child one base station over the same
         users, with no channel tensor written for any of them (extension):
 
@@ -1725,8 +1750,18 @@ class MacroDataset:
         of the child's kept paths, an RSRP-like quantity), in that order: NumPy arrays by default, the HBM-resident torch
         tensors when ``config('channel_output') == 'torch'``.  One child gives ``Dataset.compute_rate``.  At most 8
         children with equal ``n_ue``, each within the limits of ``compute_rate`` with the Gram over the UE array (at most 8
-        elements; include/deepmimo_amd.h has the rule): anything else raises ValueError before any GPU work.  Not cached."""
-        from .engine import check_cell_rate_call
+        elements; include/deepmimo_amd.h has the rule): anything else raises ValueError before any GPU work.  Not cached.
+
+        ``serving_set`` (in place of ``serving``): joint transmission - a user served by a cluster of children at once
+        (multi-TRP, CoMP, cell-free), each child an independent stream, equal power per antenna, no channel knowledge at
+        the transmitters.  ``"all"``: every child serves every user, the full-cooperation bound; or a bool or integer
+        array or tensor [n_ue, B], non-zero meaning member (``dm.serving_clusters`` builds one from ``link_snr``).  With
+        S_u the set of user u the sum over ``b != s`` above runs over the children outside S_u, the serving term over
+        those inside; a user with an empty set, or whose set reaches it on no path, gets 0.  A set of one child gives the
+        bits of ``serving`` with that index.  With ``details`` the third result is the set as read, bool [n_ue, B], in
+        place of the index.  Giving both ``serving`` and ``serving_set``, or a ``serving_set`` of another shape, dtype or
+        string, raises ValueError before any GPU work."""
+        from .engine import check_cell_rate_call, check_serving_set
         B = len(self.datasets)
         Dataset._required_snr("compute_cell_rate", snr_db, scalar=False)      # one per link: check_cell_rate_call's
         if not 1 <= B <= 8:
@@ -1742,12 +1777,13 @@ class MacroDataset:
             serving = np.asarray(serving)
             if serving.dtype.kind not in "iu" or serving.shape != (n_ue,):
                 raise ValueError(f"compute_cell_rate: serving must be None, an int or an int array of shape ({n_ue},)")
+        serving_set = check_serving_set("compute_cell_rate", serving_set, n_ue, B, serving)
         plist = [d._call_params(prm) for d, prm in zip(self.datasets, plist)]
         check_cell_rate_call(plist, [d._loaded_paths() for d in self.datasets], snr_db)
         np.random.seed(1001)
         runs = [d._run_prep(want_side="light") for d in self.datasets]
         res = runs[0][0].cell_rate([prep for _, prep in runs], snr_db, serving=serving, per_subcarrier=per_subcarrier,
-                                   details=details)
+                                   details=details, serving_set=serving_set)
         return Dataset._deliver(res)
 
     def compute_serving_beam(self, codebook, params=None, metric: str = "power"):

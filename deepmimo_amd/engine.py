@@ -454,6 +454,61 @@ def link_snrs_from_db(snr_db, n_links: int):
     return [snr_linear_from_db(snr_db)] * n_links
 
 
+def check_serving_set(who: str, serving_set, n_ue: int, n_links: int, serving=None):
+    """The `serving_set` of a cell-rate call (DMX_FLAG_SERVING_SET, include/deepmimo_amd.h), checked without a GPU: None (no
+    sets: the call without the flag), "all" (every link serves every user) or a bool or integer array / tensor
+    [n_ue, n_links], non-zero meaning that the link is a member of the user's set.  ValueError for anything else, and for
+    `serving` given beside it.  Returns None, "all" or the array / tensor as given."""
+    if serving_set is None:
+        return None
+    if serving is not None:
+        raise ValueError(f"{who}: serving and serving_set are two forms of the same argument, give one of them")
+    if isinstance(serving_set, str):
+        if serving_set != "all":
+            raise ValueError(f"{who}: serving_set must be None, 'all' or a bool or integer array of shape ({n_ue}, {n_links}), "
+                             f"got {serving_set!r}")
+        return "all"
+    if hasattr(serving_set, "detach"):
+        kind = "b" if str(serving_set.dtype) == "torch.bool" else "f" if serving_set.is_floating_point() or serving_set.is_complex() else "i"
+        shape, dtype, t = tuple(serving_set.shape), serving_set.dtype, serving_set
+    else:
+        try:
+            t = np.asarray(serving_set)
+        except (TypeError, ValueError):
+            t = np.empty(0, object)
+        kind, shape, dtype = t.dtype.kind, t.shape, t.dtype
+    if kind not in "biu" or shape != (n_ue, n_links):
+        raise ValueError(f"{who}: serving_set must be None, 'all' or a bool or integer array of shape ({n_ue}, {n_links}), got "
+                         f"{dtype} of shape {tuple(shape)}")
+    return t
+
+
+def serving_clusters(link_snr, max_size: int, within_db=None):
+    """Serving sets from the links' wideband receive SNR: per user the strongest link and further links in descending
+    `link_snr`, as a bool array [n_ue, B] for ``MacroDataset.compute_cell_rate(serving_set=...)``.  `link_snr`: [n_ue, B],
+    linear, as ``compute_cell_rate(details=True)`` returns it - it does not depend on the subcarrier selection, so a call
+    with one selected subcarrier is the cheap way to get it.  A user's set starts with its strongest link (the first on
+    ties) and grows in descending link_snr (index order on ties) until it holds `max_size` links or the next link is more
+    than `within_db` dB below the strongest (None: no such limit).  A link with link_snr == 0 - no kept path - is never a
+    member, so a user no link reaches has the empty set.  Pure NumPy."""
+    ls = np.asarray(link_snr.detach().cpu().numpy() if hasattr(link_snr, "detach") else link_snr, dtype=np.float64)
+    if ls.ndim != 2 or not np.isfinite(ls).all() or (ls < 0).any():
+        raise ValueError(f"serving_clusters: link_snr must be a finite, non-negative array [n_ue, B], got shape {ls.shape}")
+    if isinstance(max_size, bool) or not isinstance(max_size, (int, np.integer)) or max_size < 1:
+        raise ValueError(f"serving_clusters: max_size must be an integer >= 1, got {max_size!r}")
+    if within_db is not None and not (np.isfinite(within_db) and within_db >= 0):
+        raise ValueError(f"serving_clusters: within_db must be None or finite and >= 0, got {within_db!r}")
+    n_ue, B = ls.shape
+    order = np.argsort(-ls, axis=1, kind="stable")                       # descending, index order on ties
+    ranked = np.take_along_axis(ls, order, axis=1)
+    keep = (ranked > 0) & (np.arange(B)[None, :] < int(max_size))
+    if within_db is not None:
+        keep &= ranked >= ranked[:, :1] * 10.0 ** (-float(within_db) / 10.0)
+    member = np.zeros((n_ue, B), bool)
+    np.put_along_axis(member, order, keep, axis=1)
+    return member
+
+
 def check_cell_rate_call(params_list, n_paths_loaded_list, snr_db):
     """Everything `MacroDataset.compute_cell_rate` can refuse without a GPU, as ValueError: the link count, an snr_db that is
     not finite (or not one per link), time domain or rx_filter on a link, and links dmx_cell_rate_supported does not take
@@ -1103,7 +1158,7 @@ class ChannelEngine:
         return self._supported("dmx_cell_rate_supported", self._links(preps, [1.0] * len(preps)), len(preps))
 
     def cell_rate(self, preps, snr_db, serving=None, user_begin: int = 0, user_count: Optional[int] = None,
-                  per_subcarrier: bool = False, details: bool = False):
+                  per_subcarrier: bool = False, details: bool = False, serving_set=None):
         """dmx_cell_rate: per-user downlink rate in bit/s/Hz under inter-cell interference.  `preps`: one preparation per
         link (base station) over the same users; `snr_db`: total transmit power over noise power per subcarrier, a scalar or
         one value per link.  With s the serving link of a user and rho_b = snr_b / M_tx,b,
@@ -1112,7 +1167,11 @@ class ChannelEngine:
         `serving`: None (the kernel serves each user by the link of largest link_snr), an int, or an int array / tensor
         [user_count]; a value outside 0..B-1 means not served (rate 0).  Returns rate; with `per_subcarrier` also rate_k
         float32 [user_count, K]; with `details` also serving (int32 [user_count], -1 = not served) and link_snr (float32
-        [user_count, B], linear: snr_b times the summed power of the link's kept paths), in that order."""
+        [user_count, B], linear: snr_b times the summed power of the link's kept paths), in that order.
+        `serving_set` (in place of `serving`): "all", or a bool or integer array / tensor [user_count, B], non-zero meaning
+        that the link transmits to the user - DMX_FLAG_SERVING_SET on copies of the preparations' parameter blocks, for this
+        call only.  The members of a user's set add into A_k, every other link into N_k; `details` then gives the set as read,
+        bool [user_count, B], in place of the index."""
         preps = list(preps)
         B = len(preps)
         if not 1 <= B <= nat.MAX_LINKS:
@@ -1123,6 +1182,11 @@ class ChannelEngine:
             raise ValueError("cell rate: the links must cover the same users (equal n_ue)")
         user_count = self._users(n_ue, user_begin, user_count)
         serv = None
+        members = check_serving_set("cell rate", serving_set, user_count, B, serving)
+        if members is not None and not isinstance(members, str):
+            t = members if isinstance(members, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(members))
+            link = torch.arange(B, dtype=torch.int32, device=self.device)     # device work only: the call stays capturable
+            serv = ((t.to(self.device) != 0).to(torch.int32) << link).sum(dim=1, dtype=torch.int32).contiguous()
         if serving is not None:
             if isinstance(serving, (int, np.integer)) and not isinstance(serving, bool):
                 serv = torch.full((user_count,), int(np.clip(serving, -1, 2 ** 31 - 1)), dtype=torch.int32, device=self.device)
@@ -1136,10 +1200,20 @@ class ChannelEngine:
         rk = torch.empty((user_count, K), dtype=torch.float32, device=self.device) if per_subcarrier else None
         sv = torch.empty((user_count,), dtype=torch.int32, device=self.device) if details else None
         ls = torch.empty((user_count, B), dtype=torch.float32, device=self.device) if details else None
+        links = self._links(preps, snrs)
+        call_ps = []                                                        # the flagged copies live until the call returns
+        if members is not None:
+            for b, prep in enumerate(preps):
+                call_p = nat.DmxParams.from_buffer_copy(prep.params_struct)  # the pointers inside stay owned by the preparation
+                call_p.flags |= nat.FLAG_SERVING_SET
+                call_ps.append(call_p)
+                links[b].prm = C.pointer(call_p)
         with torch.cuda.device(self.device):
-            rc = self.lib.dmx_cell_rate(self._links(preps, snrs), B, n_ue, int(user_begin), int(user_count), _ptr(serv),
+            rc = self.lib.dmx_cell_rate(links, B, n_ue, int(user_begin), int(user_count), _ptr(serv),
                                         _ptr(r), _ptr(rk), _ptr(sv), _ptr(ls), self._stream_ptr())
         nat.check(rc, "dmx_cell_rate")
+        if members is not None and details:
+            sv = (sv[:, None] >> torch.arange(B, dtype=torch.int32, device=self.device)[None, :]) & 1 != 0
         res = (r,) + ((rk,) if per_subcarrier else ()) + ((sv, ls) if details else ())
         return res[0] if len(res) == 1 else res
 

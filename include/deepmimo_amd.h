@@ -237,6 +237,26 @@ typedef struct dmx_params {
 #define DMX_FLAG_ANGLE_DELAY_POWER 1024u
 #define DMX_FLAG_ANGLE_DELAY_PROFILE 4096u
 
+/* Serving sets in the cell rate: dmx_cell_rate reads `serving` as a SET of links per user in place of one index, so a user
+ * may be served by several links at once - joint transmission from a cluster of base stations (multi-TRP, CoMP, cell-free),
+ * several streams to one user in a multi-user group, or, with every link serving, the full-cooperation bound.  The model is
+ * the one of dmx_cell_rate: equal power per antenna, no channel knowledge at the transmitters, every link an independent
+ * Gaussian codebook.  The values are defined at dmx_cell_rate below.
+ * The flag (value 16384; 2, 8, 32, 128, 512, 2048 and 8192 stay unknown bits) is an option of the call and not of the
+ * preparation, like the options of the beam sweep, the codebook rate and the angle-delay call above: the workspaces are
+ * those of dmx_path_prep WITHOUT it.  It is set on every link of a call or on none: a mix is DMX_ERR_ARG, with
+ * DMX_FLAG_SERVING_SET and the first link that differs from link 0 in dmx_last_error().  Per link it combines with
+ * DMX_FLAG_ADAPTIVE_TERMS and with DMX_FLAG_NEAR_FIELD as without it; shape limits, the LDS rule and the argument checks
+ * are unchanged:
+ *   dmx_cell_rate, dmx_cell_rate_supported
+ *                         take it.
+ *   every other entry point that takes a dmx_params block - dmx_path_prep, dmx_channels_fd, dmx_channels_fd_lpf,
+ *   dmx_channels_td, dmx_channels_fd_beams, dmx_beam_power, dmx_channels_fd_direct, dmx_fd_kernel_choice, every other
+ *   consumer - and every other dmx_*_supported query: DMX_ERR_ARG, with DMX_FLAG_SERVING_SET in dmx_last_error().
+ * Not covered: precoders computed in the library, the uplink, coherent joint precoding with channel knowledge at the
+ * transmitters, more than DMX_MAX_LINKS links. */
+#define DMX_FLAG_SERVING_SET 16384u
+
 /* Subcarrier index bound of the float32-phase kernels.  The matrix-core and folded kernels (variants 2-5, 8, 10-12, the
  * beam entry points) reduce the phase dn k / N in float32 as qh (k mod 4096) + ql k, whose error grows linearly with
  * |k|: they meet the error claim above (~2e-6 of a user's peak) only while every selected |k| is below this bound.  The
@@ -540,6 +560,23 @@ int dmx_channel_precoders(const dmx_params* prm, const void* workspace, int64_t 
  * no atomics: launches repeat bit for bit, a user sub-range equals the same rows of a whole launch, a launch with fewer
  * outputs writes the same bits, and links whose users have no kept path change nothing.  Subcarrier phases are reduced in
  * float64: any int32 index is valid.
+ *
+ * With DMX_FLAG_SERVING_SET in the flags of EVERY link (for this call only: the records were prepared without it) serving[i]
+ * is a set of links: bit b (1 << b, b < n_links) means that link b transmits to the user, bits at or above n_links are
+ * ignored, a negative entry is the empty set, and serving == NULL means that every link serves every user.  With S_u the
+ * set of user u:
+ *   N_k            = I + sum_{b not in S_u} rho_b H_{b,k} H_{b,k}^H
+ *   A_k            = N_k + sum_{b in S_u} rho_b H_{b,k} H_{b,k}^H
+ *   rate_k[u, k]   = log2 det A_k - log2 det N_k,      rate[u] = 1 / K sum_k rate_k[u, k]
+ * the sum rate of the set's independent streams at a joint receiver (non-coherent joint transmission); with every link in
+ * the set N_k = I and the value is the full-cooperation rate log2 det(I + sum_b rho_b H_b H_b^H).  link_snr is unchanged.
+ * out_serving receives the set as read: the bits below n_links, 0 for a negative entry, all n_links bits for NULL.  A user
+ * whose set is empty, or none of whose set's links has a kept path, gets +0.0 in rate and rate_k; a link without a kept path
+ * contributes nothing on either side; no value is NaN, infinite or negative.  The members add into the serving Gram in link
+ * order, everything else into the interference Gram, and A_k is formed on those same floats by the same epilogue, with the
+ * same repeatability: launches repeat bit for bit, a user sub-range equals the rows of a whole launch, fewer outputs write
+ * the same bits.  A set of exactly one bit, 1 << s, writes rate, rate_k and link_snr bit-equal to the call without the flag
+ * and serving = s.  Without the flag every output bit is what it was.
  *
  * dmx_cell_rate_supported - host-only: 1 if dmx_cell_rate takes these links, 0 if not (dmx_last_error() then names the
  * limit), negative on a bad argument; workspace may be NULL.  Taken: 1 <= n_links <= DMX_MAX_LINKS; every link with
